@@ -15,10 +15,17 @@ total work is fixed).
 `--gpus N` (N > 1) without a launcher: this process starts N rank processes itself (before any GPU call) and relays
 rank 0's line.  Under `python -m torch.distributed.run` the ranks come from the environment.
 
-Prints ONE JSON line (rank 0) with the contract keys plus `roofline` (dominant kernel, live HIP event timing on the
-library's launch stream), `cpu_baseline` (the CPU oracle -- test infrastructure -- timed on a bounded sample of the
-same workload on this host) and the extra figures SURVEY.md 8d asks for (PCIe-inclusive rate, integer-VALU fraction,
-P_Skip fraction, N-process CPU baseline, output hash check, secondary configurations).
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line (rank 0) with the contract keys
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds, as before, `roofline`
+(dominant kernel, live HIP event timing on the library's launch stream during the timed steps), `cpu_baseline` (the CPU
+oracle -- test infrastructure -- timed on a bounded sample of the same workload on this host) and the extra figures
+SURVEY.md 8d asks for (PCIe-inclusive rate, integer-VALU fraction, P_Skip fraction, N-process CPU baseline, output hash
+check against the committed oracle values, secondary configurations).
+
+`--dump-outputs DIR` writes what the timed path computed in its last timed step (rank 0's streams) as .npy files:
+`rbsp_len` (float64 [pictures][streams], RBSP bytes of every picture of every stream), `nal_type` (float32, same
+shape) and `rbsp_sample` (float32 [pictures][streams][P], the RBSP bytes at P fixed, seeded fractions of each RBSP's
+length; -1 where the RBSP is empty).
 """
 import argparse
 import hashlib
@@ -38,6 +45,8 @@ ME_BYTES_PER_MB = 528          # 256 B current luma + 256 B refe
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 VALU_LANE_OPS = 78.6e12        # 256 CU x 4 SIMD x 32 lanes x 2.4 GHz
 LANE_OPS_PER_MB = 2.1e5        # the reference-exact search at WindowSize 32
+RBSP_WINDOW = 2 << 20          # bytes of RBSP read back per stream and picture (output check, --dump-outputs)
+DUMP_BYTES = 48 << 20          # --dump-outputs: budget of rbsp_sample.npy
 
 CONFIGS = {
     "1080p": dict(W=1920, H_in=1080, H=1072, gop=30, qp=12, window=32, maxdiff=3, scaling="weak",
@@ -141,12 +150,17 @@ def main():
     ap.add_argument("--streams", type=int, default=int(os.environ.get("FER_BENCH_STREAMS", "256")))
     ap.add_argument("--contexts", type=int, default=int(os.environ.get("FER_BENCH_CONTEXTS", "1")),
                     help="encoder contexts per GPU, each on its own HIP stream and host thread (streams are split evenly)")
-    ap.add_argument("--cpu-frames", type=int, default=30, help="pictures of the CPU-baseline sample: 30 = one full GOP of one stream, "
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: output "
+                    "hash check, per-kernel roofline (HIP events in the timed steps), CPU baselines, PCIe-inclusive rate, "
+                    "macroblock-type and speculation statistics, secondary configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, under 64 MB in all)")
+    ap.add_argument("--cpu-frames", type=int, default=30, help="--full: pictures of the CPU-baseline sample: 30 = one full GOP of one stream, "
                     "about 70 s on one core, run beside the GPU part (0 = skip)")
-    ap.add_argument("--cpu-nproc-frames", type=int, default=4, help="pictures each process of the N-process CPU leg encodes")
-    ap.add_argument("--secondary", type=int, default=1, help="also time configs[1] (720p I-only) and configs[4] (decode)")
-    ap.add_argument("--e2e", type=int, default=1, help="also time the PCIe-inclusive path (pinned host pictures in, host RBSP out)")
-    ap.add_argument("--probe-build", type=int, default=0, help="development only: a -DFER_PROBE library with FER_DBG set skips "
+    ap.add_argument("--cpu-nproc-frames", type=int, default=4, help="--full: pictures each process of the N-process CPU leg encodes")
+    ap.add_argument("--secondary", type=int, default=1, help="--full: also time configs[1] (720p I-only) and configs[4] (decode)")
+    ap.add_argument("--e2e", type=int, default=1, help="--full: also time the PCIe-inclusive path (pinned host pictures in, host RBSP out)")
+    ap.add_argument("--probe-build", type=int, default=0, help="--full, development only: a -DFER_PROBE library with FER_DBG set skips "
                     "stages on purpose, so a wrong output hash is reported (\"ok\": false) instead of ending the run")
     ap.add_argument("--resolve-wgs", type=int, default=0, help="workgroups of the persistent motion-chain launch (0 = library default)")
     ap.add_argument("--overlap-sort", type=int, default=0, help="0 = the sort of the reference picture runs before k_me_pre instead of beside it")
@@ -233,7 +247,7 @@ def main():
     # the CPU baseline's single-core leg (one full GOP of stream 0 through oracle/fo_cli, about 70 s) starts now and runs
     # beside the GPU part on one of the host's cores
     cpu_job = cpu_sample = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0 and args.config == "1080p":
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0 and args.config == "1080p":
         cpu_sample = parts[0][:, 0].cpu().numpy()
         tmp_ = stage_oracle_input(cpu_sample, min(args.cpu_frames, GOP), "one")
         cpu_job = (run_oracle_enc(cfg, tmp_, min(args.cpu_frames, GOP)), tmp_)
@@ -276,8 +290,20 @@ def main():
         if err:
             raise err[0]
 
-    def step():
-        threaded(run_ctx)
+    def step(sink=None):
+        threaded(lambda i: run_ctx(i, sink))
+
+    # --dump-outputs: the last timed step also copies every picture's RBSP (the first RBSP_WINDOW bytes of each stream) and
+    # lengths into device buffers, asynchronously on each context's stream behind the picture that wrote them
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = [(torch.empty((GOP, encs[i].S, RBSP_WINDOW), dtype=torch.uint8, device=dev),
+                 torch.zeros((GOP, encs[i].S), dtype=torch.int32, device=dev), [None] * GOP) for i in range(NC)]
+
+    def capture(i, t, nt):
+        buf, lens, nts = dump[i]
+        encs[i].copy_rbsp_device(buf[t].data_ptr(), lens[t].data_ptr(), stride=RBSP_WINDOW, nbytes=RBSP_WINDOW)
+        nts[t] = nt
 
     def sync():
         torch.cuda.synchronize()
@@ -287,24 +313,26 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    stats0 = [e.stats().copy() for e in encs]
-    spec0 = [e.read("SPEC_STAT").copy() for e in encs]
-    for e in encs:
-        e.get_profile(reset=True)
-        e.profile(True)
+    if args.full:
+        stats0 = [e.stats().copy() for e in encs]
+        spec0 = [e.read("SPEC_STAT").copy() for e in encs]
+        for e in encs:
+            e.get_profile(reset=True)
+            e.profile(True)
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for k in range(args.steps):
+        step(capture if dump is not None and k == args.steps - 1 else None)
     sync()
     dt = time.perf_counter() - t0
     prof = {}
     status = []
     for e in encs:
-        for k, (ms_, n_) in e.get_profile(reset=True).items():
-            a = prof.get(k, (0.0, 0))
-            prof[k] = (a[0] + ms_, a[1] + n_)
-        e.profile(False)
+        if args.full:
+            for k, (ms_, n_) in e.get_profile(reset=True).items():
+                a = prof.get(k, (0.0, 0))
+                prof[k] = (a[0] + ms_, a[1] + n_)
+            e.profile(False)
         status += e.status()
     if any(status):
         raise SystemExit(f"device error flags {status}")
@@ -312,16 +340,38 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    counts = sum((e.stats() - s0).sum(axis=0) for e, s0 in zip(encs, stats0))   # brojTipova over the timed steps
-    spec = sum((e.read("SPEC_STAT") - s0).astype("int64") for e, s0 in zip(encs, spec0))
 
     total_mbs = total_streams * GOP * nmb * args.steps
     value = total_mbs / dt
+    if dump is not None:
+        for e in encs:
+            e.sync()
+        write_outputs(Path(args.dump_outputs), dump, torch, np)
+        dump = None
+        torch.cuda.empty_cache()
+    line_ = {"metric": "macroblocks/sec encode (1080p full-search ME) + bit-exact bitstream vs ref",
+             "value": round(value, 1), "unit": "macroblocks/s", "n_gpus": world, "steps": args.steps,
+             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+             "scaling": cfg["scaling"], "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+             "config": {"workload": cfg["workload"], "content": args.content,
+                        "coded_size": f"{W}x{H}", "streams_per_gpu": S, "contexts_per_gpu": NC, "gop": GOP, "qp": cfg["qp"],
+                        "window": cfg["window"], "maxdiff": cfg["maxdiff"], "mbs_per_step": total_streams * GOP * nmb,
+                        "parallelism": f"{world} x {S} independent closed-GOP streams"}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line_), flush=True)
+        for e in encs:
+            e.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    counts = sum((e.stats() - s0).sum(axis=0) for e, s0 in zip(encs, stats0))   # brojTipova over the timed steps
+    spec = sum((e.read("SPEC_STAT") - s0).astype("int64") for e, s0 in zip(encs, spec0))
 
     # ---- output check: one more (untimed) GOP through the very path that was timed -- device pictures in, two
     # contexts on two host threads, ferhip_encode_picture_dev -- with the RBSP of every picture read back; stream 0
     # (1080p) or the merged GOP streams (4k) hashed and compared with the committed oracle value
-    cap = 2 << 20
+    cap = RBSP_WINDOW
     host_rbsp = [torch.empty((GOP, encs[i].S, cap), dtype=torch.uint8).pin_memory() for i in range(NC)]
     host_len = [torch.zeros((GOP, encs[i].S), dtype=torch.int32).pin_memory() for i in range(NC)]
     nal_types = [[None] * GOP for _ in range(NC)]
@@ -481,14 +531,7 @@ def main():
             encs.clear()
             secondary = run_secondary(pkg, torch, dev)
         coded = int(counts.sum())
-        out = {"metric": "macroblocks/sec encode (1080p full-search ME) + bit-exact bitstream vs ref",
-               "value": round(value, 1), "unit": "macroblocks/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-               "scaling": cfg["scaling"], "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-               "config": {"workload": cfg["workload"], "content": args.content,
-                          "coded_size": f"{W}x{H}", "streams_per_gpu": S, "contexts_per_gpu": NC, "gop": GOP, "qp": cfg["qp"],
-                          "window": cfg["window"], "maxdiff": cfg["maxdiff"], "mbs_per_step": total_streams * GOP * nmb,
-                          "parallelism": f"{world} x {S} independent closed-GOP streams"},
+        out = dict(line_, **{
                "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_nproc": cpu_n,
                "value_e2e": round(value_e2e, 1) if value_e2e else None,
                "value_e2e_note": "pinned host pictures in (double-buffered asynchronous H2D), host RBSP out (D2H), same streams and GOP",
@@ -498,12 +541,37 @@ def main():
                "speculation": {"partitions_decided_by_chain": int(spec[0]), "predictor_guess_hits": int(spec[1]),
                                "hit_rate": round(float(spec[1]) / max(int(spec[0]), 1), 5),
                                "pskip_verdicts": int(spec[2]), "pskip_guess_hits": int(spec[3])},
-               "output_check": check, "secondary": secondary}
+               "output_check": check, "secondary": secondary})
         print(json.dumps(out), flush=True)
     for e in encs:
         e.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def write_outputs(out_dir, dump, torch, np):
+    """--dump-outputs: the RBSP of every picture and stream of the last timed step, reduced to its lengths, NAL unit types
+    and a fixed, seeded sample of its bytes (see the module docstring)."""
+    lens = np.concatenate([ln.cpu().numpy() for _, ln, _ in dump], axis=1).astype(np.int64)   # [pictures][streams]
+    if lens.max() > RBSP_WINDOW:
+        raise SystemExit("RBSP larger than the read-back window")
+    nal = np.concatenate([np.array(nts, dtype=np.int64) for _, _, nts in dump], axis=1)
+    G, S = lens.shape
+    P = max(1, min(1024, DUMP_BYTES // (4 * G * S)))
+    frac = np.sort(np.random.default_rng(20240601).random(P))
+    pos = np.minimum((frac[None, None, :] * lens[:, :, None]).astype(np.int64), np.maximum(lens[:, :, None] - 1, 0))
+    parts, s0 = [], 0
+    for buf, _, _ in dump:
+        n = buf.shape[1]
+        idx = torch.from_numpy(pos[:, s0:s0 + n]).to(buf.device)
+        parts.append(torch.gather(buf, 2, idx).cpu().numpy())
+        s0 += n
+    sample = np.concatenate(parts, axis=1).astype(np.float32)
+    sample[lens == 0] = -1.0
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "rbsp_len.npy", lens.astype(np.float64))
+    np.save(out_dir / "nal_type.npy", nal.astype(np.float32))
+    np.save(out_dir / "rbsp_sample.npy", sample)
 
 
 def rehearse_ranks(args, rank, world, dist, torch, pkg):

@@ -21,6 +21,17 @@ def load_pkg():
     return m
 
 
+def golden_bytes(name):
+    """Contents of the fixture tests/golden/<name>; one larger than a committed file may be (1 MiB) is stored as
+    <name>.part0, <name>.part1, ... and joined here."""
+    gold = ROOT / "tests" / "golden"
+    if (gold / name).exists():
+        return (gold / name).read_bytes()
+    parts = sorted(gold.glob(name + ".part*"), key=lambda q: int(q.name[len(name) + 5:]))
+    assert parts, f"tests/golden/{name} missing"
+    return b"".join(q.read_bytes() for q in parts)
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu)")
 

@@ -11,6 +11,7 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+from conftest import golden_bytes
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -449,7 +450,7 @@ def test_gpu_decoder_reproduces_reference_md5_on_drugi(pkg):
     """The reference's own fixture F/drugi.264 (x264 baseline, 640x480, 1000 pictures, intra MBs in P
     slices, mb_qp_delta != 0) decoded on the GPU gives the md5 of the REFERENCE's output recorded in
     SURVEY.md section 4 -- a pin of the HIP decode path that does not go through the oracle."""
-    stream = (GOLD / "drugi.264").read_bytes()
+    stream = golden_bytes("drugi.264")
     out, pics, W, H = pkg.decode_streams([stream], 1000)
     assert pics == [1000] and (W, H) == (640, 480)
     h = hashlib.md5()
@@ -502,7 +503,7 @@ def test_legacy_rbsp_decode_seam(pkg, tmp_path):
     frame.C[1] = None
     lib.RBSP_decode.argtypes = [NALunit]
     lib.RBSP_decode.restype = None
-    stream = (GOLD / "drugi.264").read_bytes()
+    stream = golden_bytes("drugi.264")
     NP = 40
     nals = pkg.split_nals(stream[:4_000_000])
     want, pics, W, H = pkg.decode_streams([stream], NP)
@@ -629,7 +630,7 @@ def test_gop_shards_over_two_contexts_equal_one_continuous_run(pkg, fo):
 
 
 def test_bench_ranks_shard_the_4k_gops(pkg):
-    """bench.py --gpus 2 starts two rank processes itself (gloo rehearsal: both ranks on this GPU), each rank encodes
+    """bench.py --full --gpus 2 starts two rank processes itself (gloo rehearsal: both ranks on this GPU), each rank encodes
     its closed GOPs of the 64-picture 4K sequence with libferhip, the host merges the NAL units: the SHA-256 must be
     that of ONE continuous oracle run (tests/golden/goldens.json, BASELINE configs[3])."""
     import json
@@ -637,7 +638,7 @@ def test_bench_ranks_shard_the_4k_gops(pkg):
     import sys
     root = Path(__file__).resolve().parent.parent
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "4k", "--gpus", "2", "--dist-backend", "gloo",
-                          "--steps", "1", "--warmup", "0", "--cpu-frames", "0"], capture_output=True, text=True, timeout=600)
+                          "--steps", "1", "--warmup", "0", "--cpu-frames", "0", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"

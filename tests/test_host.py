@@ -27,8 +27,11 @@ def test_library_exports_every_declared_symbol(pkg):
 
 
 def test_create_without_gpu_fails_loudly(pkg):
-    import torch
-    if torch.cuda.is_available():
+    # asked in a fresh process: in this one, the HIP runtime libferhip.so initialised for the GPU tests that ran before
+    # can leave the runtime bundled with torch reporting no device although there is one
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True,
+                       text=True, timeout=300)
+    if r.stdout.strip().endswith("True"):
         pytest.skip("GPU present")
     with pytest.raises(pkg.FerHipError):
         pkg.FerHip(176, 144, 1)

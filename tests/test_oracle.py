@@ -15,6 +15,7 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+from conftest import golden_bytes
 
 HERE = Path(__file__).resolve().parent
 GOLD = HERE / "golden"
@@ -22,7 +23,7 @@ REF_MD5_DRUGI = "346891974ac8cafcc6bb72706e34f950"  # SURVEY.md section 4 (refer
 
 
 def test_decoder_reproduces_reference_md5_on_drugi(fo):
-    data = (GOLD / "drugi.264").read_bytes()
+    data = golden_bytes("drugi.264")
     n, frames, st = fo.decode_stream_md5(data)
     assert n == 1000 and (st["W"], st["H"]) == (640, 480)
     h = hashlib.md5()

@@ -2,22 +2,29 @@
 (every one of them includes stdafx.h -> <tchar.h>): their INITIALISER DATA is read from the reference's source text and
 compared with the oracle's tables and with the tables / formulas of the device code.
 
-Build-container only: skipped where /root/reference is absent (the GPU box).  Nothing of the reference is stored in the
-repository; the numbers are parsed at test time.  This narrows the "encoder parity unpinned" gap of DESIGN.md section 2 --
-the tables the encoder's arithmetic rests on are the reference's own -- it does not close it (the control flow around them
+The numbers are parsed by build() (oracle/Makefile, target `ref`, oracle/ref_tables.py) into
+oracle/_ref/reference_tables.json, a git-ignored build product like oracle/_ref/libfer_leaf.so: skipped where the
+reference tree was absent at build time.  Nothing of the reference is stored in the repository.  This narrows the
+"encoder parity unpinned" gap of DESIGN.md section 2 -- the tables the encoder's arithmetic rests on are the reference's own -- it does not close it (the control flow around them
 stays pinned by restatement and round trip only).
 """
 import ctypes as C
+import json
 import re
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-REF = Path("/root/reference/fer_h264/fer_h264")
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "h264-fer_amd" / "csrc"
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="reference tree not present (GPU box)")
+REF_TABLES = ROOT / "oracle" / "_ref" / "reference_tables.json"
+pytestmark = pytest.mark.skipif(not REF_TABLES.exists(), reason="oracle/_ref/reference_tables.json not built (reference tree absent)")
+
+
+def _ref(name):
+    """numbers of the reference's table `name` (oracle/ref_tables.py)"""
+    return np.array(json.loads(REF_TABLES.read_text())[name])
 
 
 def _text(path):
@@ -68,12 +75,12 @@ def _cls(i, j):
 
 
 def test_level_scale_and_level_quantize(fo):
-    ls = _ints(REF / "scaleTransform.cpp", "LevelScale").reshape(6, 4, 4)
-    lq = _ints(REF / "quantizationTransform.cpp", "LevelQuantize").reshape(6, 4, 4)
+    ls = _ref("LevelScale").reshape(6, 4, 4)
+    lq = _ref("LevelQuantize").reshape(6, 4, 4)
     L = fo.lib()
     L.fo_level_scale.restype = L.fo_level_quantize.restype = C.c_int
     v = _dev_v()
-    assert np.array_equal(v, _ints(REF / "scaleTransform.cpp", "v").reshape(6, 3))
+    assert np.array_equal(v, _ref("v").reshape(6, 3))
     for m in range(6):
         for i in range(4):
             for j in range(4):
@@ -85,18 +92,18 @@ def test_level_scale_and_level_quantize(fo):
 
 
 def test_zigzag_and_block_origins(fo):
-    zz = _ints(REF / "scaleTransform.cpp", "ZigZagReordering").reshape(16, 2)   # {y, x}
+    zz = _ref("ZigZagReordering").reshape(16, 2)   # {y, x}
     assert np.array_equal(_oracle_array(fo, "fo_zigzag", 32).reshape(16, 2), zz)
     assert np.array_equal(_dev_u8("c_zz"), zz[:, 0] * 4 + zz[:, 1])
     izz = _dev_u8("c_izz")                                                       # scan position of raster sample
     assert np.array_equal(izz[_dev_u8("c_zz")], np.arange(16))
-    so = _ints(REF / "h264_globals.cpp", "Intra4x4ScanOrder").reshape(16, 2)    # {x, y}
+    so = _ref("Intra4x4ScanOrder").reshape(16, 2)    # {x, y}
     assert np.array_equal(_oracle_array(fo, "fo_blk_xy", 32).reshape(16, 2), so)
     assert np.array_equal(_dev_u8("c_bx"), so[:, 0]) and np.array_equal(_dev_u8("c_by"), so[:, 1])
 
 
 def test_chroma_qp_table(fo):
-    q = _ints(REF / "inttransform.cpp", "qPiToQPc")
+    q = _ref("qPiToQPc")
     assert q.size == 52
     assert np.array_equal(_oracle_array(fo, "fo_qpc", 52), q)
     assert np.array_equal(_ints(CSRC / "fer_api.hip", "k_qpc"), q)
@@ -106,19 +113,18 @@ def test_chroma_qp_table(fo):
 
 
 def test_coded_block_pattern_maps(fo):
-    g = REF / "h264_globals.cpp"
     for ref_name, fo_name, dev_name in (("codeNum_to_coded_block_pattern_intra", "fo_code_to_cbp_intra", "c_code_cbp_intra"),
                                         ("codeNum_to_coded_block_pattern_inter", "fo_code_to_cbp_inter", "c_code_cbp_inter"),
                                         ("coded_block_pattern_to_codeNum_intra", "fo_cbp_intra_to_code", "c_cbp_intra_code"),
                                         ("coded_block_pattern_to_codeNum_inter", "fo_cbp_inter_to_code", "c_cbp_inter_code")):
-        r = _ints(g, ref_name)
+        r = _ref(ref_name)
         assert r.size == 48 and sorted(r) == list(range(48))
         assert np.array_equal(_oracle_array(fo, fo_name, 48), r), ref_name
         assert np.array_equal(_dev_u8(dev_name), r), ref_name
 
 
 def test_intra_to_chroma_pred_mode():
-    r = _ints(REF / "intra.cpp", "intraToChromaPredMode")
+    r = _ref("intraToChromaPredMode")
     assert list(r) == [2, 1, 0, 3]
     assert list(_ints(ROOT / "oracle" / "fo_intra.c", "intraToChroma")) == list(r)
     # the device spells the same map as a conditional chain (fer_intra.hip)
@@ -130,21 +136,18 @@ def test_macroblock_type_tables():
     """I_Macroblock_Modes / P_and_SP_macroblock_modes (F/h264_globals.cpp:25-132): the columns the hot path uses.
     Intra16x16: mb_type = 1 + Intra16x16PredMode + 4 CodedBlockPatternChroma + 12 [CodedBlockPatternLuma == 15] -- what
     k_intra_mb writes and k_dec_parse reads; P: the partition shapes behind p_part_w / p_part_h (fer_mvpred.h)."""
-    t = re.sub(r"//[^\n]*", "", _text(REF / "h264_globals.cpp"))
-    body = t[t.index("I_Macroblock_Modes"):]
-    rows = re.findall(r"\{\s*(\d+)\s*,\s*I_16x16_\w+\s*,\s*NA\s*,\s*Intra_16x16\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\}", body)
+    rows = _ref("I_Macroblock_Modes_intra16x16").tolist()
     assert len(rows) == 24
     for mbt, pred, cbc, cbl in rows:
         mbt, pred, cbc, cbl = int(mbt), int(pred), int(cbc), int(cbl)
         assert cbl in (0, 15)
         assert mbt == 1 + pred + 4 * cbc + 12 * (cbl == 15)
-    pbody = t[t.index("P_and_SP_macroblock_modes"):t.index("I_Macroblock_Modes")]
-    prow = re.findall(r"\{\s*(\d+)\s*,\s*P_\w+\s*,\s*(\d+)\s*,\s*\w+\s*,\s*\w+\s*,\s*(\d+)\s*,\s*(\d+)\s*\}", pbody)
+    prow = _ref("P_and_SP_macroblock_modes_p").tolist()
     shapes = {int(a): (int(n), int(w), int(h)) for a, n, w, h in prow}
     assert shapes == {0: (1, 16, 16), 1: (2, 16, 8), 2: (2, 8, 16), 3: (4, 8, 8), 4: (4, 8, 8)}
     dev = _text(CSRC / "fer_mvpred.h")
     assert "p_part_w(int t) { return (t == 0 || t == 1 || t == FER_P_SKIP) ? 16 : 8; }" in dev
     assert "p_part_h(int t) { return (t == 0 || t == 2 || t == FER_P_SKIP) ? 16 : 8; }" in dev
     # rows 5.. of the P table are the I rows shifted by 5 (mb_type of an intra macroblock in a P slice)
-    irows_in_p = re.findall(r"\{\s*(\d+)\s*,\s*I_16x16_\w+\s*,\s*NA\s*,\s*Intra_16x16\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\}", pbody)
+    irows_in_p = _ref("P_and_SP_macroblock_modes_intra16x16").tolist()
     assert [tuple(map(int, r)) for r in irows_in_p] == [tuple(map(int, r)) for r in rows]

@@ -1,5 +1,5 @@
-import json,glob
-for f in sorted(glob.glob("gpurun_out/ab_*.json")):
+import json,glob,os
+for f in sorted(glob.glob(os.path.join(os.environ.get("OUT", "bench_out"), "ab_*.json"))):
     try: d=json.load(open(f))
     except Exception as e: print(f,"ERR"); continue
     k=d["roofline"]["kernels"]

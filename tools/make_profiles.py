@@ -53,12 +53,12 @@ md = ["# Round 2 — rocprofv3 kernel summaries of the benchmark command", "",
       "1080p IPPP, one warm-up GOP + one timed GOP (+ the output-check GOP); MI355X.  The `at::native` kernels belong "
       "to the synthetic-input generator.", ""]
 md += stats_table("stats2", "Default: 256 streams in two contexts of 128",
-                  "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 1 --warmup 1 --cpu-frames 0 --secondary 0 --e2e 0", b2)
+                  "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --cpu-frames 0 --secondary 0 --e2e 0", b2)
 md += ["", "With two contexts the kernels of one context share the CUs with the other's: a kernel's duration includes that "
        "(the streaming kernels of the reference preparation stretch most), and the per-kernel totals add up to more than the wall "
        "time.  The isolated table follows.", ""]
 md += stats_table("stats1", "One context of 128 streams (every kernel alone on the GPU)",
-                  "... bench.py --steps 1 --warmup 1 --cpu-frames 0 --secondary 0 --e2e 0 --contexts 1 --streams 128", b1)
+                  "... bench.py --full --steps 1 --warmup 1 --cpu-frames 0 --secondary 0 --e2e 0 --contexts 1 --streams 128", b1)
 (prof / "r02_kernel_stats_bench.md").write_text("\n".join(md) + "\n")
 
 

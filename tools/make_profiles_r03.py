@@ -35,7 +35,7 @@ b1 = first_json(go / "bench_prof1.json")
 S_BENCH = b1["config"]["streams_per_gpu"]
 rows = list(csv.DictReader(open(newest(str(go / "stats1/*/*_kernel_stats.csv")))))
 md = ["# Round 3 — rocprofv3 kernel summary of the benchmark command", "",
-      "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 1 --warmup 1 --cpu-frames 0 --secondary 0 --e2e 0`", "",
+      "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --cpu-frames 0 --secondary 0 --e2e 0`", "",
       "1080p IPPP, ONE context of %d streams (the default: every kernel alone on the GPU), one warm-up GOP + one timed GOP + the "
       "output-check GOP; MI355X.  Bench line of the same run: %.2f M MB/s, roofline kernel `%s` (average launch %.1f us by HIP events "
       "inside bench.py).  The `at::native` kernels belong to the synthetic-input generator." % (S_BENCH, b1["value"] / 1e6,
