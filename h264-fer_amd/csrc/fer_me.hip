@@ -843,16 +843,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
 // record is one 12-byte load; the exact filter decides, so the candidate set and its order are the reference's).
 //
 // Control flow is kept off the scalar unit (one per CU: a state machine that produced the next 64-record batch with
-// ~30 scalar instructions made this kernel scalar-issue bound).  The slices of 16 steps j (32 slices) are cut into
-// batches by the LANES: slice k lives in lane k, an exclusive prefix of the batch counts places its batches in a
-// table in LDS, and lane b then holds the descriptor of batch b: first record, record count, bucket, "last batch of
-// its step" (where the stop test falls).  The batch loop reads descriptors with v_readlane, two batches in flight.
-// Groups of steps with more than 64 batches (flat content: thousands of positions per sum) go slice by slice.
-// sink(ok, rank, rel, D) is called for every batch by all lanes: ok = the lane holds a candidate, rank = its
-// arrival index, rel = (tx - sx) << 16 | (ty - sy) & 0xffff, D = its feature distance, info = the batch descriptor
-// (step and side, see below); it returns true to end the
-// walk at once (wave-uniform).  Returns the count; jend = the step j the walk ended in.
-// tbl = 128 dwords of LDS private to the calling wavefront.
+// ~30 scalar instructions made this kernel scalar-issue bound).  The records of the 32 slices of 16 steps j are
+// concatenated in arrival order and cut into full 64-record batches (a slice holds ~46 records on textured content,
+// so one batch per slice left them 72 % full); each lane finds its slice through a bitmap of slice starts in LDS
+// (mbcnt over the batch's 64 bits), so the slice fields and the stop tests are per lane.  Four batches in flight.
+// Groups of steps with more than 62 x 64 records (flat content: thousands of positions per sum) go slice by slice.
+// sink(ok, rank, rel, D, info) is called for every batch by all lanes: ok = the lane holds a candidate, rank = its
+// arrival index, rel = (tx - sx) << 16 | (ty - sy) & 0xffff, D = its feature distance, info = the lane's slice
+// descriptor (step j bits 8-15, bucket bits 16-30, side bit 31; a batch may span slices); it returns true (in any
+// lane) to end the walk after the batch.  Returns the count; jend = the step j the walk ended in.
+// tbl = 192 dwords of 8-byte aligned LDS private to the calling wavefront.
 // max_slice: slices with more records than this are not read (the caller bounds them otherwise) -- those of the steps
 // j > 0, and those of step 0 as well when skip0 is set.
 // probe(bucket) may return a number of candidates the slice of that bucket is KNOWN to hold (0 = unknown): when that
@@ -897,14 +897,13 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
         r1 = e[1];
         r2 = e[2];
     };
-    auto filter = [&](uint32_t info, uint32_t r0, uint32_t r1, uint32_t r2) -> bool {
-        // |tx - sx| + |ty - sy| < 280 and both half sums within 100, on u16 pairs
-        const int b_cnt = (int)(info & 127u);
+    // |tx - sx| + |ty - sy| < 280 and both half sums within 100, on u16 pairs
+    auto passes = [&](uint32_t r0, uint32_t r1) -> bool {
         uint32_t dist = __builtin_amdgcn_sad_u16(r0, sxy, 0);
         uint32_t e12 = pk_abs16(pk_sub16(r1, sp.s12));
-        bool ok = lane < b_cnt && dist < 280u && (pk_sub16(e12, 0x00640064u) & 0x80008000u) == 0x80008000u;
-        unsigned long long mk = __ballot(ok);
-        int rank = tren + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        return dist < 280u && (pk_sub16(e12, 0x00640064u) & 0x80008000u) == 0x80008000u;
+    };
+    auto feat_d = [&](uint32_t info, uint32_t r0, uint32_t r1, uint32_t r2) -> uint32_t {
         uint32_t D;
         if (!QUIRK) {
             // feature distance from the sorted payload (kar0 == a): |s0-a| + sum |si-qi| + sum |(s0-si) - (a-qi)|;
@@ -918,6 +917,14 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
             int px = min((int)(r0 >> 16), d.W - 1), py = min((int)(r0 & 0xffff), d.H - 1);
             D = (uint32_t)feat_dist_rec(F0 + ((size_t)py * d.W + px) * 6, sp);
         }
+        return D;
+    };
+    auto filter = [&](uint32_t info, uint32_t r0, uint32_t r1, uint32_t r2) -> bool {
+        const int b_cnt = (int)(info & 127u);
+        bool ok = lane < b_cnt && passes(r0, r1);
+        unsigned long long mk = __ballot(ok);
+        int rank = tren + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        const uint32_t D = feat_d(info, r0, r1, r2);
         const bool halt = sink(ok, rank, (int)pk_sub16(r0, sxy), (int)D, info);
         tren += __popcll(mk);
         return halt || tren > halt_cnt;  // the sink has what it wanted, or the caller only asked whether the count passes halt_cnt
@@ -986,36 +993,120 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
         const uint32_t st = (uint32_t)__shfl((int)kb, step + (side ? 32 : 0)), en = (uint32_t)__shfl((int)kb, step + (side ? 48 : 16));
         uint32_t cnt = (lane < 32 && en > st) ? en - st : 0u;
         if (cnt > max_slice && (j0 + step > 0 || skip0)) cnt = 0u;
-        const int nb = (int)((cnt + 63u) >> 6);
         const int a_k = side ? su[0] + j0 + step : su[0] - (j0 + step);
         const uint32_t ja = ((uint32_t)(j0 + step) << 8) | ((uint32_t)(a_k & 0x7fff) << 16) | ((uint32_t)side << 31);
-        int pre = nb;  // inclusive prefix over the lanes
+        int pre = (int)cnt;  // inclusive prefix of the records over the lanes
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) {
             int v = __shfl_up(pre, o);
             if (lane >= o) pre += v;
         }
-        const int TB = __builtin_amdgcn_readlane(pre, 31);
-        if (TB == 0) continue;
-        if (TB <= 62) {
-            // the step's last batch: the high side's last one, or the low side's when the high side is empty
-            const int nb_hi = __shfl(nb, lane | 1);
-            const bool closes = side == 1 || nb_hi == 0;
-            tbl[lane] = g0;  // empty batches behind the last one
+        const int T = __builtin_amdgcn_readlane(pre, 31);
+        if (T == 0) continue;
+        if (T <= 62 * 64) {
+            // Dense batches: the records of the group's slices, concatenated in slice order (= arrival order), are cut 64
+            // to a batch, so a batch may hold the tail of one slice and the heads of the next ones.  Each lane finds its
+            // slice from a bitmap of the slice starts (tbl[0 .. 124], bit = place in the concatenation, plus one bit at
+            // T): the starts at or below its place, counted with mbcnt, give the rank of its slice among the non-empty
+            // ones, and that indexes the slice table (tbl[128 ..]: first record - first place, descriptor).
+            const uint32_t E = (uint32_t)pre - cnt;  // first place of slice k
+            // the step's last slice: the high side, or the low side when the high side is empty
+            const uint32_t cnt_hi = (uint32_t)__shfl((int)cnt, lane | 1);
+            const bool closes = side == 1 || cnt_hi == 0u;
+            const unsigned long long ne = __ballot(cnt > 0u);
+            const int nne = __popcll(ne);
+            const int rk = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ne >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ne, 0u));
+            WAVE_LDS_SYNC();
+            tbl[lane] = 0u;
             tbl[64 + lane] = 0u;
             WAVE_LDS_SYNC();
-            for (int i = 0; __any(i < nb); i++) {
-                if (i < nb) {
-                    const int b = pre - nb + i;
-                    const uint32_t c = min(cnt - 64u * (uint32_t)i, 64u);
-                    tbl[b] = st + 64u * (uint32_t)i;
-                    tbl[64 + b] = c | ((closes && i == nb - 1) ? 128u : 0u) | ja;
-                }
+            if (cnt > 0u) {
+                __hip_atomic_fetch_or(&tbl[E >> 5], 1u << (E & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                tbl[128 + 2 * rk] = st - E - g0;
+                tbl[129 + 2 * rk] = ja | (closes ? 128u : 0u);
             }
+            if (lane == 0) __hip_atomic_fetch_or(&tbl[T >> 5], 1u << (T & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             WAVE_LDS_SYNC();
-            const uint32_t dstart = tbl[lane], dinfo = tbl[64 + lane];
-            WAVE_LDS_SYNC();
-            if (run_table(dstart, dinfo, TB)) return tren;
+            const int nbd = (T + 63) >> 6;
+            int dbase = 0;  // slice starts in front of the next batch to describe (described in order)
+            // batch b: the lane's record (stream-relative index) and its descriptor = the slice's | bit 0: last record of
+            // its slice.  b >= nbd: the stream's first record (fetched ahead, never used).
+            auto ddesc = [&](int b, uint32_t &li, uint32_t &inf) {
+                const int bb = min(b, nbd - 1);
+                const uint32_t w0 = tbl[2 * bb], w1 = tbl[2 * bb + 1], w2 = tbl[2 * bb + 2];
+                const unsigned long long M = ((unsigned long long)w1 << 32) | w0;
+                const int inc = (int)__builtin_amdgcn_mbcnt_hi(w1, __builtin_amdgcn_mbcnt_lo(w0, 0u)) + (int)((M >> lane) & 1ull);
+                const int r = min(dbase + inc - 1, nne - 1);  // (lanes past T: the last slice)
+                dbase += __popcll(M);
+                const uint32_t last = lane < 63 ? (uint32_t)((M >> (lane + 1)) & 1ull) : (w2 & 1u);
+                const uint32_t g = min(64u * (uint32_t)bb + (uint32_t)lane, (uint32_t)T - 1u);
+                const uint2 e = *(const uint2 *)&tbl[128 + 2 * r];
+                li = b < nbd ? e.x + g : 0u;
+                inf = e.y | last;
+            };
+            auto fetchl = [&](uint32_t li, uint32_t &r0, uint32_t &r1, uint32_t &r2) {
+                const uint32_t *e = (const uint32_t *)(srec_s + __umul24(li, 12u));
+                r0 = e[0];
+                r1 = e[1];
+                r2 = e[2];
+            };
+            // the stop tests of the walk fall on lanes: the first lane that closes a step with the count past 128 ends
+            // the walk there; the first lane that takes the count past halt_cnt ends it with the last record of its step
+            // in the batch.  Lanes behind the end are handed to the sink as not ok.  true = the walk is over.
+            auto dstep = [&](int b, uint32_t inf, uint32_t r0, uint32_t r1, uint32_t r2) -> bool {
+                const bool valid = 64 * b + lane < T;
+                const bool ok0 = valid && passes(r0, r1);
+                const unsigned long long mk = __ballot(ok0);
+                const int rank = tren + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                const int incl = rank + (int)ok0;
+                const int jl = (int)((inf >> 8) & 255u);
+                const unsigned long long s1 = __ballot(valid && (inf & 129u) == 129u && incl > 128);
+                const unsigned long long s2 = __ballot(valid && incl > halt_cnt);
+                unsigned long long live = __ballot(valid);
+                if (s1) live &= (2ull << (__ffsll((long long)s1) - 1)) - 1ull;
+                if (s2) {
+                    const int j2 = __builtin_amdgcn_readlane(jl, __ffsll((long long)s2) - 1);
+                    live &= __ballot(jl <= j2);
+                }
+                const bool ok = ok0 && ((live >> lane) & 1ull);
+                const bool halt = sink(ok, rank, (int)pk_sub16(r0, sxy), (int)feat_d(inf, r0, r1, r2), inf);
+                tren += __popcll(mk & live);
+                const unsigned long long hm = __ballot(halt);
+                if (hm) {  // the sink has what it wanted
+                    jend = __builtin_amdgcn_readlane(jl, __ffsll((long long)hm) - 1);
+                    return true;
+                }
+                if (s1 | s2) {
+                    jend = __builtin_amdgcn_readlane(jl, 63 - __clzll((long long)live));
+                    return true;
+                }
+                return false;
+            };
+            // four batches in flight, as in run_table
+            uint32_t lA, lB, lC, lD, iA, iB, iC, iD;
+            uint32_t A0, A1, A2, B0, B1, B2, C0, C1, C2, D0, D1, D2;
+            ddesc(0, lA, iA);
+            fetchl(lA, A0, A1, A2);
+            ddesc(1, lB, iB);
+            fetchl(lB, B0, B1, B2);
+            ddesc(2, lC, iC);
+            fetchl(lC, C0, C1, C2);
+            ddesc(3, lD, iD);
+            fetchl(lD, D0, D1, D2);
+#define DENSE_STEP(LL, II, R0, R1, R2, B) \
+            if (dstep(B, II, R0, R1, R2)) return tren; \
+            ddesc(B + 4, LL, II);                     \
+            fetchl(LL, R0, R1, R2);
+            for (int b = 0; b < nbd; b += 4) {
+                DENSE_STEP(lA, iA, A0, A1, A2, b)
+                if (b + 1 >= nbd) break;
+                DENSE_STEP(lB, iB, B0, B1, B2, b + 1)
+                if (b + 2 >= nbd) break;
+                DENSE_STEP(lC, iC, C0, C1, C2, b + 2)
+                if (b + 3 >= nbd) break;
+                DENSE_STEP(lD, iD, D0, D1, D2, b + 3)
+            }
+#undef DENSE_STEP
         } else {
             // a crowded group: slice by slice, 62 batches of a slice at a time
             for (int k = 0; k < 32; k++) {
@@ -1085,7 +1176,7 @@ __global__ __launch_bounds__(64, 8) void k_me_walk(FerDev d)
     su[4] = wave_sum((px & 3) > 1 ? 0 : v);
     const SuPk sp = su_pack(su);
     int2 *out = (int2 *)(d.st2 + pidx * FER_ST2_CAP * 2);
-    __shared__ uint32_t tbl[128];
+    __shared__ __attribute__((aligned(16))) uint32_t tbl[192];
     int jend;
     // more than FER_ST2_CAP candidates make the partition "crowded" (below): the count itself is not needed then, and
     // the step the stop test would fire in is the current one (the count is already past 128)
@@ -1255,22 +1346,22 @@ __global__ __launch_bounds__(64, 8) void k_me_walk(FerDev d)
             // the second visit of bucket su[0] repeats them), every other candidate it reads -> the list, and the
             // smallest positive distance of those (the general bound)
             int j2, dpos = 0x7fffffff;
+            // (a batch may span several slices: the sink works per lane and keeps its counters wave-uniform)
             walk_buckets_q<false>(d, s, su, sp, sx, sy, lane, tbl, 0x7fffffff, j2, [&](bool ok, int rank, int rel, int D, uint32_t info) {
                 (void)rank;
                 const int j = (int)((info >> 8) & 255u);
-                if (j > jend) return true;
-                if (j == 0 && (info >> 31)) return false;  // (the second visit of bucket su[0]: the same records)
-                if (ok && D > 0) dpos = min(dpos, D);
-                p2_add(ok && D > 0, rel, (uint32_t)D, j, (int)(info >> 31));
-                if (j == 0) {
-                    const bool z = ok && D == 0;
-                    const unsigned long long mz = __ballot(z);
-                    const int zr = zc + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mz, 0u));
-                    if (z && zr < 33) out[zr] = make_int2(rel, 0);
-                    zc += __popcll(mz);
-                    if (zc >= 33) return true;  // 33 candidates of distance 0 are the whole list: nothing else is needed
-                }
-                return false;
+                const bool in = j <= jend && !(j == 0 && (info >> 31));  // (the second visit of bucket su[0]: the same records)
+                const bool z = in && j == 0 && ok && D == 0;
+                const unsigned long long mz = __ballot(z);
+                const int zr = zc + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mz, 0u));
+                if (z && zr < 33) out[zr] = make_int2(rel, 0);
+                zc += __popcll(mz);
+                // 33 candidates of distance 0 are the whole list: nothing else is needed, and the records of later slices in
+                // the batch that completes them are not taken (the walk ends with that slice's batch)
+                const bool take = in && ok && D > 0 && (j == 0 || zc < 33);
+                if (take) dpos = min(dpos, D);
+                p2_add(take, rel, (uint32_t)D, j, (int)(info >> 31));
+                return j > jend || zc >= 33;
             }, (uint32_t)FER_BIG_SLICE, skip0);
             dmin = max(min(dmin, wave_min(dpos)), 1);
             if (zc < 33 && zc > 0) {  // the repeats of the second visit
