@@ -1480,7 +1480,7 @@ struct DecSession {
     uint32_t *d_info = nullptr;
     size_t TWmax = 0, nm = 0, fsz = 0;
     std::vector<uint32_t> info, hdr;
-    std::vector<char> anyP, anyAny, keep;
+    std::vector<char> anyP, anyAny, keep, pres;  // pres[t * S + s]: stream s has a picture at step t of the window
     // A picture whose slice carries an empty reference-list modification is NOT stored as the reference picture
     // (modificationProcess, F/ref_frames.cpp:130-183): the stream's last decoded picture (what `frame` holds, what a
     // slice that ends early leaves in place) then differs from its reference picture and waits in `hold`.
@@ -1587,10 +1587,102 @@ static int dec_copy_stream(ferhip_ctx *c, uint8_t *dst, const uint8_t *src, int 
     return 0;
 }
 
+// Per-stream error isolation of a window (the live decoder, ferhip_decs_*).  Without it the first stream that fails
+// fails the window.  With it a stream's fault ends that stream's part of the window: the faulted picture and the ones
+// after it are not reconstructed, status[s] records the FERHIP_E_* and the other streams go on.  The output then goes
+// through k_dec_out, which writes only the slots of pictures that were decoded.
+struct DecIsolate {
+    int *status = nullptr;       // [S] 0, or the first fault of stream s in this call
+    std::vector<char> stop;      // [S] stream s faulted inside a window: it takes no more pictures in this call
+    uint8_t *out = nullptr;      // [max_pictures][S][fsz]: picture k of stream s at (k * S + s) * fsz, or NULL
+    bool out_dev = false;        // out is device memory
+    int2 *d_map = nullptr;       // [TWmax][S] device: the (stream, slot) pairs of every step for k_dec_out
+    std::vector<int2> map;       // ... host side
+    std::vector<int> nmap;       // [TW] pairs per step
+    std::vector<size_t> fin;     // host output: slot (k * S + s) of the caller's buffer of every staged picture, in order
+    uint8_t *d_stage = nullptr, *h_stage = nullptr;  // host output: the window's pictures, packed, on the device and pinned
+    size_t stage_cap = 0;        // pictures
+};
+
+// After the parse of an isolated window: find each faulted stream's first faulted picture (B.state[pic * 4 + 3]), drop it
+// and the stream's later pictures from the window (macroblocks reached = 0, so the reconstruction leaves them alone),
+// clear the sticky status, then lay out the output of the pictures that remain.  pictures[s] = pictures of stream s
+// before this window.
+static int dec_isolate_faults(DecSession &ss, size_t TW, DecIsolate &iso, const int *pictures)
+{
+    ferhip_ctx *c = ss.c;
+    const int S = ss.S;
+    bool any = false;
+    for (int s = 0; s < S; s++) any |= c->h_status[s] != 0;
+    if (any) {
+        std::vector<int> st(TW * S * 4);
+        if (hipMemcpyAsync(st.data(), ss.B.state, st.size() * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
+            hipStreamSynchronize(c->st) != hipSuccess)
+            return FERHIP_E_HIP;
+        for (int s = 0; s < S; s++) {
+            if (!c->h_status[s]) continue;
+            bool hit = false;
+            for (size_t t = 0; t < TW; t++) {
+                const size_t pic = t * S + s;
+                if (!ss.pres[pic]) continue;
+                if (!hit && st[pic * 4 + 3]) {
+                    hit = true;
+                    iso.stop[s] = 1;
+                    iso.status[s] = (st[pic * 4 + 3] & FER_ERR_DEC_UNSUPPORTED) ? FERHIP_E_UNSUP : FERHIP_E_DEVICE;
+                }
+                if (hit) {
+                    ss.pres[pic] = 0;
+                    st[pic * 4 + 1] = 0;
+                }
+            }
+            if (!hit) return FERHIP_E_HIP;  // a status bit without a faulted picture: the device state is not to be trusted
+        }
+        if (hipMemcpyAsync(ss.B.state, st.data(), st.size() * 4, hipMemcpyHostToDevice, c->st) != hipSuccess ||
+            hipMemsetAsync(c->d.status, 0, sizeof(int) * S, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)
+            return FERHIP_E_HIP;
+        for (size_t t = 0; t < TW; t++) {
+            ss.anyP[t] = ss.anyAny[t] = 0;
+            for (int s = 0; s < S; s++)
+                if (ss.pres[t * S + s]) {
+                    ss.anyAny[t] = 1;
+                    ss.anyP[t] |= ss.hdr[(t * S + s) * 4 + 3] == 0;
+                }
+        }
+    }
+    if (!iso.out) return 0;
+    // output: step t writes map[t * S + k], k < nmap[t] = (stream, slot); the slot is the caller's (picture * S + stream)
+    // for device output, the next free picture of the staging buffer for host output
+    iso.map.resize(TW * S);
+    iso.nmap.assign(TW, 0);
+    iso.fin.clear();
+    for (size_t t = 0; t < TW; t++)
+        for (int s = 0; s < S; s++) {
+            if (!ss.pres[t * S + s]) continue;
+            const size_t slot = (size_t)(pictures[s] + (int)t) * S + s;
+            int2 &e = iso.map[t * S + iso.nmap[t]++];
+            e.x = s;
+            e.y = iso.out_dev ? (int)slot : (int)iso.fin.size();
+            if (!iso.out_dev) iso.fin.push_back(slot);
+        }
+    if (!iso.out_dev && iso.fin.size() > iso.stage_cap) {  // grows to the largest window seen, then stays
+        if (iso.d_stage) hipFree(iso.d_stage);
+        if (iso.h_stage) hipHostFree(iso.h_stage);
+        iso.d_stage = iso.h_stage = nullptr;
+        iso.stage_cap = 0;
+        const size_t cap = std::min(std::max(iso.fin.size(), (size_t)S), ss.TWmax * S);
+        if (hipMalloc((void **)&iso.d_stage, cap * ss.fsz) != hipSuccess || hipHostMalloc((void **)&iso.h_stage, cap * ss.fsz) != hipSuccess)
+            return FERHIP_E_HIP;
+        iso.stage_cap = cap;
+    }
+    if (hipMemcpyAsync(iso.d_map, iso.map.data(), TW * S * sizeof(int2), hipMemcpyHostToDevice, c->st) != hipSuccess) return FERHIP_E_HIP;
+    return 0;
+}
+
 // Decode pictures [t0, t0 + TW) of every stream: slices[s][t] = the slice NAL of picture t of stream s (streams may
-// be shorter).  out (host, may be NULL) receives picture t of stream s at (t * S + s) * fsz; pictures[s] counts.
+// be shorter; nullptr = no picture at that step).  out (host, may be NULL) receives picture t of stream s at
+// (t * S + s) * fsz; pictures[s] counts.  iso: see DecIsolate (out is then unused).
 static int dec_session_window(DecSession &ss, const std::vector<std::vector<const NalRef *>> &slices, size_t t0, size_t TW,
-                              uint8_t *out, int *pictures)
+                              uint8_t *out, int *pictures, DecIsolate *iso = nullptr)
 {
     ferhip_ctx *c = ss.c;
     FerDev &d = c->d;
@@ -1604,6 +1696,7 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
     ss.anyP.assign(TW, 0);
     ss.anyAny.assign(TW, 0);
     ss.keep.assign(TW * S, 1);
+    ss.pres.assign(TW * S, 0);
     // slice headers and the offsets of the slices in the window's RBSP buffer
     size_t total = 0;
     for (size_t t = 0; t < TW; t++)
@@ -1611,11 +1704,20 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             uint32_t *in = &ss.info[(t * S + s) * 6];
             uint32_t *hd = &ss.hdr[(t * S + s) * 4];
             hd[3] = 2;
-            if (t0 + t >= slices[s].size()) continue;
+            if (t0 + t >= slices[s].size() || !slices[s][t0 + t] || (iso && iso->stop[s])) continue;
             const NalRef &n = *slices[s][t0 + t];
             int ov = 0;
             int rc = dec_parse_slice_header(ss.hs[s], n.rbsp.data(), n.rbsp.size(), n.type, n.ref_idc, in, ov);
-            if (rc) return rc;
+            // a header that runs past the end of its NAL unit, or a SliceQPY outside 0..51: damaged
+            if (!rc && iso && (in[1] > n.rbsp.size() * 8 || in[3] > 51)) rc = FERHIP_E_ARG;
+            if (rc) {
+                if (!iso) return rc;
+                iso->status[s] = rc;
+                iso->stop[s] = 1;
+                for (int k = 0; k < 6; k++) in[k] = 0;
+                continue;
+            }
+            ss.pres[t * S + s] = 1;
             in[4] = (uint32_t)total;
             in[5] = (uint32_t)(total >> 32);
             total += (n.rbsp.size() + 15) & ~(size_t)15;
@@ -1642,7 +1744,7 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         auto gather = [&](int k) {
             for (int s = k; s < S; s += nth)
                 for (size_t t = 0; t < TW; t++) {
-                    if (t0 + t >= slices[s].size()) continue;
+                    if (!ss.pres[t * S + s]) continue;
                     const NalRef &n = *slices[s][t0 + t];
                     const uint32_t *in = &ss.info[(t * S + s) * 6];
                     memcpy(ar->h_rbsp + (((size_t)in[5] << 32) | in[4]), n.rbsp.data(), n.rbsp.size());
@@ -1670,11 +1772,16 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
     if (hipMemcpyAsync(c->h_status, d.status, sizeof(int) * S, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
         hipStreamSynchronize(c->st) != hipSuccess || hipGetLastError() != hipSuccess)
         return FERHIP_E_HIP;
-    for (int s = 0; s < S; s++)
-        if (c->h_status[s]) {
-            fprintf(stderr, "ferhip: stream %d decode status 0x%x\n", s, c->h_status[s]);
-            return (c->h_status[s] & FER_ERR_DEC_UNSUPPORTED) ? FERHIP_E_UNSUP : FERHIP_E_DEVICE;
-        }
+    if (iso) {
+        int rc = dec_isolate_faults(ss, TW, *iso, pictures);
+        if (rc) return rc;
+    } else {
+        for (int s = 0; s < S; s++)
+            if (c->h_status[s]) {
+                fprintf(stderr, "ferhip: stream %d decode status 0x%x\n", s, c->h_status[s]);
+                return (c->h_status[s] & FER_ERR_DEC_UNSUPPORTED) ? FERHIP_E_UNSUP : FERHIP_E_DEVICE;
+            }
+    }
     ss.t_parse += dec_now() - ta;
     ta = dec_now();
     for (size_t t = 0; t < TW; t++) {
@@ -1684,7 +1791,7 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             hipSuccess)
             return FERHIP_E_HIP;
         for (int s = 0; s < S; s++)  // ... which, for a stream whose last picture was not stored as reference, waits in `hold`
-            if (ss.held[s] && dec_copy_stream(c, c->planes[c->cur_set], ss.hold, s)) return FERHIP_E_HIP;
+            if (ss.held[s] && (!iso || ss.pres[t * S + s]) && dec_copy_stream(c, c->planes[c->cur_set], ss.hold, s)) return FERHIP_E_HIP;
         FerDev ds = d;  // this picture's slice of the window
         const size_t o = t * nm;
         ds.mb_type = B.mb_type + o;
@@ -1701,12 +1808,16 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         fer_launch_decode_recon(ds, ss.anyP[t] != 0, true, c->st);
         c->cur_set ^= 1;  // the decoded picture becomes the reference (modificationProcess -> frameDeepCopy)
         bind_planes(c);
-        if (out) {
+        if (iso) {
+            if (iso->out)
+                fer_launch_decode_out(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], iso->out_dev ? iso->out : iso->d_stage,
+                                      c->st);
+        } else if (out) {
             int rc = ferhip_get_recon(c, out + (t0 + t) * S * ss.fsz, 1);
             if (rc) return rc;
         }
         for (int s = 0; s < S; s++) {
-            if (t0 + t >= slices[s].size()) continue;
+            if (!ss.pres[t * S + s]) continue;
             if (!ss.keep[t * S + s]) {
                 // not stored: the picture moves to `hold`, the stream's reference picture (still intact in the other
                 // set) moves back into the reference set
@@ -1723,9 +1834,29 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         }
         if (pictures)
             for (int s = 0; s < S; s++)
-                if (t0 + t < slices[s].size()) pictures[s]++;
+                if (ss.pres[t * S + s]) pictures[s]++;
+    }
+    size_t staged = 0;
+    if (iso && iso->out && !iso->out_dev) {
+        for (size_t t = 0; t < TW; t++) staged += (size_t)iso->nmap[t];
+        if (staged && hipMemcpyAsync(iso->h_stage, iso->d_stage, staged * ss.fsz, hipMemcpyDeviceToHost, c->st) != hipSuccess)
+            return FERHIP_E_HIP;
     }
     if (hipStreamSynchronize(c->st) != hipSuccess || hipGetLastError() != hipSuccess) return FERHIP_E_HIP;
+    if (staged) {  // the staged pictures to their slots of the caller's buffer (nothing else of it is written)
+        const size_t fsz = ss.fsz;
+        auto scatter = [&](size_t j0, size_t j1) {
+            for (size_t j = j0; j < j1; j++) memcpy(iso->out + iso->fin[j] * fsz, iso->h_stage + j * fsz, fsz);
+        };
+        const size_t nth = std::min<size_t>(std::min<size_t>(staged * fsz >> 23, 16), std::max(1u, std::thread::hardware_concurrency()));
+        if (nth <= 1) {
+            scatter(0, staged);
+        } else {
+            std::vector<std::thread> th;
+            for (size_t k = 0; k < nth; k++) th.emplace_back(scatter, staged * k / nth, staged * (k + 1) / nth);
+            for (auto &x : th) x.join();
+        }
+    }
     ss.t_recon += dec_now() - ta;
     return 0;
 }
@@ -1883,6 +2014,181 @@ extern "C" int ferhip_dec_nal(ferhip_dec *dc, int nal_unit_type, int nal_ref_idc
     if (width) *width = dc->h.W;
     if (height) *height = dc->h.H;
     return 0;
+}
+
+// ---- live decoder: S streams that arrive piece by piece, one window of all of them per call ----
+struct ferhip_decs {
+    DecSession ss;
+    int S = 0, W = 0, H = 0, P = 0;
+    std::vector<std::vector<uint8_t>> store;  // RBSP of each stream's chunk (kept between calls)
+    std::vector<std::vector<NalRef>> nals;
+    std::vector<size_t> cursor;               // next NAL unit of each stream's chunk
+    std::vector<int> queued;                  // slice NAL units taken from each stream's chunk in this call
+    std::vector<char> need_idr;               // after a fault: P slices are refused until an IDR slice
+    DecIsolate iso;
+};
+
+// Stream s back to the state of a new decoder; forget_ps = also forget its parameter sets, else keep them and refuse
+// P slices until the next IDR slice
+static int decs_reset(ferhip_decs *d, int s, bool forget_ps)
+{
+    ferhip_ctx *c = d->ss.c;
+    const FerDev &dv = c->d;
+    const size_t S = (size_t)d->S;
+    hipError_t e = hipMemsetAsync(dv.dec_state + s * 4, 0, 4 * sizeof(int), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(dv.dec_cac + s * 128, 0, 128 * sizeof(int16_t), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(dv.status + s, 0, sizeof(int), c->st);
+    const size_t off[3] = {(size_t)s * dv.ysz, S * dv.ysz + (size_t)s * dv.csz, S * (dv.ysz + dv.csz) + (size_t)s * dv.csz};
+    const size_t len[3] = {dv.ysz, dv.csz, dv.csz};
+    for (int set = 0; set < 2; set++)
+        for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMemsetAsync(c->planes[set] + off[k], 0, len[k], c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess) return FERHIP_E_HIP;
+    d->ss.held[s] = 0;
+    DecHdr &h = d->ss.hs[s];
+    if (forget_ps) {
+        h = DecHdr{};
+    } else {
+        h.nref_active_minus1 = h.mod_flag = h.mod_copies = 0;
+    }
+    d->need_idr[s] = !forget_ps;
+    return 0;
+}
+
+extern "C" int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, int height, int max_pictures)
+{
+    if (!out) return FERHIP_E_ARG;
+    *out = nullptr;
+    if (nstreams <= 0 || width <= 0 || height <= 0 || width % 16 || height % 16 || max_pictures <= 0) return FERHIP_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        fprintf(stderr, "ferhip: no HIP device; the hot path has no CPU fallback\n");
+        return FERHIP_E_HIP;
+    }
+    ferhip_decs *d = new ferhip_decs();
+    int rc = dec_session_open(d->ss, width, height, nstreams, (size_t)max_pictures, false);
+    if (rc) {
+        delete d;
+        return rc;
+    }
+    d->S = nstreams;
+    d->W = width;
+    d->H = height;
+    d->P = max_pictures;
+    d->store.resize(nstreams);
+    d->nals.resize(nstreams);
+    d->cursor.assign(nstreams, 0);
+    d->queued.assign(nstreams, 0);
+    d->need_idr.assign(nstreams, 0);
+    if (hipMalloc((void **)&d->iso.d_map, d->ss.TWmax * nstreams * sizeof(int2)) != hipSuccess) {
+        ferhip_decs_destroy(d);
+        return FERHIP_E_HIP;
+    }
+    *out = d;
+    return 0;
+}
+
+extern "C" void ferhip_decs_destroy(ferhip_decs *d)
+{
+    if (!d) return;
+    if (d->ss.c) {
+        (void)hipSetDevice(d->ss.c->device);
+        hipStreamSynchronize(d->ss.c->st);
+    }
+    if (d->iso.d_map) hipFree(d->iso.d_map);
+    if (d->iso.d_stage) hipFree(d->iso.d_stage);
+    if (d->iso.h_stage) hipHostFree(d->iso.h_stage);
+    dec_session_close(d->ss);
+    delete d;
+}
+
+extern "C" int ferhip_decs_reset_stream(ferhip_decs *d, int s)
+{
+    if (!d || s < 0 || s >= d->S) return FERHIP_E_ARG;
+    (void)hipSetDevice(d->ss.c->device);
+    return decs_reset(d, s, true);
+}
+
+// Take stream s's next NAL units up to the first parameter set that follows a slice (that one belongs to the next
+// window: a slice is parsed with the parameter sets that precede it), appending its slices to `slices`.
+static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices, int *status)
+{
+    DecHdr &h = d->ss.hs[s];
+    std::vector<NalRef> &nals = d->nals[s];
+    for (size_t &i = d->cursor[s]; i < nals.size() && !status[s]; i++) {
+        const NalRef &n = nals[i];
+        HostBR r{n.rbsp.data(), n.rbsp.size(), 0};
+        if (n.type == 7 || n.type == 8) {
+            if (!slices.empty()) return;
+            DecHdr hn = h;
+            int rc = n.type == 7 ? dec_parse_sps(hn, r) : dec_parse_pps(hn, r);
+            if (!rc && n.type == 7 && (hn.W != d->W || hn.H != d->H)) rc = FERHIP_E_UNSUP;  // one picture size per decoder
+            if (rc)
+                status[s] = rc;
+            else
+                h = hn;
+        } else if (n.type == 1 || n.type == 5) {
+            if (!h.have_sps || !h.have_pps || (n.type == 1 && d->need_idr[s]))
+                status[s] = FERHIP_E_STATE;
+            else if (d->queued[s] >= d->P)
+                status[s] = FERHIP_E_ARG;
+            else {
+                slices.push_back(&n);
+                d->queued[s]++;
+                if (n.type == 5) d->need_idr[s] = 0;
+            }
+        }  // every other NAL unit type (SEI, AUD ...) is ignored, as in the reference
+    }
+}
+
+extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
+                                  int *pictures, int *status)
+{
+    if (!d || !chunks || !lens || !pictures || !status) return FERHIP_E_ARG;
+    const int S = d->S;
+    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
+    size_t bytes = 0;
+    for (int s = 0; s < S; s++) {
+        pictures[s] = status[s] = 0;
+        d->nals[s].clear();
+        d->cursor[s] = 0;
+        d->queued[s] = 0;
+        if (chunks[s] && lens[s]) bytes += lens[s];
+    }
+    {  // NAL splitting: a few threads when there is much of it
+        const int nth = bytes < ((size_t)1 << 20) ? 1 : std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
+        auto split = [&](int k) {
+            for (int s = k; s < S; s += nth)
+                if (chunks[s] && lens[s]) split_stream(chunks[s], lens[s], d->nals[s], d->store[s]);
+        };
+        if (nth == 1) {
+            split(0);
+        } else {
+            std::vector<std::thread> th;
+            for (int k = 0; k < nth; k++) th.emplace_back(split, k);
+            for (auto &x : th) x.join();
+        }
+    }
+    d->iso.status = status;
+    d->iso.stop.assign(S, 0);
+    d->iso.out = out;
+    d->iso.out_dev = out_on_device != 0;
+    std::vector<std::vector<const NalRef *>> slices(S);
+    int rc = 0;
+    for (;;) {  // one window per call, unless a chunk carries a parameter set behind one of its slices
+        size_t T = 0;
+        for (int s = 0; s < S; s++) {
+            slices[s].clear();
+            decs_take(d, s, slices[s], status);
+            T = std::max(T, slices[s].size());
+        }
+        if (T == 0) break;
+        for (size_t t0 = 0; t0 < T && !rc; t0 += d->ss.TWmax) rc = dec_session_window(d->ss, slices, t0, std::min(d->ss.TWmax, T - t0), nullptr, pictures, &d->iso);
+        if (rc) break;
+    }
+    for (int s = 0; s < S && !rc; s++)
+        if (status[s]) rc = decs_reset(d, s, false);
+    return rc;
 }
 
 // ---- block-level KATs: the reference's per-block entry points (F/quantizationTransform.h, F/scaleTransform.h) as

@@ -22,6 +22,10 @@
 #include "fer_intra_dev.h"
 #include "fer_mvpred.h"
 
+#include <algorithm>
+#include <map>
+#include <mutex>
+
 // Bit reader over one slice: a 64-bit window of the stream starting at the 32-bit aligned position wbase (big-endian),
 // refilled 32 bits at a time.  The stream itself comes in through a 512-byte ring in LDS, one coalesced 256-byte load of
 // the whole wavefront per 2 048 bits: a refill is then a DS read, not a trip to memory (a dword requested from memory
@@ -144,7 +148,9 @@ struct DecLutsLds {  // the same tables, resident in LDS for one parse wavefront
     uint16_t rb[6][8];
     uint16_t lev[DEC_LEV_STATES][1 << DEC_LEV_BITS];
 };
-static DecLuts *g_dec_luts = nullptr;
+// the decode tables of every device that has decoded (built on first use, kept until exit)
+static std::mutex g_dec_luts_mu;
+static std::map<int, DecLuts *> g_dec_luts;
 
 // second build step: split the 16-bit coeff_token table by its first 8 bits
 __global__ void k_dec_split_luts(DecLuts *L)
@@ -539,6 +545,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
         if (i_size == 0) {  // no picture for this stream at this step
             if (lane == 0) {
                 st[1] = 0;
+                st[3] = 0;
                 summ[0] = summ[3] = 0;
             }
             continue;
@@ -555,6 +562,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
         for (int i = lane; i < 2 * 4 * 16; i += 64) (&cac[0][0][0])[i] = 0;
         DEC_WSYNC();
         int cur = 0;
+        int perr = 0;  // the error that ended this picture's parse (d.status only says which stream)
         bool more = true;
         int mvd[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
         int sub[4] = {0, 0, 0, 0};
@@ -598,6 +606,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
             int t = (int)db_ue(b);
             if (t > 31 || (stype == 2 && t > 24)) {
                 atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                perr = FER_ERR_DEC_SYNTAX;
                 break;
             }
             mbt[cur] = t;
@@ -607,6 +616,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
             const bool inter = !i4 && !i16;
             if ((t == 25 && stype == 2) || (t == 30 && stype != 2)) {
                 atomicOr(&d.status[s], FER_ERR_DEC_UNSUPPORTED);  // I_PCM
+                perr = FER_ERR_DEC_UNSUPPORTED;
                 break;
             }
             int chroma_mode = 0;
@@ -622,6 +632,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
                     }
                     if (badsub) {
                         atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                        perr = FER_ERR_DEC_SYNTAX;
                         break;
                     }
                     if (ref_sub && t != FER_P_8x8ref0)
@@ -662,6 +673,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
                 chroma_mode = (int)db_ue(b);
                 if (chroma_mode > 3) {
                     atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                    perr = FER_ERR_DEC_SYNTAX;
                     break;
                 }
             }
@@ -670,6 +682,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
                 unsigned code = db_ue(b);
                 if (code > 47) {
                     atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                    perr = FER_ERR_DEC_SYNTAX;
                     break;
                 }
                 int cbp = i4 ? c_code_cbp_intra[code] : c_code_cbp_inter[code];
@@ -726,6 +739,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
             DP_MARK(1)
             if (bad) {
                 atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                perr = FER_ERR_DEC_SYNTAX;
                 break;
             }
             // chroma AC of this macroblock = the persistent ChromaACLevel (stale when cbp == 0)
@@ -798,6 +812,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
         for (int i = lane; i < 128; i += 64) B.cac_out[pic * 128 + i] = (&cac[0][0][0])[i];
         if (lane == 0) {
             st[1] = cur;  // macroblocks reached (the rest of the picture keeps the previous content)
+            st[3] = perr;
             summ[0] = delta_known;
             summ[1] = mb_qp_delta;
             summ[2] = n_inherit;
@@ -1050,20 +1065,39 @@ __global__ __launch_bounds__(64) void k_dec_intra(FerDev d, int diag)
     recon_chroma(d, lv, lane, dec_qpc(d, s, QPy), &L.predC[0][0][0], Cp[0], Cp[1], Wc, xp, yp);
 }
 
+// the decode tables of the current device; null if they cannot be allocated
+static const DecLuts *dec_luts(hipStream_t st)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lk(g_dec_luts_mu);
+    auto it = g_dec_luts.find(dev);
+    if (it != g_dec_luts.end()) return it->second;
+    // once per device: invert the code tables.  The build is waited for before the tables are published, so a decoder
+    // on another stream of the same device never reads them half-built.
+    DecLuts *L = nullptr;
+    if (hipMalloc((void **)&L, sizeof(DecLuts)) != hipSuccess) return nullptr;
+    hipMemsetAsync(L, 0, sizeof(DecLuts), st);
+    hipLaunchKernelGGL(k_dec_build_luts, dim3(256), dim3(256), 0, st, L);
+    hipLaunchKernelGGL(k_dec_split_luts, dim3(4), dim3(256), 0, st, L);
+    if (hipStreamSynchronize(st) != hipSuccess) {
+        hipFree(L);
+        return nullptr;
+    }
+    g_dec_luts[dev] = L;
+    return L;
+}
+
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st)
 {
-    if (!g_dec_luts) {  // once per process: invert the code tables (the buffer lives until exit)
-        if (hipMalloc((void **)&g_dec_luts, sizeof(DecLuts)) != hipSuccess) return;
-        hipMemsetAsync(g_dec_luts, 0, sizeof(DecLuts), st);
-        hipLaunchKernelGGL(k_dec_build_luts, dim3(256), dim3(256), 0, st, g_dec_luts);
-        hipLaunchKernelGGL(k_dec_split_luts, dim3(4), dim3(256), 0, st, g_dec_luts);
-    }
+    const DecLuts *luts = dec_luts(st);
+    if (!luts) return;
     // static LDS of k_dec_parse<PW>: the tables + PW * (tcur 24 + stream ring 512 + ChromaACLevel 256 + the macroblock's levels); dynamic: the rows
     const size_t fixed = sizeof(DecLutsLds), per_wave = 24 + 512 + 256 + FER_LEVELS * 2 + (size_t)d.mbw * (sizeof(DecNb) + 2);
     const int npic = d.S * B.TW;
 #define DEC_PARSE_LAUNCH(PW)                                                                                                          \
     hipLaunchKernelGGL(k_dec_parse<PW>, dim3((npic + PW - 1) / PW), dim3(64 * PW), (size_t)PW * d.mbw * (sizeof(DecNb) + 2), st, d, B, \
-                       g_dec_luts)
+                       luts)
     const size_t lds = 160 * 1024 - 512;
     hipMemsetAsync(B.state + 2, 0, sizeof(int), st);
     if (fixed + 16 * per_wave <= lds)
@@ -1087,5 +1121,36 @@ void fer_launch_decode_recon(const FerDev &d, bool anyP, bool anyIntra, hipStrea
         int ndiag = d.mbw + 2 * (d.mbh - 1);
         int maxk = min(d.mbh, (d.mbw + 1) / 2);
         for (int dg = 0; dg < ndiag; dg++) hipLaunchKernelGGL(k_dec_intra, dim3(maxk, d.S), dim3(64), 0, st, d, dg);
+    }
+}
+
+// The decoded pictures of one step, from the plane-major picture set `set` ([S] Y, [S] Cb, [S] Cr) into I420 slots of
+// W*H*3/2 bytes: map[j] = (stream, slot), blockIdx.y = j.  Consecutive lanes move consecutive V-sized pieces of a slot
+// (every plane is a multiple of 64 bytes, so a piece never straddles two); no other slot is touched.
+template <typename V>
+__global__ __launch_bounds__(256) void k_dec_out(const uint8_t *__restrict__ set, const int2 *__restrict__ map, uint8_t *__restrict__ dst,
+                                                 int S, size_t ysz, size_t csz)
+{
+    const int2 m = map[blockIdx.y];
+    const size_t fsz = ysz + 2 * csz, n = fsz / sizeof(V);
+    const V *sy = (const V *)(set + (size_t)m.x * ysz);
+    const V *su = (const V *)(set + (size_t)S * ysz + (size_t)m.x * csz);
+    const V *sv = (const V *)(set + (size_t)S * (ysz + csz) + (size_t)m.x * csz);
+    V *o = (V *)(dst + (size_t)m.y * fsz);
+    const size_t ny = ysz / sizeof(V), nc = csz / sizeof(V);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        o[i] = i < ny ? sy[i] : (i < ny + nc ? su[i - ny] : sv[i - ny - nc]);
+}
+
+void fer_launch_decode_out(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, hipStream_t st)
+{
+    if (n <= 0) return;
+    const size_t fsz = d.ysz + 2 * d.csz;
+    if (((uintptr_t)dst & 15) == 0) {
+        const unsigned nb = (unsigned)std::min<size_t>((fsz / 16 + 255) / 256, 1024);
+        hipLaunchKernelGGL(k_dec_out<uint4>, dim3(nb, n), dim3(256), 0, st, set, map, dst, d.S, d.ysz, d.csz);
+    } else {  // a caller's buffer that is not 16-byte aligned (a view into a larger tensor): byte by byte
+        const unsigned nb = (unsigned)std::min<size_t>((fsz + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_dec_out<uint8_t>, dim3(nb, n), dim3(256), 0, st, set, map, dst, d.S, d.ysz, d.csz);
     }
 }

@@ -142,7 +142,7 @@ struct DecBatch {
     uint8_t *dec_qp;
     uint8_t *carry;       // [TW][S][nmb] 1 = the macroblock's chroma AC levels are the block carried into its picture
     uint32_t *hdr;        // [TW][S][4] like FerDev.hdr (slice type in [3])
-    int *state;           // [TW][S][4]: [0] mb_qp_delta carried into the picture, [1] macroblocks reached
+    int *state;           // [TW][S][4]: [0] mb_qp_delta carried into the picture, [1] macroblocks reached, [3] FER_ERR_DEC_* of its parse
     int *summ;            // [TW][S][4]: parsed a mb_qp_delta?, its last value, macroblocks before the first one, wrote chroma AC?
     int16_t *cac_in;      // [TW][S][128] ChromaACLevel carried into the picture
     int16_t *cac_out;     // [TW][S][128] ... left behind by it

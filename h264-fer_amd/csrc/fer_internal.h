@@ -32,3 +32,5 @@ void fer_launch_cavlc(const FerDev &d, hipStream_t st);
 void fer_launch_block_kat(int qP, const int32_t *in, int32_t *out, int keep_dc, int inverse, size_t n, hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);
+// map[j] = (stream, slot): picture of stream map[j].x in `set` -> dst + map[j].y * W*H*3/2 (I420), for j < n
+void fer_launch_decode_out(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, hipStream_t st);

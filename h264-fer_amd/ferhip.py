@@ -82,6 +82,11 @@ def load_library():
     lib.ferhip_dec_destroy.argtypes = [vp]
     lib.ferhip_dec_destroy.restype = None
     lib.ferhip_dec_nal.argtypes = [vp, i, i, vp, sz, vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_decs_create.argtypes = [C.POINTER(vp), i, i, i, i]
+    lib.ferhip_decs_decode.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_decs_reset_stream.argtypes = [vp, i]
+    lib.ferhip_decs_destroy.argtypes = [vp]
+    lib.ferhip_decs_destroy.restype = None
     lib.ferhip_y4m_open.argtypes = [C.POINTER(vp), C.c_char_p, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     lib.ferhip_y4m_read.argtypes = [vp, vp]
     lib.ferhip_y4m_close.argtypes = [vp]
@@ -420,6 +425,95 @@ class Decoder:
             self.close()
         except Exception:
             pass
+
+
+class LiveDecoder:
+    """Live decoder for nstreams streams of one coded picture size (ferhip_decs_*): each decode() call takes whatever
+    every stream has now (whole NAL units, see access_units) and decodes all of it together.  A stream's faults come
+    back in `status` and do not disturb the other streams."""
+
+    def __init__(self, nstreams, width, height, max_pictures=1):
+        self.lib = load_library()
+        self.S, self.W, self.H, self.P = nstreams, width, height, max_pictures
+        self.fsz = width * height * 3 // 2
+        self.h = C.c_void_p()
+        _chk(self.lib.ferhip_decs_create(C.byref(self.h), nstreams, width, height, max_pictures), "ferhip_decs_create")
+
+    def decode(self, chunks, out=None):
+        """chunks: one bytes or None per stream.  out: [max_pictures][S][W*H*3/2] uint8 -- a NumPy array, a DeviceBuffer,
+        a torch tensor on the CPU or on the decoder's device -- or None for a new zeroed NumPy array.  -> (out, pictures,
+        status): picture k of stream s in out[k, s] for k < pictures[s]; every other slot is left as it was."""
+        if len(chunks) != self.S:
+            raise FerHipError(f"LiveDecoder.decode: {len(chunks)} chunks for {self.S} streams")
+        need = self.P * self.S * self.fsz
+        if out is None:
+            out = np.zeros((self.P, self.S, self.fsz), np.uint8)
+        on_dev = 0
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+                raise FerHipError("LiveDecoder.decode: out must be a C-contiguous uint8 array of [max_pictures][S][W*H*3/2]")
+            ptr = out.ctypes.data
+        elif isinstance(out, DeviceBuffer):
+            if out.kind != 0 or out.nbytes < need:
+                raise FerHipError("LiveDecoder.decode: out must be a device DeviceBuffer of [max_pictures][S][W*H*3/2] bytes")
+            ptr, on_dev = out.ptr, 1
+        else:  # torch tensor
+            import torch
+            if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < need:
+                raise FerHipError("LiveDecoder.decode: out must be a contiguous uint8 tensor of [max_pictures][S][W*H*3/2]")
+            if out.is_cuda:
+                on_dev = 1
+                torch.cuda.current_stream(out.device).synchronize()  # the decoder writes from a stream of its own
+            ptr = out.data_ptr()
+        arr = (C.c_char_p * self.S)(*[c if c else None for c in chunks])
+        lens = (C.c_size_t * self.S)(*[len(c) if c else 0 for c in chunks])
+        pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
+        _chk(self.lib.ferhip_decs_decode(self.h, arr, lens, C.c_void_p(ptr), on_dev, pics, status), "ferhip_decs_decode")
+        return out, list(pics), list(status)
+
+    def reset_stream(self, s):
+        _chk(self.lib.ferhip_decs_reset_stream(self.h, s), "ferhip_decs_reset_stream")
+
+    def close(self):
+        if self.h:
+            self.lib.ferhip_decs_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def access_units(stream):
+    """Split an Annex-B stream (4-byte start codes) into chunks of whole NAL units, each ending with one slice NAL
+    unit (what follows the last slice joins the last chunk).  A chunk ends where the decoder's splitter ends that
+    slice -- at the zero bytes of the next start code -- so every NAL unit keeps exactly the bytes and the RBSP size it
+    has inside the whole stream.  b"".join(access_units(s)) == s.  Host only."""
+    chunks, begin, pos, n = [], 0, 0, len(stream)
+    while True:
+        j = stream.find(b"\x00\x00\x00\x01", pos)
+        if j < 0:
+            break
+        st = j + 4
+        ends = [e for e in (stream.find(b"\x00\x00\x00", st), stream.find(b"\x00\x00\x01", st)) if e >= 0]
+        en = min(ends) if ends else n
+        if en == st:  # an empty NAL unit: the decoder's splitter skips it
+            pos = en
+            continue
+        if en - st == 1:  # a header byte without payload: the decoder's splitter stops there
+            break
+        if stream[st] & 31 in (1, 5):
+            chunks.append(stream[begin:en])
+            begin = en
+        pos = en
+    if begin < n:
+        if chunks:
+            chunks[-1] += stream[begin:]
+        else:
+            chunks.append(stream[begin:])
+    return chunks
 
 
 def unescape_nal(nal):

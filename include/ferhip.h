@@ -206,6 +206,34 @@ int ferhip_dec_nal(ferhip_dec *d, int nal_unit_type, int nal_ref_idc, const uint
                    int *got_picture, int *width, int *height);
 void ferhip_dec_destroy(ferhip_dec *d);
 
+/* ---- live decoder: S streams of one coded picture size whose NAL units arrive piece by piece ----
+ * Each call takes what every stream has now, parses the slices of all streams with one launch and reconstructs them
+ * together; a stream's pictures over all calls, in order, are byte-identical to what ferhip_decode_streams gives for
+ * the concatenation of its chunks, however its NAL units are spread over calls and whichever other streams are present.
+ * width, height: multiples of 16.  max_pictures: slice NAL units per stream and call.  One thread at a time per decoder;
+ * it lives on the HIP device that is current at create.
+ *
+ * chunks[s], lens[s]: whole NAL units of stream s, Annex-B with 4-byte start codes, or NULL / 0 = nothing new for
+ * stream s in this call.  out: [max_pictures][nstreams][W*H*3/2] I420, picture k of stream s of this call at
+ * (k*nstreams + s)*W*H*3/2; out_on_device = 1: out is device memory on the decoder's device; out = NULL: no copy.
+ * Slots of stream s from pictures[s] on are not written.  pictures[s] = pictures of stream s decoded in this call.
+ * status[s] = 0 or the fault of stream s in this call: FERHIP_E_DEVICE (syntax error in slice data), FERHIP_E_UNSUP
+ * (syntax the GPU path does not implement, an SPS of another picture size), FERHIP_E_ARG (a slice header that runs
+ * past its NAL unit, more than max_pictures slices), FERHIP_E_STATE (a slice before the stream's SPS and PPS, a P
+ * slice after a fault before the next IDR slice).  A fault affects only its stream: the faulted picture and the rest
+ * of the stream's chunk are dropped, pictures[s] counts the pictures before it, and the stream restarts as a new
+ * decoder that has received its last SPS and PPS, from the next IDR slice on.  The other streams decode as if that
+ * stream had been absent.
+ * Returns 0 when the call ran, even if some streams failed; FERHIP_E_ARG / _HIP for the call as a whole.
+ *
+ * ferhip_decs_reset_stream: stream s forgets everything, its parameter sets included (a new feed on that slot). */
+typedef struct ferhip_decs ferhip_decs;
+int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, int height, int max_pictures);
+int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
+                       int *pictures, int *status);
+int ferhip_decs_reset_stream(ferhip_decs *d, int s);
+void ferhip_decs_destroy(ferhip_decs *d);
+
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
  * centre.  ferhip_y4m_read fills one coded-size I420 picture (use pinned memory when it feeds ferhip_set_frames);
