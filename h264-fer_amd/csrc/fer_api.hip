@@ -45,6 +45,9 @@ struct ferhip_ctx {
     uint32_t *h_hdr_ring;  // pinned [FER_HDR_SLOTS][S][4]; a pinned source is read when the copy executes, not when it is
     hipEvent_t hdr_ev[8];  // enqueued, so a slot is rewritten only after the copy that last used it has run
     int hdr_slot;
+    std::vector<FerRcPar> rate;  // ferhip_set_rate: the settings of every stream, sent with the next picture's headers
+    bool rate_dirty;
+    FerRcPar *h_rate_ring;       // pinned [FER_HDR_SLOTS][S], the header ring's companion
     uint32_t *h_len;       // pinned [S]
     int *h_status;         // pinned [S]
     unsigned long long *h_sad;
@@ -171,6 +174,7 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     c->ev_a = c->ev_b = c->ev_c = c->ev_d = nullptr;
     c->overlap_sort = 0;  // measured: kernels of two HIP streams do not share the GPU here (the sort stretches to k_me_pre's length)
     c->h_hdr = c->h_hdr_ring = c->h_len = nullptr;
+    c->h_rate_ring = nullptr;
     c->h_status = nullptr;
     c->h_sad = nullptr;
     for (int i = 0; i < FER_HDR_SLOTS; i++) c->hdr_ev[i] = nullptr;
@@ -189,17 +193,6 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     d.mbh = H / 16;
     d.nmb = d.mbw * d.mbh;
     d.S = S;
-    d.qp = p->qp;
-    d.qpc = k_qpc[p->qp];  // chroma_qp_index_offset == 0 (F/headers_and_parameter_sets.cpp:490)
-    for (int k = 0; k < 2; k++) {  // the three LevelScale / LevelQuantize values of each QP (F/scaleTransform.cpp:32-40)
-        static const int v[6][3] = {{10, 16, 13}, {11, 18, 14}, {13, 20, 16}, {14, 23, 18}, {16, 25, 20}, {18, 29, 23}};
-        const int m = (k ? d.qpc : d.qp) % 6;
-        for (int c = 0; c < 3; c++) {
-            const int ls = 16 * v[m][c];
-            d.lsq[k][c] = (int16_t)ls;
-            d.lsq[k][3 + c] = (int16_t)((65536 + ls) / (2 * ls));
-        }
-    }
     d.window = p->window;
     d.maxdiff_set = p->maxdiff;
     d.basic = p->basic ? 1 : 0;
@@ -278,6 +271,9 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     d.bits_cap_words = ((size_t)d.nmb * 1024 + 4096) / 4;
     rc |= dalloc(c, &d.bits, decode_only ? (size_t)1 : (size_t)(d.bits_cap_words * S));
     rc |= dalloc(c, &d.hdr, (size_t)4 * S);
+    rc |= dalloc(c, &d.qp, (size_t)S);
+    rc |= dalloc(c, &d.rc_par, (size_t)S);
+    rc |= dalloc(c, &d.rc, (size_t)S);
     rc |= dalloc(c, &d.out_bytes, (size_t)S);
     rc |= dalloc(c, &d.status, (size_t)S);
     rc |= dalloc(c, &d.sad, (size_t)S);
@@ -300,6 +296,7 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
         return FERHIP_E_HIP;
     }
     if (hipHostMalloc((void **)&c->h_hdr_ring, sizeof(uint32_t) * 4 * S * FER_HDR_SLOTS) != hipSuccess ||
+        hipHostMalloc((void **)&c->h_rate_ring, sizeof(FerRcPar) * S * FER_HDR_SLOTS) != hipSuccess ||
         hipHostMalloc((void **)&c->h_len, sizeof(uint32_t) * S) != hipSuccess ||
         hipHostMalloc((void **)&c->h_status, sizeof(int) * S) != hipSuccess ||
         hipHostMalloc((void **)&c->h_sad, sizeof(unsigned long long) * S) != hipSuccess) {
@@ -314,6 +311,17 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     c->hdr_slot = 0;
     c->h_hdr = c->h_hdr_ring;
     c->ss.assign(S, StreamState{0, 0, 0, 0, 0, 0});
+    // every stream starts in constant QP at params.qp, which is also the QP of its PPS; chroma_qp_index_offset == 0
+    // (F/headers_and_parameter_sets.cpp:490)
+    c->rate.assign(S, FerRcPar{FERHIP_RC_CQP, p->qp, 0, 51, 1, 0, p->intra_every, p->qp, 0, 0, 0});
+    c->rate_dirty = true;
+    {
+        std::vector<int> q0(S, p->qp | k_qpc[p->qp] << 8);
+        if (hipMemcpy(d.qp, q0.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess) {
+            ferhip_destroy(c);
+            return FERHIP_E_HIP;
+        }
+    }
     c->types.assign(S, 2);
     c->cur_set = 0;
     c->refprep_valid = false;
@@ -340,6 +348,7 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
     if (c->st_aux) hipStreamSynchronize(c->st_aux);
     for (void *p : c->allocs) hipFree(p);
     if (c->h_hdr_ring) hipHostFree(c->h_hdr_ring);
+    if (c->h_rate_ring) hipHostFree(c->h_rate_ring);
     for (int i = 0; i < FER_HDR_SLOTS; i++)
         if (c->hdr_ev[i]) hipEventDestroy(c->hdr_ev[i]);
     if (c->h_len) hipHostFree(c->h_len);
@@ -581,7 +590,7 @@ extern "C" size_t ferhip_write_sps(ferhip_ctx *c, uint8_t *rbsp, size_t cap)
 }
 
 // pps_write, F/headers_and_parameter_sets.cpp:478-513 (weighted_bipred_idc field carries the value 1)
-extern "C" size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap)
+static size_t write_pps(int qp, uint8_t *rbsp, size_t cap)
 {
     ByteW w{rbsp, cap, 0};
     w.ue(0);
@@ -593,13 +602,22 @@ extern "C" size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap)
     w.ue(0);
     w.put(1, 0);
     w.put(2, 1);
-    w.se(14 + c->p.qp - 26);
+    w.se(14 + qp - 26);
     w.se(0);
     w.se(0);
     w.put(1, 0);
     w.put(1, 0);
     w.put(1, 0);
     return w.trailing();
+}
+
+extern "C" size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap) { return write_pps(c->p.qp, rbsp, cap); }
+
+// the PPS of stream s: pic_init_qp = 14 + base[s] (0 for a bad argument)
+extern "C" size_t ferhip_write_pps_stream(ferhip_ctx *c, int s, uint8_t *rbsp, size_t cap)
+{
+    if (!c || !rbsp || s < 0 || s >= c->d.S) return 0;
+    return write_pps(c->rate[s].base, rbsp, cap);
 }
 
 // writeNAL, F/nal.cpp:261-299
@@ -660,7 +678,7 @@ static void build_header(ferhip_ctx *c, int s, int nal_type)
         h.put(1, 0);  // no_output_of_prior_pics_flag
         h.put(1, 0);  // long_term_reference_flag
     }
-    h.se(-14);
+    // slice_qp_delta is appended on the device by k_rc_plan once the picture's QP is known (fer_rate.hip)
     c->h_hdr[s * 4 + 0] = (uint32_t)(h.v >> 32);
     c->h_hdr[s * 4 + 1] = (uint32_t)h.v;
     c->h_hdr[s * 4 + 2] = (uint32_t)h.n;
@@ -676,10 +694,16 @@ static int hdr_begin(ferhip_ctx *c)
     c->h_hdr = c->h_hdr_ring + (size_t)c->hdr_slot * 4 * c->d.S;
     return 0;
 }
-// ... and send it
+// ... and send it, with the rate settings when they changed
 static int hdr_upload(ferhip_ctx *c)
 {
     CK(hipMemcpyAsync(c->d.hdr, c->h_hdr, sizeof(uint32_t) * 4 * c->d.S, hipMemcpyHostToDevice, c->st));
+    if (c->rate_dirty) {
+        FerRcPar *h = c->h_rate_ring + (size_t)c->hdr_slot * c->d.S;
+        memcpy(h, c->rate.data(), sizeof(FerRcPar) * c->d.S);
+        CK(hipMemcpyAsync(c->d.rc_par, h, sizeof(FerRcPar) * c->d.S, hipMemcpyHostToDevice, c->st));
+        c->rate_dirty = false;
+    }
     CK(hipEventRecord(c->hdr_ev[c->hdr_slot], c->st));
     return 0;
 }
@@ -743,6 +767,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
         anyI |= c->types[s] == 2;
     }
     if (hdr_upload(c)) return FERHIP_E_HIP;
+    fer_launch_rc_plan(d, c->st);  // each stream's QP and slice_qp_delta, before anything reads qp[] or hdr[] (fer_rate.hip)
     const int ndiag = d.mbw + 2 * (d.mbh - 1);
     if (anyP) {
         // The radix sort of the reference picture's positions and its bucket index are a stream of HBM traffic that only
@@ -915,7 +940,7 @@ extern "C" int ferhip_encode_streams(ferhip_ctx *c, const uint8_t *frames, int n
         size_t pos = 0, n;
         n = ferhip_write_sps(c, hdr, sizeof hdr);
         pos += ferhip_write_nal(1, 7, hdr, n, out + (size_t)s * out_stride + pos);
-        n = ferhip_write_pps(c, hdr, sizeof hdr);
+        n = ferhip_write_pps_stream(c, s, hdr, sizeof hdr);
         pos += ferhip_write_nal(1, 8, hdr, n, out + (size_t)s * out_stride + pos);
         out_len[s] = pos;
     }
@@ -954,6 +979,49 @@ extern "C" int ferhip_get_stats(ferhip_ctx *c, int *out)
     (void)hipSetDevice(c->device);
     CK(ctx_sync(c));
     CK(hipMemcpy(out, c->d.stats, sizeof(int) * 5 * c->d.S, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// rate control: the settings take effect with the next picture, k_rc_plan applies them on the device
+extern "C" int ferhip_set_rate(ferhip_ctx *c, int s, const ferhip_rate *r)
+{
+    if (!c || !r || s < -1 || s >= c->d.S) return FERHIP_E_ARG;
+    if (r->mode != FERHIP_RC_CQP && r->mode != FERHIP_RC_ABR) return FERHIP_E_ARG;
+    if (r->qp < 0 || r->qp > 51) return FERHIP_E_ARG;
+    if (r->mode == FERHIP_RC_ABR && (r->qp_min < 0 || r->qp_max > 51 || r->qp_min > r->qp_max || r->max_step < 1 || r->window < 0 ||
+                                     r->target_bits <= 0 || r->ip_offset < -51 || r->ip_offset > 51))
+        return FERHIP_E_ARG;
+    const int s0 = s < 0 ? 0 : s, s1 = s < 0 ? c->d.S : s + 1;
+    // before a stream's first picture its PPS is not sent yet: r->qp becomes its base, which pic_init_qp_minus26 must hold
+    for (int k = s0; k < s1; k++)
+        if (c->ss[k].frames_done == 0 && r->qp > 37) return FERHIP_E_ARG;
+    for (int k = s0; k < s1; k++) {
+        FerRcPar &p = c->rate[k];
+        if (r->mode == FERHIP_RC_ABR && p.mode != FERHIP_RC_ABR) p.gen++;
+        p.mode = r->mode;
+        p.qp = r->qp;
+        if (r->mode == FERHIP_RC_ABR) {
+            p.qp_min = r->qp_min;
+            p.qp_max = r->qp_max;
+            p.max_step = r->max_step;
+            p.ip_offset = r->ip_offset;
+            p.window = r->window > 0 ? r->window : c->p.intra_every;
+            p.target = r->target_bits;
+        }
+        if (c->ss[k].frames_done == 0) p.base = r->qp;
+    }
+    c->rate_dirty = true;
+    return 0;
+}
+
+// QP of every stream's last picture (params.qp before the first); waits for that picture
+extern "C" int ferhip_get_qp(ferhip_ctx *c, int *out)
+{
+    if (!c || !out) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    CK(ctx_sync(c));
+    CK(hipMemcpy(out, c->d.qp, sizeof(int) * c->d.S, hipMemcpyDeviceToHost));
+    for (int s = 0; s < c->d.S; s++) out[s] &= 0xff;
     return 0;
 }
 

@@ -39,10 +39,33 @@
 #define FER_LV_CDC 272
 #define FER_LV_CAC 280
 
+// Rate control of one stream (ferhip_set_rate, k_rc_plan in fer_rate.hip).  FerRcPar is the host's setting, uploaded with the
+// picture's slice headers after every change; FerRcState lives on the device only.
+struct FerRcPar {
+    int mode, qp, qp_min, qp_max, max_step, ip_offset, window;  // window resolved (0 -> intra_every)
+    int base;         // QP of the stream's PPS: slice_qp_delta = qp - base - 14
+    int gen;          // bumped when the stream enters ABR: k_rc_plan then clears err and have[]
+    int pad;
+    long long target; // RBSP bits per picture (ABR)
+};
+struct FerRcState {
+    long long err;           // sum of bits - target over the pictures coded in ABR since it was entered
+    long long last_bits[2];  // [0] = P, [1] = I: bits of the last picture of that type
+    int last_qp[2], have[2];
+    int prev_type;           // type (0 = P, 1 = I) of the stream's last picture
+    int pending;             // 1: the last picture was coded in ABR and is not accounted yet
+    int gen;                 // FerRcPar::gen this state belongs to
+    int pad;
+};
+
 struct FerDev {
     int W, H, Wc, Hc, mbw, mbh, nmb, S;
-    int qp, qpc, window, maxdiff_set, basic;
-    int16_t lsq[2][6];  // [luma qp / chroma qpc][LevelScale of class (even,even), (odd,odd), mixed; then LevelQuantize likewise]
+    int window, maxdiff_set, basic;
+    // QP of the picture being coded, per stream: QPy | QPc << 8, written by k_rc_plan before the first launch that quantises
+    // (k_p_resid, k_intra_mb read it once per wavefront); the LevelScale / LevelQuantize row of a QP is c_lsq[QP % 6]
+    int *qp;             // [S]
+    FerRcPar *rc_par;    // [S] rate settings of every stream
+    FerRcState *rc;      // [S] controller state
     int dbg;  // -DFER_PROBE builds only (env FER_DBG): bit mask that skips kernel stages for timing; the shipped
               // library compiles every test of it away (FER_DBGF)
     size_t ysz, csz;
@@ -156,6 +179,7 @@ struct DecBatch {
 #define FER_ERR_DEC_UNSUPPORTED 16
 #define FER_ERR_CHAIN_TIMEOUT 32
 #define FER_ERR_CHAIN_UNRESOLVED 64  // a P macroblock reached the residual stage without this picture's vectors
+#define FER_ERR_HDR_OVERFLOW 128     // the slice header with its slice_qp_delta is longer than the 64-bit header word
 
 // ---------------------------------------------------------------- tables
 // CAVLC tables: H.264 Tables 9-5, 9-7..9-10 as (length, code); zig-zag; block origins.
@@ -212,6 +236,11 @@ static __constant__ uint8_t c_rb_len[6][7] = {{1, 1, 0, 0, 0, 0, 0}, {1, 2, 2, 0
 static __constant__ uint8_t c_rb_code[6][7] = {{1, 0, 0, 0, 0, 0, 0}, {1, 1, 0, 0, 0, 0, 0}, {3, 2, 1, 0, 0, 0, 0},
                                         {3, 2, 1, 1, 0, 0, 0}, {3, 2, 3, 2, 1, 0, 0}, {3, 0, 1, 3, 2, 5, 4}};
 // raster index (y*4+x) of scan position k (F/scaleTransform.cpp:43-47)
+// the three LevelScale values of QP % 6 (F/scaleTransform.cpp:32-40) times 16 for the classes (even,even), (odd,odd), mixed,
+// then LevelQuantize = (65536 + ls) / (2 * ls) likewise
+static __constant__ int16_t c_lsq[6][6] = {{160, 256, 208, 205, 128, 158}, {176, 288, 224, 186, 114, 146},
+                                           {208, 320, 256, 158, 102, 128}, {224, 368, 288, 146, 89, 114},
+                                           {256, 400, 320, 128, 82, 102},  {288, 464, 368, 114, 71, 89}};
 static __constant__ uint8_t c_zz[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
 // x,y origin of luma 4x4 block k (F/h264_globals.cpp:209-214)
 static __constant__ uint8_t c_bx[16] = {0, 4, 0, 4, 8, 12, 8, 12, 0, 4, 0, 4, 8, 12, 8, 12};
@@ -581,7 +610,7 @@ struct RowQ {  // per-lane constants of a row of a 4x4 block
     int lq[4], ls[4];    // LevelQuantize / LevelScale of (row, x)
 };
 
-__device__ __forceinline__ RowQ rowq_make(int row, const int16_t (&t)[6])  // t = FerDev::lsq[luma / chroma]
+__device__ __forceinline__ RowQ rowq_make(int row, const int16_t (&t)[6])  // t = c_lsq[QP % 6] of luma / chroma
 {
     RowQ q;
     q.row = row;

@@ -76,6 +76,7 @@ __global__ __launch_bounds__(64) void k_intra_mb(FerDev d, int diag)
     const int lane = threadIdx.x;
     const int s = blockIdx.y;
     if (d.hdr[s * 4 + 3] != 2) return;
+    const int qpw = d.qp[s];  // the stream's QPy | QPc << 8 for this picture (uniform: a scalar load)
     int y_lo = diag - (d.mbw - 1);
     y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
     const int mby = y_lo + blockIdx.x, mbx = diag - 2 * mby;
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(64) void k_intra_mb(FerDev d, int diag)
     uint8_t *Cp[2] = {d.curCb + (size_t)s * d.csz, d.curCr + (size_t)s * d.csz};
     const int xp = mbx << 4, yp = mby << 4;
     const bool availL = mbx > 0, availT = mby > 0, lastcol = mbx == d.mbw - 1;
-    const int QPy = d.qp, QPc = d.qpc;
+    const int QPy = qpw & 0xff, QPc = qpw >> 8;
     const size_t mbi = (size_t)s * d.nmb + mb;
     const bool stale_skip = d.mb_type[mbi] == FER_P_SKIP;  // mb_type_array entry left by the previous picture
 
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(64) void k_intra_mb(FerDev d, int diag)
     // serial by construction: a block predicts from the reconstruction of the blocks before it.
     {
         const int row = lane & 3;
-        const RowQ rq = rowq_make(row, d.lsq[0]);
+        const RowQ rq = rowq_make(row, c_lsq[QPy % 6]);
         const uint32_t zrow = ((const uint32_t *)c_izz)[row];
         for (int blk = 0; blk < 16; blk++) {
             // setIntra4x4PredMode (F/intra.cpp:878-942)

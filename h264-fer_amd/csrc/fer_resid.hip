@@ -59,6 +59,7 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
     const uint8_t *Rp = (pl ? d.refCr : d.refCb) + (size_t)s * d.csz;
     uint8_t *dstC = Cp + (size_t)(yp / 2 + cy0) * Wc + xp / 2 + cx0;
     const int ptype = (int)d.hdr[s * 4 + 3], mtype = mbt[mb];
+    const int qpw = d.qp[s], QPy = qpw & 0xff, QPc = qpw >> 8;  // the stream's QP for this picture (uniform: a scalar load)
     const uint32_t svL = *(const uint32_t *)dstL, svC = *(const uint32_t *)dstC;
     // the vectors of this macroblock and of its left / above / above-right / above-left neighbours, one per lane
     int tbl;
@@ -155,8 +156,8 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
         int r[4], c[4], dc0;
 #pragma unroll
         for (int k = 0; k < 4; k++) r[k] = iabs(srcv[k] - pfL[k]) < MAXDIFF ? 0 : srcv[k] - pfL[k];
-        const RowQ q = rowq_make(row, d.lsq[0]);
-        fwd_row(q, r, d.qp, false, c, dc0);
+        const RowQ q = rowq_make(row, c_lsq[QPy % 6]);
+        fwd_row(q, r, QPy, false, c, dc0);
         const uint32_t z = ((const uint32_t *)c_izz)[row];
         int cnt = 0;
 #pragma unroll
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
         cnt = quad_sum(cnt);
         if (row == 0) tcs[blk] = (uint8_t)cnt;
         nz_l = __ballot(cnt != 0);
-        inv_row(q, c, d.qp, false, r);
+        inv_row(q, c, QPy, false, r);
         uint32_t o = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) o |= (uint32_t)clip255(pfL[k] + r[k]) << (8 * k);
@@ -185,8 +186,8 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
             const int sk = (svC >> (8 * k)) & 0xff;
             r[k] = iabs(sk - pf[k]) <= MAXDIFF ? 0 : sk - pf[k];
         }
-        const RowQ q = rowq_make(row, d.lsq[1]);
-        fwd_row(q, r, d.qpc, true, c, dcraw);
+        const RowQ q = rowq_make(row, c_lsq[QPc % 6]);
+        fwd_row(q, r, QPc, true, c, dcraw);
         // chroma DC: 2x2 Hadamard + quantiser on the four DC values of each plane (row-0 lanes of its blocks)
         int dcq, dcdeq;
         {
@@ -196,10 +197,10 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
                 f0[i] = __builtin_amdgcn_readlane(dcraw, i * 4);
                 f1[i] = __builtin_amdgcn_readlane(dcraw, 16 + i * 4);
             }
-            fwd_dc_chroma(f0, cq0, d.qpc);
-            inv_dc_chroma(cq0, dq0, d.qpc);
-            fwd_dc_chroma(f1, cq1, d.qpc);
-            inv_dc_chroma(cq1, dq1, d.qpc);
+            fwd_dc_chroma(f0, cq0, QPc);
+            inv_dc_chroma(cq0, dq0, QPc);
+            fwd_dc_chroma(f1, cq1, QPc);
+            inv_dc_chroma(cq1, dq1, QPc);
             const int a = cb == 0 ? cq0[0] : (cb == 1 ? cq0[1] : (cb == 2 ? cq0[2] : cq0[3]));
             const int b = cb == 0 ? cq1[0] : (cb == 1 ? cq1[1] : (cb == 2 ? cq1[2] : cq1[3]));
             const int e = cb == 0 ? dq0[0] : (cb == 1 ? dq0[1] : (cb == 2 ? dq0[2] : dq0[3]));
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
         nz_c = __ballot(act && cnt != 0);
         dcm = __ballot(act && dcq != 0);
         if (row == 0) c[0] = dcdeq;
-        inv_row(q, c, d.qpc, true, r);
+        inv_row(q, c, QPc, true, r);
         uint32_t o = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) o |= (uint32_t)clip255(pf[k] + r[k]) << (8 * k);

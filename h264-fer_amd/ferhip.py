@@ -10,6 +10,7 @@ NAL_SLICE, NAL_IDR, NAL_AUTO = 1, 5, 0
 BUF = dict(INTERP=1, FEAT=2, SORTPOS=3, KOLIKO=4, MBTYPE=5, MV=6, MVD=7, LEVELS=8, CBP=9, TC=10, I4MODE=11,
            CUR=12, REF=13, TIMING=14, ST2N=15, ST2=16, SPEC_STAT=17, MBSIZE=18)
 TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT = 1, 2, 3, 4
+RC_CQP, RC_ABR = 0, 1
 _BUF_DTYPE = {1: np.uint8, 2: np.uint16, 3: np.uint32, 4: np.int32, 5: np.int32, 6: np.int16, 7: np.int16,
               8: np.int16, 9: np.uint8, 10: np.uint8, 11: np.uint8, 12: np.uint8, 13: np.uint8, 14: np.int64, 15: np.int32, 16: np.int32,
               17: np.uint64, 18: np.int32}
@@ -22,6 +23,12 @@ class FerHipError(RuntimeError):
 class Params(C.Structure):
     _fields_ = [("qp", C.c_int), ("basic", C.c_int), ("window", C.c_int), ("maxdiff", C.c_int),
                 ("intra_every", C.c_int)]
+
+
+class Rate(C.Structure):
+    """ferhip_rate of include/ferhip.h"""
+    _fields_ = [("mode", C.c_int), ("qp", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("max_step", C.c_int),
+                ("ip_offset", C.c_int), ("window", C.c_int), ("target_bits", C.c_longlong)]
 
 
 def lib_path():
@@ -64,6 +71,10 @@ def load_library():
     lib.ferhip_write_sps.restype = sz
     lib.ferhip_write_pps.argtypes = [vp, vp, sz]
     lib.ferhip_write_pps.restype = sz
+    lib.ferhip_write_pps_stream.argtypes = [vp, i, vp, sz]
+    lib.ferhip_write_pps_stream.restype = sz
+    lib.ferhip_set_rate.argtypes = [vp, i, C.POINTER(Rate)]
+    lib.ferhip_get_qp.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_write_nal.argtypes = [i, i, vp, sz, vp]
     lib.ferhip_write_nal.restype = sz
     lib.ferhip_encode_streams.argtypes = [vp, vp, i, vp, sz, C.POINTER(sz), vp]
@@ -221,11 +232,25 @@ class FerHip:
         _chk(self.lib.ferhip_get_recon(self.ctx, out.ctypes.data, 1), "ferhip_get_recon")
         return out
 
-    def encode_streams(self, frames, want_recon=False):
-        """frames: [T][S][fsz] uint8 -> (list of Annex-B byte strings, recon or None)."""
+    def encode_streams(self, frames, want_recon=False, want_qp=False):
+        """frames: [T][S][fsz] uint8 -> (list of Annex-B byte strings, recon or None); want_qp: also the [T][S] QPs used."""
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         T = a.size // (self.S * self.fsz)
         a = a.reshape(T, self.S, self.fsz)
+        if want_qp:
+            # ferhip_encode_streams picture by picture, with the QP of every picture read back
+            out = [b"".join(self.sps_pps(s)) for s in range(self.S)]
+            rec = np.empty((T, self.S, self.fsz), np.uint8) if want_recon else None
+            qps = np.empty((T, self.S), np.int32)
+            for t in range(T):
+                self.set_frames(a[t])
+                rbsp, nt = self.encode_picture()
+                for s in range(self.S):
+                    out[s] += self.write_nal(nt[s], rbsp[s])
+                qps[t] = self.last_qp()
+                if want_recon:
+                    rec[t] = self.get_recon()
+            return out, rec, qps
         stride = 64 + T * (self.nmb * 1024 + 4096) * 3 // 2
         out = np.empty((self.S, stride), np.uint8)
         ln = (C.c_size_t * self.S)()
@@ -234,13 +259,19 @@ class FerHip:
                                             rec.ctypes.data if want_recon else None), "ferhip_encode_streams")
         return [bytes(out[s, : ln[s]]) for s in range(self.S)], rec
 
-    def sps_pps(self):
+    def sps_pps(self, stream=None):
+        """Annex-B SPS and PPS; stream = s: the PPS of stream s (pic_init_qp = 14 + its base QP), None: of params.qp"""
         b = np.empty(64, np.uint8)
         o = np.empty(128, np.uint8)
         n = self.lib.ferhip_write_sps(self.ctx, b.ctypes.data, 64)
         m = self.lib.ferhip_write_nal(1, 7, b.ctypes.data, n, o.ctypes.data)
         sps = bytes(o[:m])
-        n = self.lib.ferhip_write_pps(self.ctx, b.ctypes.data, 64)
+        if stream is None:
+            n = self.lib.ferhip_write_pps(self.ctx, b.ctypes.data, 64)
+        else:
+            n = self.lib.ferhip_write_pps_stream(self.ctx, stream, b.ctypes.data, 64)
+            if n == 0:
+                raise FerHipError(f"ferhip_write_pps_stream({stream}) failed")
         m = self.lib.ferhip_write_nal(1, 8, b.ctypes.data, n, o.ctypes.data)
         return sps, bytes(o[:m])
 
@@ -249,6 +280,19 @@ class FerHip:
         o = np.empty(len(rbsp) * 3 // 2 + 16, np.uint8)
         m = self.lib.ferhip_write_nal(1, nal_type, r.ctypes.data, len(rbsp), o.ctypes.data)
         return bytes(o[:m])
+
+    # --- rate control
+    def set_rate(self, stream=-1, mode=RC_CQP, qp=None, qp_min=0, qp_max=51, max_step=2, ip_offset=3, window=0,
+                 target_bits=0):
+        """ferhip_set_rate for one stream (or every stream, -1) from the next picture on; qp None = params.qp"""
+        r = Rate(mode, self.params.qp if qp is None else qp, qp_min, qp_max, max_step, ip_offset, window, int(target_bits))
+        _chk(self.lib.ferhip_set_rate(self.ctx, stream, C.byref(r)), "ferhip_set_rate")
+
+    def last_qp(self):
+        """QP of every stream's last picture (waits for it)"""
+        a = (C.c_int * self.S)()
+        _chk(self.lib.ferhip_get_qp(self.ctx, a), "ferhip_get_qp")
+        return list(a)
 
     # --- stage entry points / state read-back
     def fill_interpolated(self):

@@ -103,19 +103,61 @@ int ferhip_get_recon(ferhip_ctx *c, void *dst, int host);
 /* SPS / PPS RBSP (F/headers_and_parameter_sets.cpp:305-391,478-513) and NAL framing with
  * emulation prevention (F/nal.cpp:261-299); host-side, byte-serial. */
 size_t ferhip_write_sps(ferhip_ctx *c, uint8_t *rbsp, size_t cap);
-size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap);
+size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap);  /* pic_init_qp = 14 + params.qp; see ferhip_write_pps_stream */
 size_t ferhip_write_nal(int nal_ref_idc, int nal_type, const uint8_t *rbsp, size_t n, uint8_t *out);
 
-/* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134):
+/* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134), each stream with its own PPS:
  * frames host [T][S][W*H*3/2]; out host [S][out_stride] Annex-B; out_len[S].
  * recon (optional) host [T][S][W*H*3/2]. */
 int ferhip_encode_streams(ferhip_ctx *c, const uint8_t *frames, int nframes, uint8_t *out, size_t out_stride,
                           size_t *out_len, uint8_t *recon);
 
+/* ---- rate control: per-stream QP of every picture ----
+ * Each stream of a context codes every picture at one QP (mb_qp_delta stays 0) and chooses it per picture.  The choice is
+ * made on the device, by a kernel that runs before the picture's first quantising launch, from the RBSP length of the
+ * stream's previous picture already in device memory: rate control adds no host synchronisation to the picture pipeline.
+ *
+ * base[s] = the QP in stream s's PPS (pic_init_qp = 14 + base[s], ferhip_write_pps_stream).  It starts as params.qp; a
+ * ferhip_set_rate call made before the stream's first picture sets it to r->qp (which must then be <= 37, so that
+ * pic_init_qp_minus26 = base - 12 stays within -26..25); after the first picture it is frozen.  Every slice header carries
+ * slice_qp_delta = qp - base[s] - 14, so a stream kept at one QP q is byte-identical to the reference run with _qParameter = q.
+ *
+ * FERHIP_RC_CQP: every picture at r->qp (0..51), from the next picture on; may change between any two pictures.
+ * FERHIP_RC_ABR: steers to target_bits RBSP bits per picture on average, in integer arithmetic:
+ *   P6 = {65536, 73562, 82570, 92682, 104032, 116772} (2^16 * 2^(k/6));  pow2q16(d) = P6[d mod 6] shifted by floor(d / 6)
+ *   est(y, q) = (last_bits[y] * pow2q16(last_qp[y] - q)) >> 16, y = 0 for P, 1 for I pictures
+ *   before choosing, the stream's previous picture (type y', QP q', b = 8 * its RBSP bytes), if it was coded in ABR, is accounted:
+ *     err += b - target; last_bits[y'] = b; last_qp[y'] = q'; have[y'] = 1
+ *   window = r->window > 0 ? r->window : intra_every
+ *   T = clamp(target - err / window (truncating), max(target / 8, 1), 8 * target)
+ *   P picture: have[P] ? the smallest q in [qp_min, qp_max] with est(P, q) <= T (qp_max if none), clamped to last_qp[P] +- max_step
+ *              : have[I] ? last_qp[I] + ip_offset : r->qp
+ *   I picture: have[P] ? last_qp[P] - ip_offset : have[I] ? last_qp[I] : r->qp
+ *   then clamped to [qp_min, qp_max].  An I picture's extra bits land in err and the P pictures of the next window pictures pay
+ *   them back.  Entering ABR (from CQP or at create) clears err and have[]; a call in ABR keeps them.
+ * Invalid arguments return FERHIP_E_ARG: s outside -1..S-1, qp outside 0..51, a base of 38 or more before the first picture,
+ * and in ABR qp_min < 0, qp_max > 51, qp_min > qp_max, max_step < 1, window < 0, |ip_offset| > 51, target_bits <= 0.
+ * ferhip_set_rate only records the settings; ferhip_get_qp is the only rate-control call that waits (for the last picture). */
+#define FERHIP_RC_CQP 0
+#define FERHIP_RC_ABR 1
+typedef struct {
+    int mode;              /* FERHIP_RC_CQP / FERHIP_RC_ABR */
+    int qp;                /* CQP: QP of every picture from the next one on; ABR: QP of the first picture */
+    int qp_min, qp_max;    /* ABR: 0 <= qp_min <= qp_max <= 51 */
+    int max_step;          /* ABR: largest change between consecutive P pictures (>= 1) */
+    int ip_offset;         /* ABR: an I picture takes the last P QP minus this */
+    int window;            /* ABR: pictures over which the accumulated error is paid back; 0 = intra_every */
+    long long target_bits; /* ABR: RBSP bits per picture, > 0 */
+} ferhip_rate;
+int ferhip_set_rate(ferhip_ctx *c, int s, const ferhip_rate *r); /* s = -1: every stream; applies from the next picture */
+int ferhip_get_qp(ferhip_ctx *c, int *qp_per_stream);            /* QP of each stream's last picture (waits for it) */
+size_t ferhip_write_pps_stream(ferhip_ctx *c, int s, uint8_t *rbsp, size_t cap); /* pic_init_qp = 14 + base[s] */
+
 /* statistics of Starter::DohvatiStatistiku: brojTipova[5] per stream, accumulated */
 int ferhip_get_stats(ferhip_ctx *c, int *counts5_per_stream);
 /* sticky device error flags per stream (bits 0, 1: unused, bit 2: RBSP buffer overflow, bits 3, 4: decoder syntax
- * error / unsupported syntax, bit 5: motion chain timeout, bit 6: a P macroblock without this picture's vectors) */
+ * error / unsupported syntax, bit 5: motion chain timeout, bit 6: a P macroblock without this picture's vectors, bit 7: a slice header with its
+ * slice_qp_delta longer than 64 bits -- more than about 4000 IDR pictures in a row) */
 int ferhip_status(ferhip_ctx *c, int *flags_per_stream);
 const char *ferhip_version(void);
 
