@@ -48,6 +48,8 @@ struct ferhip_ctx {
     std::vector<FerRcPar> rate;  // ferhip_set_rate: the settings of every stream, sent with the next picture's headers
     bool rate_dirty;
     FerRcPar *h_rate_ring;       // pinned [FER_HDR_SLOTS][S], the header ring's companion
+    int qflags;                  // ferhip_set_quality
+    long long q_count;           // pictures measured so far: the next record goes to ring slot q_count % FERHIP_QUALITY_RING
     uint32_t *h_len;       // pinned [S]
     int *h_status;         // pinned [S]
     unsigned long long *h_sad;
@@ -175,6 +177,8 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     c->overlap_sort = 0;  // measured: kernels of two HIP streams do not share the GPU here (the sort stretches to k_me_pre's length)
     c->h_hdr = c->h_hdr_ring = c->h_len = nullptr;
     c->h_rate_ring = nullptr;
+    c->qflags = 0;
+    c->q_count = 0;
     c->h_status = nullptr;
     c->h_sad = nullptr;
     for (int i = 0; i < FER_HDR_SLOTS; i++) c->hdr_ev[i] = nullptr;
@@ -708,6 +712,45 @@ static int hdr_upload(ferhip_ctx *c)
     return 0;
 }
 
+// Quality measurement: what run_picture measures -- the flags of ferhip_set_quality, and at least the SSE when a stream is in
+// FERHIP_RC_QUALITY (its controller reads the luma SSE of the stream's last picture)
+static int quality_flags(ferhip_ctx *c)
+{
+    int f = c->qflags;
+    for (const FerRcPar &r : c->rate)
+        if (r.mode == FERHIP_RC_QUALITY) {
+            f |= FERHIP_QM_SSE;
+            break;
+        }
+    return f;
+}
+
+// the snapshot of the source, the ring and k_quality's partials, on first use
+static int quality_alloc(ferhip_ctx *c)
+{
+    FerDev &d = c->d;
+    if (d.qsrc) return 0;
+    const int G = fer_quality_groups(d);
+    uint8_t *src = nullptr;
+    ferhip_quality *ring = nullptr;
+    unsigned long long *lsse = nullptr;
+    FerQPart *part = nullptr;
+    unsigned *ticket = nullptr;
+    if (dalloc(c, &src, d.ysz * 3 / 2 * d.S) || dalloc(c, &ring, (size_t)FERHIP_QUALITY_RING * d.S) || dalloc(c, &lsse, (size_t)d.S) ||
+        dalloc(c, &part, (size_t)G * d.S) || dalloc(c, &ticket, (size_t)d.S) || hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
+        (void)hipGetLastError();
+        fprintf(stderr, "ferhip: could not allocate the quality measurement buffers\n");
+        return FERHIP_E_HIP;
+    }
+    d.qgroups = G;
+    d.qring = ring;
+    d.q_lsse = lsse;
+    d.qpart = part;
+    d.qticket = ticket;
+    d.qsrc = src;
+    return 0;
+}
+
 // selectNALUnitType, F/ref_frames.cpp:185-234: nt[s] in = request (AUTO / IDR / SLICE), out = decision
 static int decide_types(ferhip_ctx *c, const int *nal_type, std::vector<int> &nt)
 {
@@ -768,6 +811,12 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
     }
     if (hdr_upload(c)) return FERHIP_E_HIP;
     fer_launch_rc_plan(d, c->st);  // each stream's QP and slice_qp_delta, before anything reads qp[] or hdr[] (fer_rate.hip)
+    // quality measurement: the source is reconstructed in place, so it is kept before the first launch that reconstructs
+    const int qflags = quality_flags(c);
+    if (qflags) {
+        if (quality_alloc(c)) return FERHIP_E_HIP;
+        CK(hipMemcpyAsync(d.qsrc, d.curY, d.ysz * 3 / 2 * S, hipMemcpyDeviceToDevice, c->st));
+    }
     const int ndiag = d.mbw + 2 * (d.mbh - 1);
     if (anyP) {
         // The radix sort of the reference picture's positions and its bucket index are a stream of HBM traffic that only
@@ -848,6 +897,10 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
     {
         ProfScope ps(c, FERHIP_PH_CAVLC, 1);
         fer_launch_cavlc(d, c->st);
+    }
+    if (qflags) {  // after entropy coding: the record carries the RBSP length (fer_quality.hip)
+        fer_launch_quality(d, qflags, (int)(c->q_count % FERHIP_QUALITY_RING), c->ss[0].frames_done, c->st);
+        c->q_count++;
     }
     CK(hipGetLastError());
     // the reconstruction becomes the reference picture (frameDeepCopy, F/ref_frames.cpp:17)
@@ -986,32 +1039,65 @@ extern "C" int ferhip_get_stats(ferhip_ctx *c, int *out)
 extern "C" int ferhip_set_rate(ferhip_ctx *c, int s, const ferhip_rate *r)
 {
     if (!c || !r || s < -1 || s >= c->d.S) return FERHIP_E_ARG;
-    if (r->mode != FERHIP_RC_CQP && r->mode != FERHIP_RC_ABR) return FERHIP_E_ARG;
+    if (r->mode != FERHIP_RC_CQP && r->mode != FERHIP_RC_ABR && r->mode != FERHIP_RC_QUALITY) return FERHIP_E_ARG;
     if (r->qp < 0 || r->qp > 51) return FERHIP_E_ARG;
-    if (r->mode == FERHIP_RC_ABR && (r->qp_min < 0 || r->qp_max > 51 || r->qp_min > r->qp_max || r->max_step < 1 || r->window < 0 ||
-                                     r->target_bits <= 0 || r->ip_offset < -51 || r->ip_offset > 51))
+    if (r->mode != FERHIP_RC_CQP &&
+        (r->qp_min < 0 || r->qp_max > 51 || r->qp_min > r->qp_max || r->max_step < 1 || r->ip_offset < -51 || r->ip_offset > 51))
         return FERHIP_E_ARG;
+    if (r->mode == FERHIP_RC_ABR && (r->window < 0 || r->target_bits <= 0)) return FERHIP_E_ARG;
+    if (r->mode == FERHIP_RC_QUALITY && r->target_sse <= 0) return FERHIP_E_ARG;
     const int s0 = s < 0 ? 0 : s, s1 = s < 0 ? c->d.S : s + 1;
     // before a stream's first picture its PPS is not sent yet: r->qp becomes its base, which pic_init_qp_minus26 must hold
     for (int k = s0; k < s1; k++)
         if (c->ss[k].frames_done == 0 && r->qp > 37) return FERHIP_E_ARG;
     for (int k = s0; k < s1; k++) {
         FerRcPar &p = c->rate[k];
-        if (r->mode == FERHIP_RC_ABR && p.mode != FERHIP_RC_ABR) p.gen++;
+        if (r->mode != FERHIP_RC_CQP && p.mode != r->mode) p.gen++;
         p.mode = r->mode;
         p.qp = r->qp;
-        if (r->mode == FERHIP_RC_ABR) {
+        if (r->mode != FERHIP_RC_CQP) {
             p.qp_min = r->qp_min;
             p.qp_max = r->qp_max;
             p.max_step = r->max_step;
             p.ip_offset = r->ip_offset;
+        }
+        if (r->mode == FERHIP_RC_ABR) {
             p.window = r->window > 0 ? r->window : c->p.intra_every;
             p.target = r->target_bits;
         }
+        if (r->mode == FERHIP_RC_QUALITY) p.tsse = r->target_sse;
         if (c->ss[k].frames_done == 0) p.base = r->qp;
     }
     c->rate_dirty = true;
     return 0;
+}
+
+extern "C" int ferhip_set_quality(ferhip_ctx *c, int flags)
+{
+    if (!c || (flags & ~(FERHIP_QM_SSE | FERHIP_QM_SSIM))) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    if (flags && quality_alloc(c)) return FERHIP_E_HIP;
+    c->qflags = flags;
+    return 0;
+}
+
+// the ring, oldest record first; waits for the last picture
+extern "C" int ferhip_get_quality(ferhip_ctx *c, int npic, ferhip_quality *out)
+{
+    if (!c || !out || npic <= 0) return FERHIP_E_ARG;
+    if (c->q_count == 0) return FERHIP_E_STATE;
+    (void)hipSetDevice(c->device);
+    const int S = c->d.S;
+    long long n = c->q_count < FERHIP_QUALITY_RING ? c->q_count : FERHIP_QUALITY_RING;
+    if (n > npic) n = npic;
+    std::vector<ferhip_quality> ring((size_t)FERHIP_QUALITY_RING * S);
+    CK(ctx_sync(c));
+    CK(hipMemcpy(ring.data(), c->d.qring, sizeof(ferhip_quality) * ring.size(), hipMemcpyDeviceToHost));
+    for (long long k = 0; k < n; k++) {
+        const long long slot = (c->q_count - n + k) % FERHIP_QUALITY_RING;
+        memcpy(out + (size_t)k * S, ring.data() + (size_t)slot * S, sizeof(ferhip_quality) * S);
+    }
+    return (int)n;
 }
 
 // QP of every stream's last picture (params.qp before the first); waits for that picture

@@ -44,19 +44,29 @@
 struct FerRcPar {
     int mode, qp, qp_min, qp_max, max_step, ip_offset, window;  // window resolved (0 -> intra_every)
     int base;         // QP of the stream's PPS: slice_qp_delta = qp - base - 14
-    int gen;          // bumped when the stream enters ABR: k_rc_plan then clears err and have[]
+    int gen;          // bumped when the stream enters ABR or QUALITY: k_rc_plan then clears err and have[]
     int pad;
     long long target; // RBSP bits per picture (ABR)
+    long long tsse;   // luma SSE per picture (QUALITY)
 };
 struct FerRcState {
     long long err;           // sum of bits - target over the pictures coded in ABR since it was entered
     long long last_bits[2];  // [0] = P, [1] = I: bits of the last picture of that type
     int last_qp[2], have[2];
     int prev_type;           // type (0 = P, 1 = I) of the stream's last picture
-    int pending;             // 1: the last picture was coded in ABR and is not accounted yet
+    int pending;             // the last picture was coded in 1: ABR, 2: QUALITY, and is not accounted yet
     int gen;                 // FerRcPar::gen this state belongs to
     int pad;
+    long long last_sse[2];   // QUALITY: luma SSE of the last picture of that type
 };
+
+// Quality measurement (ferhip_set_quality, k_quality in fer_quality.hip): one partial result per workgroup, summed in a fixed
+// order by the stream's last workgroup.
+struct FerQPart {
+    unsigned long long sse[3];
+    double ssim;
+};
+struct ferhip_quality;
 
 struct FerDev {
     int W, H, Wc, Hc, mbw, mbh, nmb, S;
@@ -66,6 +76,13 @@ struct FerDev {
     int *qp;             // [S]
     FerRcPar *rc_par;    // [S] rate settings of every stream
     FerRcState *rc;      // [S] controller state
+    // quality measurement, all null until it is first enabled
+    uint8_t *qsrc;              // a copy of the current picture set (plane-major like planes[]) taken before it is overwritten
+    ferhip_quality *qring;      // [FERHIP_QUALITY_RING][S] one record per measured picture
+    unsigned long long *q_lsse; // [S] luma SSE of the last measured picture (k_rc_plan in QUALITY)
+    FerQPart *qpart;            // [S][qgroups] per-workgroup partial sums of k_quality
+    unsigned *qticket;          // [S] workgroups of k_quality done (reset by the last one)
+    int qgroups;
     int dbg;  // -DFER_PROBE builds only (env FER_DBG): bit mask that skips kernel stages for timing; the shipped
               // library compiles every test of it away (FER_DBGF)
     size_t ysz, csz;

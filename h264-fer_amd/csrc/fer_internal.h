@@ -30,6 +30,8 @@ void fer_launch_p_resid(const FerDev &d, hipStream_t st);
 void fer_launch_intra(const FerDev &d, hipStream_t st);
 void fer_launch_cavlc(const FerDev &d, hipStream_t st);
 void fer_launch_rc_plan(const FerDev &d, hipStream_t st);
+int fer_quality_groups(const FerDev &d);
+void fer_launch_quality(const FerDev &d, int flags, int slot, int picture, hipStream_t st);
 void fer_launch_block_kat(int qP, const int32_t *in, int32_t *out, int keep_dc, int inverse, size_t n, hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);

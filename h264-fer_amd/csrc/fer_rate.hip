@@ -1,7 +1,7 @@
 // fer_rate.hip -- per-stream QP of every picture (ferhip_set_rate): k_rc_plan picks each stream's QP on the device from the
-// RBSP lengths of its last picture, so that the picture pipeline needs no host synchronisation for rate control.  One lane
-// per stream; runs on the context's main stream after the slice headers have been uploaded and before the first launch that
-// reads FerDev::qp or FerDev::hdr.
+// RBSP length (ABR) or the luma SSE (QUALITY, written by k_quality) of its last picture, so that the picture pipeline needs
+// no host synchronisation for rate control.  One lane per stream; runs on the context's main stream after the slice headers
+// have been uploaded and before the first launch that reads FerDev::qp or FerDev::hdr.
 #include "../../include/ferhip.h"
 #include "fer_internal.h"
 
@@ -25,6 +25,14 @@ __device__ __forceinline__ unsigned long long rc_est(const FerRcState &r, int y,
     return ((unsigned long long)r.last_bits[y] * pow2q16(r.last_qp[y] - q)) >> 16;
 }
 
+// QUALITY: est(y, q) = (last_sse[y] * pow2q16(2 * (q - last_qp[y]))) >> 16 <= target, with the 128-bit product exact
+__device__ __forceinline__ bool rc_sse_fits(const FerRcState &r, int y, int q, long long target)
+{
+    const unsigned long long a = (unsigned long long)r.last_sse[y], m = pow2q16(2 * (q - r.last_qp[y]));
+    const unsigned long long lo = a * m, hi = __umul64hi(a, m);
+    return (hi >> 16) == 0 && ((lo >> 16) | (hi << 48)) <= (unsigned long long)target;
+}
+
 __device__ __forceinline__ int rc_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(64) void k_rc_plan(FerDev d)
@@ -34,18 +42,23 @@ __global__ __launch_bounds__(64) void k_rc_plan(FerDev d)
     const FerRcPar p = d.rc_par[s];
     FerRcState r = d.rc[s];
     const int y = d.hdr[s * 4 + 3] == 2 ? 1 : 0;  // 0 = P, 1 = I
-    if (p.mode == FERHIP_RC_ABR && r.gen != p.gen) {  // entering ABR
+    if (p.mode != FERHIP_RC_CQP && r.gen != p.gen) {  // entering ABR or QUALITY
         r.err = 0;
         r.have[0] = r.have[1] = 0;
         r.pending = 0;
         r.gen = p.gen;
     }
     const int last_qp = d.qp[s] & 0xff;
-    if (r.pending) {  // (a) account the last picture: it was coded in ABR
+    if (r.pending == 1) {  // (a) account the last picture: it was coded in ABR
         const long long b = 8ll * d.out_bytes[s];
         const int yp = r.prev_type;
         r.err += b - p.target;
         r.last_bits[yp] = b;
+        r.last_qp[yp] = last_qp;
+        r.have[yp] = 1;
+    } else if (r.pending == 2) {  // ... in QUALITY: its luma SSE, written by k_quality behind it on this stream
+        const int yp = r.prev_type;
+        r.last_sse[yp] = (long long)d.q_lsse[s];
         r.last_qp[yp] = last_qp;
         r.have[yp] = 1;
     }
@@ -74,8 +87,21 @@ __global__ __launch_bounds__(64) void k_rc_plan(FerDev d)
                 q = r.last_qp[1];
         }
         q = rc_clamp(q, p.qp_min, p.qp_max);
+    } else if (p.mode == FERHIP_RC_QUALITY) {
+        if (r.have[y]) {
+            q = p.qp_min;
+            for (int k = p.qp_max; k >= p.qp_min; k--)
+                if (rc_sse_fits(r, y, k, p.tsse)) {
+                    q = k;
+                    break;
+                }
+            q = rc_clamp(q, r.last_qp[y] - p.max_step, r.last_qp[y] + p.max_step);
+        } else if (r.have[1 - y]) {
+            q = r.last_qp[1 - y] + (y == 0 ? p.ip_offset : -p.ip_offset);
+        }
+        q = rc_clamp(q, p.qp_min, p.qp_max);
     }
-    r.pending = p.mode == FERHIP_RC_ABR;
+    r.pending = p.mode == FERHIP_RC_ABR ? 1 : (p.mode == FERHIP_RC_QUALITY ? 2 : 0);
     r.prev_type = y;
     d.rc[s] = r;
     d.qp[s] = q | (int)c_qpc_tab[q] << 8;

@@ -1,5 +1,6 @@
 """ctypes binding of include/ferhip.h (no torch types cross the C ABI)."""
 import ctypes as C
+import math
 import os
 from pathlib import Path
 
@@ -10,7 +11,8 @@ NAL_SLICE, NAL_IDR, NAL_AUTO = 1, 5, 0
 BUF = dict(INTERP=1, FEAT=2, SORTPOS=3, KOLIKO=4, MBTYPE=5, MV=6, MVD=7, LEVELS=8, CBP=9, TC=10, I4MODE=11,
            CUR=12, REF=13, TIMING=14, ST2N=15, ST2=16, SPEC_STAT=17, MBSIZE=18)
 TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT = 1, 2, 3, 4
-RC_CQP, RC_ABR = 0, 1
+RC_CQP, RC_ABR, RC_QUALITY = 0, 1, 2
+QM_SSE, QM_SSIM, QUALITY_RING = 1, 2, 64
 _BUF_DTYPE = {1: np.uint8, 2: np.uint16, 3: np.uint32, 4: np.int32, 5: np.int32, 6: np.int16, 7: np.int16,
               8: np.int16, 9: np.uint8, 10: np.uint8, 11: np.uint8, 12: np.uint8, 13: np.uint8, 14: np.int64, 15: np.int32, 16: np.int32,
               17: np.uint64, 18: np.int32}
@@ -28,7 +30,36 @@ class Params(C.Structure):
 class Rate(C.Structure):
     """ferhip_rate of include/ferhip.h"""
     _fields_ = [("mode", C.c_int), ("qp", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("max_step", C.c_int),
-                ("ip_offset", C.c_int), ("window", C.c_int), ("target_bits", C.c_longlong)]
+                ("ip_offset", C.c_int), ("window", C.c_int), ("target_bits", C.c_longlong), ("target_sse", C.c_longlong)]
+
+
+class QualityRec(C.Structure):
+    """ferhip_quality of include/ferhip.h"""
+    _fields_ = [("sse", C.c_uint64 * 3), ("ssim_sum", C.c_double), ("ssim_windows", C.c_uint32), ("qp", C.c_int32),
+                ("nal_type", C.c_int32), ("rbsp_bytes", C.c_uint32), ("picture", C.c_uint32)]
+
+
+_QREC = np.dtype([("sse", np.uint64, 3), ("ssim_sum", np.float64), ("ssim_windows", np.uint32), ("qp", np.int32),
+                  ("nal_type", np.int32), ("rbsp_bytes", np.uint32), ("picture", np.uint32)], align=True)
+assert _QREC.itemsize == C.sizeof(QualityRec)
+
+
+class Quality:
+    """FerHip.quality(): arrays over [n pictures, oldest first][S streams] (sse, psnr: [..][3] for Y, Cb, Cr)"""
+
+    def __init__(self, rec, W, H):
+        self.sse = rec["sse"].astype(np.int64)
+        n = np.array([W * H, W * H // 4, W * H // 4], np.float64)
+        with np.errstate(divide="ignore"):
+            self.psnr = 10 * np.log10(255.0 ** 2 * n / self.sse)  # +inf where sse == 0
+        self.ssim_sum = rec["ssim_sum"].copy()
+        self.ssim_windows = rec["ssim_windows"].astype(np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.ssim = np.where(self.ssim_windows > 0, self.ssim_sum / np.maximum(self.ssim_windows, 1), np.nan)
+        self.qp = rec["qp"].copy()
+        self.nal_type = rec["nal_type"].copy()
+        self.rbsp_bytes = rec["rbsp_bytes"].copy()
+        self.picture = rec["picture"].copy()
 
 
 def lib_path():
@@ -75,6 +106,8 @@ def load_library():
     lib.ferhip_write_pps_stream.restype = sz
     lib.ferhip_set_rate.argtypes = [vp, i, C.POINTER(Rate)]
     lib.ferhip_get_qp.argtypes = [vp, C.POINTER(i)]
+    lib.ferhip_set_quality.argtypes = [vp, i]
+    lib.ferhip_get_quality.argtypes = [vp, i, vp]
     lib.ferhip_write_nal.argtypes = [i, i, vp, sz, vp]
     lib.ferhip_write_nal.restype = sz
     lib.ferhip_encode_streams.argtypes = [vp, vp, i, vp, sz, C.POINTER(sz), vp]
@@ -283,10 +316,33 @@ class FerHip:
 
     # --- rate control
     def set_rate(self, stream=-1, mode=RC_CQP, qp=None, qp_min=0, qp_max=51, max_step=2, ip_offset=3, window=0,
-                 target_bits=0):
-        """ferhip_set_rate for one stream (or every stream, -1) from the next picture on; qp None = params.qp"""
-        r = Rate(mode, self.params.qp if qp is None else qp, qp_min, qp_max, max_step, ip_offset, window, int(target_bits))
+                 target_bits=0, target_sse=0, target_psnr=None):
+        """ferhip_set_rate for one stream (or every stream, -1) from the next picture on; qp None = params.qp.
+
+        RC_QUALITY holds the luma SSE of every picture at target_sse.  target_psnr (dB, luma) replaces it with
+        floor(255^2 * W * H / 10^(target_psnr / 10)), the SSE of a picture with that PSNR."""
+        if target_psnr is not None:
+            target_sse = self.sse_of_psnr(target_psnr)
+        r = Rate(mode, self.params.qp if qp is None else qp, qp_min, qp_max, max_step, ip_offset, window, int(target_bits),
+                 int(target_sse))
         _chk(self.lib.ferhip_set_rate(self.ctx, stream, C.byref(r)), "ferhip_set_rate")
+
+    def sse_of_psnr(self, db):
+        """the luma SSE of a picture of this context's size at `db` dB: floor(255^2 * W * H / 10^(db / 10))"""
+        return int(math.floor(255 ** 2 * self.W * self.H / 10 ** (db / 10)))
+
+    # --- quality measurement
+    def set_quality(self, flags):
+        """ferhip_set_quality: 0 = off, QM_SSE | QM_SSIM; from the next picture on"""
+        _chk(self.lib.ferhip_set_quality(self.ctx, int(flags)), "ferhip_set_quality")
+
+    def quality(self, npic=1):
+        """the last min(npic, measured, 64) pictures' records (waits for the last picture) -> Quality"""
+        out = np.zeros((max(int(npic), 1), self.S), _QREC)
+        n = self.lib.ferhip_get_quality(self.ctx, int(npic), out.ctypes.data)
+        if n < 0:
+            raise FerHipError(f"ferhip_get_quality failed with code {n}")
+        return Quality(out[:n], self.W, self.H)
 
     def last_qp(self):
         """QP of every stream's last picture (waits for it)"""

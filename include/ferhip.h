@@ -135,23 +135,70 @@ int ferhip_encode_streams(ferhip_ctx *c, const uint8_t *frames, int nframes, uin
  *   I picture: have[P] ? last_qp[P] - ip_offset : have[I] ? last_qp[I] : r->qp
  *   then clamped to [qp_min, qp_max].  An I picture's extra bits land in err and the P pictures of the next window pictures pay
  *   them back.  Entering ABR (from CQP or at create) clears err and have[]; a call in ABR keeps them.
+ * FERHIP_RC_QUALITY: holds the luma SSE of every picture (ferhip_quality.sse[0]) at target_sse, in integer arithmetic:
+ *   est(y, q) = (last_sse[y] * pow2q16(2 * (q - last_qp[y]))) >> 16   (exact: 128-bit intermediate; SSE ~ Qstep^2)
+ *   before choosing, the stream's previous picture (type y', QP q', luma SSE e), if it was coded in QUALITY, is accounted:
+ *     last_sse[y'] = e; last_qp[y'] = q'; have[y'] = 1
+ *   picture of type y: have[y]   ? the largest q in [qp_min, qp_max] with est(y, q) <= target_sse (qp_min if none),
+ *                                  clamped to last_qp[y] +- max_step
+ *                    : have[1-y] ? last_qp[1-y] + (y == P ? ip_offset : -ip_offset)
+ *                    : r->qp
+ *   then clamped to [qp_min, qp_max].  Entering QUALITY (from CQP, ABR or at create) clears have[]; a call in QUALITY keeps it.
+ *   The SSE is the one k_quality measured on the device after the previous picture: a stream in QUALITY turns the measurement
+ *   of its context on (at least FERHIP_QM_SSE) whatever ferhip_set_quality says, and window is ignored.
  * Invalid arguments return FERHIP_E_ARG: s outside -1..S-1, qp outside 0..51, a base of 38 or more before the first picture,
- * and in ABR qp_min < 0, qp_max > 51, qp_min > qp_max, max_step < 1, window < 0, |ip_offset| > 51, target_bits <= 0.
+ * and in ABR or QUALITY qp_min < 0, qp_max > 51, qp_min > qp_max, max_step < 1, |ip_offset| > 51, in ABR also window < 0
+ * and target_bits <= 0, in QUALITY target_sse <= 0.
  * ferhip_set_rate only records the settings; ferhip_get_qp is the only rate-control call that waits (for the last picture). */
 #define FERHIP_RC_CQP 0
 #define FERHIP_RC_ABR 1
+#define FERHIP_RC_QUALITY 2
 typedef struct {
-    int mode;              /* FERHIP_RC_CQP / FERHIP_RC_ABR */
-    int qp;                /* CQP: QP of every picture from the next one on; ABR: QP of the first picture */
-    int qp_min, qp_max;    /* ABR: 0 <= qp_min <= qp_max <= 51 */
-    int max_step;          /* ABR: largest change between consecutive P pictures (>= 1) */
-    int ip_offset;         /* ABR: an I picture takes the last P QP minus this */
+    int mode;              /* FERHIP_RC_CQP / FERHIP_RC_ABR / FERHIP_RC_QUALITY */
+    int qp;                /* CQP: QP of every picture from the next one on; ABR, QUALITY: QP of the first picture */
+    int qp_min, qp_max;    /* ABR, QUALITY: 0 <= qp_min <= qp_max <= 51 */
+    int max_step;          /* >= 1; ABR: largest change between P pictures, QUALITY: between pictures of one type */
+    int ip_offset;         /* ABR, QUALITY: an I picture takes the last P QP minus this */
     int window;            /* ABR: pictures over which the accumulated error is paid back; 0 = intra_every */
     long long target_bits; /* ABR: RBSP bits per picture, > 0 */
+    long long target_sse;  /* QUALITY: luma SSE per picture, > 0 */
 } ferhip_rate;
 int ferhip_set_rate(ferhip_ctx *c, int s, const ferhip_rate *r); /* s = -1: every stream; applies from the next picture */
 int ferhip_get_qp(ferhip_ctx *c, int *qp_per_stream);            /* QP of each stream's last picture (waits for it) */
 size_t ferhip_write_pps_stream(ferhip_ctx *c, int s, uint8_t *rbsp, size_t cap); /* pic_init_qp = 14 + base[s] */
+
+/* ---- quality measurement: SSE and SSIM of every picture, on the device ----
+ * With measurement on, every picture run_picture codes is compared with its source after entropy coding, by one kernel
+ * (k_quality) per picture, and one record per stream lands in a device ring of FERHIP_QUALITY_RING pictures.  Nothing
+ * waits for it: ferhip_get_quality reads the ring, so a caller that reads once every few dozen pictures adds one sync.
+ * Measuring changes no byte of the output.  It costs a copy of the source pictures (a buffer as large as one picture set,
+ * allocated on the first enable) and the kernel; off (the default) runs nothing and allocates nothing.
+ *   sse[p]      = sum over plane p (W x H luma, W/2 x H/2 chroma) of (source - reconstruction)^2, exact integers
+ *   SSIM window = the 8x8 luma block at every (x, y) with x, y multiples of 4, x <= W - 8, y <= H - 8:
+ *                 ssim_windows = (W/4 - 1) * (H/4 - 1)
+ *   in a window, a = source, b = reconstruction: s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2, s12 = sum ab,
+ *                 vars = 64 ss - s1^2 - s2^2, covar = 64 s12 - s1 s2
+ *                 num = (2 s1 s2 + 416) (2 covar + 235963), den = (s1^2 + s2^2 + 416) (vars + 235963)  (int64, den > 0)
+ *                 value = (double)num / (double)den
+ *   ssim_sum    = the sum of the window values, added in an order fixed by W, H and S: identical from run to run.
+ *   mean SSIM = ssim_sum / ssim_windows; PSNR = 10 log10(255^2 N / sse), +inf for sse = 0. */
+#define FERHIP_QM_SSE 1  /* per-plane sum of squared differences source - reconstruction */
+#define FERHIP_QM_SSIM 2 /* luma SSIM (implies the luma sums) */
+#define FERHIP_QUALITY_RING 64
+typedef struct ferhip_quality {
+    uint64_t sse[3];       /* Y, Cb, Cr over the coded picture (measured whenever the picture is) */
+    double ssim_sum;       /* sum of the per-window SSIM values above; 0 without FERHIP_QM_SSIM */
+    uint32_t ssim_windows; /* 0 without FERHIP_QM_SSIM */
+    int32_t qp, nal_type;  /* the picture's QP and FERHIP_NAL_IDR / FERHIP_NAL_SLICE */
+    uint32_t rbsp_bytes;
+    uint32_t picture;      /* index of the picture in its stream (0 = first picture encoded) */
+} ferhip_quality;
+/* flags: 0 (default) = off, else FERHIP_QM_SSE | FERHIP_QM_SSIM; applies from the next picture.  FERHIP_E_ARG for other
+ * bits, FERHIP_E_HIP when the buffers cannot be allocated. */
+int ferhip_set_quality(ferhip_ctx *c, int flags);
+/* The last min(npic, pictures measured so far, FERHIP_QUALITY_RING) pictures, oldest first, as out[k][S]; returns how many,
+ * or an error.  Waits for the last picture.  FERHIP_E_STATE if the context has never measured. */
+int ferhip_get_quality(ferhip_ctx *c, int npic, ferhip_quality *out);
 
 /* statistics of Starter::DohvatiStatistiku: brojTipova[5] per stream, accumulated */
 int ferhip_get_stats(ferhip_ctx *c, int *counts5_per_stream);
