@@ -1286,6 +1286,13 @@ extern "C" size_t ferhip_read_buffer(ferhip_ctx *c, int which, void *dst, size_t
     case FERHIP_BUF_I4MODE: src = d.i4mode; n = nm * 16; break;
     case FERHIP_BUF_TIMING: src = d.timing; n = 64 * 8; break;
     case FERHIP_BUF_ST2N: src = d.st2n; n = nm * 16; break;
+    case FERHIP_BUF_SUMA: src = d.suma; n = nm * 4 * 5 * 4; break;
+    case FERHIP_BUF_ST3: src = d.st3; n = nm * 4 * 33 * 3 * 4; break;
+    case FERHIP_BUF_ST3N: src = d.st3n; n = nm * 16; break;
+    case FERHIP_BUF_V0: src = d.v0; n = nm * 16; break;
+    case FERHIP_BUF_SPEC_HDR: src = d.spec_hdr; n = nm * 4 * 16; break;
+    case FERHIP_BUF_SPEC_L1: src = d.spec_l1; n = nm * 4 * 17 * 8; break;
+    case FERHIP_BUF_SPEC_L2: src = d.spec_l2; n = nm * 4 * 33 * 8; break;
     case FERHIP_BUF_ST2: src = d.st2; n = nm * 4 * FER_ST2_CAP * 8; break;
     case FERHIP_BUF_SPEC_STAT: src = d.spec_stat; n = 8 * 8; break;
     case FERHIP_BUF_MBSIZE: src = d.mbsize; n = nm * 8; break;

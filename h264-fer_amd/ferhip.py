@@ -9,13 +9,15 @@ import numpy as np
 NAL_SLICE, NAL_IDR, NAL_AUTO = 1, 5, 0
 
 BUF = dict(INTERP=1, FEAT=2, SORTPOS=3, KOLIKO=4, MBTYPE=5, MV=6, MVD=7, LEVELS=8, CBP=9, TC=10, I4MODE=11,
-           CUR=12, REF=13, TIMING=14, ST2N=15, ST2=16, SPEC_STAT=17, MBSIZE=18)
+           CUR=12, REF=13, TIMING=14, ST2N=15, ST2=16, SPEC_STAT=17, MBSIZE=18,
+           SUMA=19, ST3=20, ST3N=21, V0=22, SPEC_HDR=23, SPEC_L1=24, SPEC_L2=25)
 TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT = 1, 2, 3, 4
 RC_CQP, RC_ABR, RC_QUALITY = 0, 1, 2
 QM_SSE, QM_SSIM, QUALITY_RING = 1, 2, 64
 _BUF_DTYPE = {1: np.uint8, 2: np.uint16, 3: np.uint32, 4: np.int32, 5: np.int32, 6: np.int16, 7: np.int16,
               8: np.int16, 9: np.uint8, 10: np.uint8, 11: np.uint8, 12: np.uint8, 13: np.uint8, 14: np.int64, 15: np.int32, 16: np.int32,
-              17: np.uint64, 18: np.int32}
+              17: np.uint64, 18: np.int32, 19: np.int32, 20: np.int32, 21: np.int32, 22: np.int32, 23: np.int32, 24: np.int32,
+              25: np.int32}
 
 
 class FerHipError(RuntimeError):
@@ -362,7 +364,8 @@ class FerHip:
         n = self.nmb * self.S
         px = self.W * self.H * self.S
         count = {1: px * 16, 2: px * 96, 3: px, 4: 16385 * self.S, 5: n, 6: n * 8, 7: n * 8, 8: n * 400, 9: n * 2,
-                 10: n * 24, 11: n * 16, 12: self.fsz * self.S, 13: self.fsz * self.S, 14: 64, 15: n * 4, 16: n * 4 * 384 * 2, 17: 8, 18: n * 2}[which]
+                 10: n * 24, 11: n * 16, 12: self.fsz * self.S, 13: self.fsz * self.S, 14: 64, 15: n * 4, 16: n * 4 * 384 * 2, 17: 8, 18: n * 2,
+                 19: n * 20, 20: n * 4 * 99, 21: n * 4, 22: n * 4, 23: n * 16, 24: n * 4 * 34, 25: n * 4 * 66}[which]
         out = np.empty(count, _BUF_DTYPE[which])
         got = self.lib.ferhip_read_buffer(self.ctx, which, out.ctypes.data, out.nbytes)
         if got != out.nbytes:

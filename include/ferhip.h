@@ -267,6 +267,23 @@ int ferhip_inter_encoding(ferhip_ctx *c);
                                  macroblock of the last I picture */
 #define FERHIP_BUF_ST2 16     /* int32  [S][nmb][4][384][2] the candidates (position relative to the block, feature distance); a crowded
                                  partition (count > 384) holds its summary instead: [40] = (last step, distance bound), [41] = (zeros, 0) */
+/* The lists the four motion kernels hand each other, as they stand after ferhip_inter_encoding (list-level parity
+ * tests; the layouts below are ABI for tests).  A "packed vector" is one int32: (x & 0xffff) | (y << 16), x and y
+ * signed 16-bit, in quarter samples for vectors and in whole samples for the centre of SPEC_HDR.  SPEC_HDR, SPEC_L1 and
+ * SPEC_L2 are written by k_me_spec only: with FERHIP_TUNE_SPECULATE = 0, for a stream whose picture is an I picture, and
+ * (the two lists) for a partition whose header has bit 16 clear they hold stale or uninitialised data; SUMA, ST3, ST3N
+ * and V0 likewise belong to the last P picture of the stream. */
+#define FERHIP_BUF_SUMA 19    /* int32  [S][nmb][4][5] the five box sums of every 8x8 source block (F/moestimation.cpp:440-451), k_me_pre */
+#define FERHIP_BUF_ST3 20     /* int32  [S][nmb][4][33][3] stage-3 survivors in list order: (x, y, SAD), x and y in quarter samples;
+                                 entries [0, ST3N) are set, k_me_pre */
+#define FERHIP_BUF_ST3N 21    /* int32  [S][nmb][4] number of stage-3 survivors, k_me_pre */
+#define FERHIP_BUF_V0 22      /* int32  [S][nmb][4] packed vector: the first stage-3 survivor of smallest SAD (0 with no survivor), k_me_pre */
+#define FERHIP_BUF_SPEC_HDR 23 /* int32 [S][nmb][4][4], k_me_spec: [0] = packed guessed integer centre (genx, geny) = guessed predictor >> 2;
+                                 [1] = cnt1 | cnt2 << 8 | lists written << 16 | P_Skip verdict present << 17 (cnt1 / cnt2 = entries of
+                                 SPEC_L1 / SPEC_L2; bit 17 is set on partition 0 only); [2] = packed guessed P_Skip vector (partition 0);
+                                 [3] = 1 when the guessed P_Skip test passed: no lists for any partition of the macroblock */
+#define FERHIP_BUF_SPEC_L1 24 /* int32  [S][nmb][4][17][2] stage-1 list for the guessed centre, list order: (packed vector, SAD); entries [0, cnt1) */
+#define FERHIP_BUF_SPEC_L2 25 /* int32  [S][nmb][4][33][2] re-ranked stage-2 list for the guessed centre: (packed vector, SAD); entries [0, cnt2) */
 size_t ferhip_read_buffer(ferhip_ctx *c, int which, void *dst, size_t cap);
 /* set the reference picture (dpb) directly, [S][W*H*3/2] host */
 int ferhip_set_reference(ferhip_ctx *c, const void *src);

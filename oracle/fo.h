@@ -163,7 +163,26 @@ typedef struct fo_ctx {
     int (*dbg_mvx)[4][4], (*dbg_mvy)[4][4];
     /* test hook: what coded_mb_size returned for the Intra16x16 / Intra4x4 alternative of every macroblock (I pictures) */
     int (*dbg_mbsize)[2];
+    /* test hook: the candidate lists of interEncoding, one record per 8x8 partition; NULL (default) = not recorded */
+    struct fo_me_rec *me_rec;
 } fo_ctx;
+
+/* What fo_interEncoding searched for one 8x8 partition (fo_dbg_me_record).  List 0 = stage 1 (17 entries around the
+ * predictor), 1 = stage 2 (33 of the bucket walk), 2 = stage 3 (33, centre 0, wide pass then local pass).  Entries are
+ * in list order; metric = what the entry held before eval_list replaced it with the SAD.  A record is all ints. */
+typedef struct fo_me_rec {
+    int searched; /* 0: the macroblock was coded P_Skip (or is not of the last P picture), nothing else is set */
+    int mvpx, mvpy;
+    int suma[5];
+    int n[3];
+    int bx[3][33], by[3][33], sad[3][33], metric[3][33];
+} fo_me_rec;
+#define FO_ME_REC_INTS (8 + 3 + 12 * 33)
+#ifndef __cplusplus
+_Static_assert(sizeof(fo_me_rec) == FO_ME_REC_INTS * sizeof(int), "fo_py.Oracle.me_lists slices the record by this layout");
+#endif
+int *fo_dbg_me_record(struct fo_ctx *c, int on); /* fo_debug.c: start (records zeroed) / stop recording */
+int *fo_dbg_me_lists(struct fo_ctx *c);          /* [nmb][4] fo_me_rec, NULL when recording is off */
 
 fo_ctx *fo_create(int W, int H);
 void fo_destroy(fo_ctx *c);

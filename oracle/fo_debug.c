@@ -4,6 +4,7 @@
  * path with the CPU restatement through ctypes.
  */
 #include "fo.h"
+#include <stdlib.h>
 #include <string.h>
 
 uint8_t *fo_dbg_plane(fo_ctx *c, int which) /* 0..2 frame, 3..5 dpb */
@@ -60,3 +61,19 @@ void fo_dbg_set_mv(fo_ctx *c, int mb, int sub, int part, int mvx, int mvy)
     c->mvy[mb][sub][part] = mvy;
 }
 uint8_t *fo_dbg_dpb(fo_ctx *c, int k) { return k == 0 ? c->dL : c->dC[k - 1]; }
+
+/* candidate lists of fo_interEncoding: on != 0 starts recording (records zeroed), 0 stops it; returns the records,
+ * [nmb][4] fo_me_rec (FO_ME_REC_INTS ints each), or NULL when recording is off.  Recording changes no output. */
+int *fo_dbg_me_record(fo_ctx *c, int on)
+{
+    if (!on) {
+        free(c->me_rec);
+        c->me_rec = NULL;
+        return NULL;
+    }
+    if (!c->me_rec) c->me_rec = (fo_me_rec *)malloc((size_t)c->nmb * 4 * sizeof(fo_me_rec));
+    if (!c->me_rec) return NULL; /* out of memory: recording stays off */
+    memset(c->me_rec, 0, (size_t)c->nmb * 4 * sizeof(fo_me_rec));
+    return (int *)c->me_rec;
+}
+int *fo_dbg_me_lists(fo_ctx *c) { return (int *)c->me_rec; }

@@ -74,6 +74,7 @@ void fo_destroy(fo_ctx *c)
     free(c->dbg_mvx);
     free(c->dbg_mbsize);
     free(c->dbg_mvy);
+    free(c->me_rec);
     for (int i = 0; i < 16; i++) {
         free(c->interp[i]);
         for (int k = 0; k < 5; k++) free(c->kar[k][i]);

@@ -628,13 +628,22 @@ static void mestimation(fo_ctx *c, me_list *l, int sx, int sy, int granica, int 
             }
 }
 
+/* rec (may be NULL) receives the entries that are evaluated, in list order, as list number `st` */
 static void eval_list(fo_ctx *c, me_list *l, int n, int need_bmin, int part, int mvpx, int mvpy, int *bmin, int *bx,
-                      int *by)
+                      int *by, fo_me_rec *rec, int st)
 {
     for (int j = 0; j <= n; j++) {
         if (need_bmin && !(l->bmins[j] < 100000000)) continue;
         if (!(l->bxs[j] < 100000000 && l->bys[j] < 100000000)) continue;
+        int metric = l->bmins[j];
         l->bmins[j] = sad_mvs(c, l->bxs[j], l->bys[j], part);
+        if (rec) {
+            int k = rec->n[st]++;
+            rec->bx[st][k] = l->bxs[j];
+            rec->by[st][k] = l->bys[j];
+            rec->sad[st][k] = l->bmins[j];
+            rec->metric[st][k] = metric;
+        }
         int cost = l->bmins[j] + iabs(l->bxs[j] - mvpx) + iabs(l->bys[j] - mvpy);
         if (cost < *bmin) {
             *bmin = cost;
@@ -674,6 +683,7 @@ void fo_interEncoding(fo_ctx *c, int predL[16][16], int predCr[8][8], int predCb
     } else {
         c->MAXDIFF = c->maxdiff_set;
     }
+    if (c->me_rec) memset(&c->me_rec[cur * 4], 0, 4 * sizeof(fo_me_rec));
     int exact = 0;
     for (int i = 0; i < 16; i++)
         for (int j = 0; j < 16; j++) exact += iabs(c->L[(yp + i) * W + xp + j] - predL[i][j]) <= c->MAXDIFF;
@@ -703,6 +713,13 @@ void fo_interEncoding(fo_ctx *c, int predL[16][16], int predCr[8][8], int predCb
                 l.suma[3] += ((ty % 4) > 1) ? 0 : v;
                 l.suma[4] += ((tx % 4) > 1) ? 0 : v;
             }
+        fo_me_rec *rec = c->me_rec ? &c->me_rec[cur * 4 + i] : NULL;
+        if (rec) {
+            rec->searched = 1;
+            rec->mvpx = mvpx;
+            rec->mvpy = mvpy;
+            for (int te = 0; te < 5; te++) rec->suma[te] = l.suma[te];
+        }
         int bx = 0, by = 0, bmin;
         for (int j = 0; j < 85; j++) {
             l.bmins[j] = 1000000000;
@@ -710,7 +727,7 @@ void fo_interEncoding(fo_ctx *c, int predL[16][16], int predCr[8][8], int predCb
         }
         mestimation(c, &l, relx + xp, rely + yp, c->window / 16, 1, 1, genx, geny, genx, geny);
         bmin = 2000000000;
-        eval_list(c, &l, 16, 0, i, mvpx, mvpy, &bmin, &bx, &by);
+        eval_list(c, &l, 16, 0, i, mvpx, mvpy, &bmin, &bx, &by, rec, 0);
         if (!c->basic) {
             int tren = 0;
             for (int j = 0; j < 85; j++) l.bmins[j] = 1000000000;
@@ -729,11 +746,11 @@ void fo_interEncoding(fo_ctx *c, int predL[16][16], int predCr[8][8], int predCb
                 }
                 if (tren > 128) break;
             }
-            eval_list(c, &l, 32, 1, i, mvpx, mvpy, &bmin, &bx, &by);
+            eval_list(c, &l, 32, 1, i, mvpx, mvpy, &bmin, &bx, &by, rec, 1);
             for (int j = 0; j < 85; j++) l.bmins[j] = 1000000000;
             mestimation(c, &l, relx + xp, rely + yp, c->window / 2, 1, 16, 0, 0, 0, 0);
             mestimation(c, &l, relx + xp, rely + yp, c->window / 16, 1, 1, 0, 0, 0, 0);
-            eval_list(c, &l, 32, 1, i, mvpx, mvpy, &bmin, &bx, &by);
+            eval_list(c, &l, 32, 1, i, mvpx, mvpy, &bmin, &bx, &by, rec, 2);
         }
         mvx[i] = bx;
         mvy[i] = by;

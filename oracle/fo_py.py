@@ -58,6 +58,10 @@ def lib():
         L.fo_dbg_mbsize.argtypes = [vp]
         L.fo_dbg_levels.restype = vp
         L.fo_dbg_levels.argtypes = [vp]
+        L.fo_dbg_me_record.restype = vp
+        L.fo_dbg_me_record.argtypes = [vp, i]
+        L.fo_dbg_me_lists.restype = vp
+        L.fo_dbg_me_lists.argtypes = [vp]
         L.fo_dbg_set_mb.argtypes = [vp, i, i, i, i]
         L.fo_dbg_set_mv.argtypes = [vp, i, i, i, i, i]
         L.fo_mc_sub.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i]
@@ -150,6 +154,26 @@ class Oracle:
     def mbsize(self):
         """coded_mb_size of the Intra16x16 / Intra4x4 alternative of every macroblock of the last I picture"""
         return _arr(self.L.fo_dbg_mbsize(self.c), self.nmb * 2, np.int32).reshape(self.nmb, 2).copy()
+
+    def record_me(self, on=True):
+        """Start / stop recording the candidate lists of interEncoding (off by default; changes no output)."""
+        if not self.L.fo_dbg_me_record(self.c, int(on)) and on:
+            raise MemoryError("fo_dbg_me_record")
+
+    ME_REC_INTS = 8 + 3 + 12 * 33  # FO_ME_REC_INTS
+
+    def me_lists(self):
+        """What interEncoding searched in the last P picture, per 8x8 partition (fo_me_rec of fo.h): a dict of arrays
+        with a leading [nmb * 4]: searched, mvp [2], suma [5], n [3] (stage 1, 2, 3), and bx, by, sad, metric [3][33]
+        in list order (entries [0, n) are set)."""
+        p = self.L.fo_dbg_me_lists(self.c)
+        if not p:
+            raise RuntimeError("record_me() was not called")
+        a = _arr(p, self.nmb * 4 * self.ME_REC_INTS, np.int32).reshape(self.nmb * 4, self.ME_REC_INTS).copy()
+        out = dict(searched=a[:, 0], mvp=a[:, 1:3], suma=a[:, 3:8], n=a[:, 8:11])
+        for k, name in enumerate(("bx", "by", "sad", "metric")):
+            out[name] = a[:, 11 + k * 99: 11 + (k + 1) * 99].reshape(-1, 3, 33)
+        return out
 
     # ---- one macroblock at a time (per-macroblock KATs)
     LEVELS = (("lumaLevel", 256), ("dc16", 16), ("ac16", 256), ("cdc", 8), ("cac", 128))

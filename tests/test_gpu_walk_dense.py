@@ -9,6 +9,7 @@ asserts that they do.
 """
 import numpy as np
 import pytest
+from me_model import WalkModel as Model
 
 W, H = 176, 144
 CAP = 384  # FER_ST2_CAP
@@ -37,51 +38,6 @@ def _content(pkg, kind, t):
 def _sums(cur, sx, sy):
     b = cur[sy:sy + 8, sx:sx + 8].astype(np.int64)
     return [int(b.sum()), int(b[:4].sum()), int(b[:, :4].sum()), int(b[[0, 1, 4, 5]].sum()), int(b[:, [0, 1, 4, 5]].sum())]
-
-
-class Model:
-    """The walk of F/moestimation.cpp:470-496 over the sorted feature table of the reference (plane 0)."""
-
-    def __init__(self, kar):
-        self.k = [np.asarray(k, np.int64).reshape(-1) for k in kar]
-        a = self.k[0]
-        pos = np.arange(a.size)
-        tx, ty = pos % W, pos // W
-        order = np.lexsort((ty, tx, a))  # bucket, then tx, then ty
-        self.a, self.tx, self.ty = a[order], tx[order], ty[order]
-        self.q = [k[order] for k in self.k[1:]]
-        self.start = np.searchsorted(self.a, np.arange(16385))
-
-    def walk(self, su, sx, sy):
-        """-> list of (rel, D) in arrival order up to the stop, the stop step, and the records of every slice read
-        (step, side, first index, count, indices passing the filter) up to the stop step's group end."""
-        s0 = su[0]
-        out, slices = [], []
-        count, jend = 0, 180
-        for j in range(181):
-            for side in (0, 1):
-                a = s0 + j if side else s0 - j
-                if a < 0 or a > 16383:
-                    slices.append((j, side, 0, 0, np.zeros(0, np.int64)))
-                    continue
-                lo, hi = self.start[a], self.start[a + 1]
-                tx, ty = self.tx[lo:hi], self.ty[lo:hi]
-                q = [x[lo:hi] for x in self.q]
-                ok = (np.abs(tx - sx) + np.abs(ty - sy) < 280) & (np.abs(q[0] - su[1]) < 100) & (np.abs(q[1] - su[2]) < 100)
-                D = j + sum(np.abs(su[i + 1] - q[i]) for i in range(4)) + sum(np.abs((s0 - su[i + 1]) - (a - q[i])) for i in range(4))
-                for t in np.nonzero(ok)[0]:
-                    out.append(((int(tx[t] - sx) << 16) | (int(ty[t] - sy) & 0xffff), int(D[t])))
-                slices.append((j, side, lo, hi - lo, np.nonzero(ok)[0]))
-                count += int(ok.sum())
-            if count > 128:
-                jend = j
-                break
-        for j in range(jend + 1, min(jend - jend % 16 + 16, 181)):  # the rest of the group: in its batches, not read
-            for side in (0, 1):
-                a = s0 + j if side else s0 - j
-                n = int(self.start[a + 1] - self.start[a]) if 0 <= a <= 16383 else 0
-                slices.append((j, side, 0, n, np.zeros(0, np.int64)))
-        return out, jend, slices
 
 
 def _cases(slices, jend, crowded):
