@@ -62,6 +62,14 @@ struct ferhip_ctx {
     int up_next, up_ready;  // slot the next upload fills; uploads waiting to be made current
     int cur_set;
     bool refprep_valid;
+    // live contexts: presence masks.  An ingest mask goes to the device through a pinned ring of its own (like the header
+    // ring: a pinned source is read when the copy executes); the mask of k_frame_sad needs one slot only, because the
+    // read-back of the SADs waits for the stream
+    uint8_t *d_present, *d_sadskip;   // device [S]
+    uint8_t *h_pres_ring, *h_sadskip; // pinned [FER_HDR_SLOTS][S], [S]
+    hipEvent_t pres_ev[FER_HDR_SLOTS];
+    int pres_slot;
+    std::vector<uint8_t> up_mask[2];  // ferhip_upload_frames_live: the mask of each staging slot (empty = every stream)
     // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof;
     struct Span { int phase; hipEvent_t a, b; long launches; };
@@ -181,7 +189,9 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     c->q_count = 0;
     c->h_status = nullptr;
     c->h_sad = nullptr;
-    for (int i = 0; i < FER_HDR_SLOTS; i++) c->hdr_ev[i] = nullptr;
+    for (int i = 0; i < FER_HDR_SLOTS; i++) c->hdr_ev[i] = c->pres_ev[i] = nullptr;
+    c->d_present = c->d_sadskip = c->h_pres_ring = c->h_sadskip = nullptr;
+    c->pres_slot = 0;
     c->planes[0] = c->planes[1] = nullptr;
     c->st_copy = nullptr;
     c->stage[0] = c->stage[1] = nullptr;
@@ -285,6 +295,8 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     rc |= dalloc(c, &d.dec_qp, nm);
     rc |= dalloc(c, &d.dec_state, (size_t)4 * S);
     rc |= dalloc(c, &d.dec_cac, (size_t)128 * S);
+    rc |= dalloc(c, &c->d_present, (size_t)S);
+    rc |= dalloc(c, &c->d_sadskip, (size_t)S);
     int n = W * H;
     c->sort.tmp_bytes = fer_sort_tmp_bytes(n, S);
     rc |= dalloc(c, &c->sort.rec_tmp, decode_only ? (size_t)1 : (size_t)((size_t)n * S * 3));
@@ -302,13 +314,16 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     if (hipHostMalloc((void **)&c->h_hdr_ring, sizeof(uint32_t) * 4 * S * FER_HDR_SLOTS) != hipSuccess ||
         hipHostMalloc((void **)&c->h_rate_ring, sizeof(FerRcPar) * S * FER_HDR_SLOTS) != hipSuccess ||
         hipHostMalloc((void **)&c->h_len, sizeof(uint32_t) * S) != hipSuccess ||
+        hipHostMalloc((void **)&c->h_pres_ring, (size_t)S * FER_HDR_SLOTS) != hipSuccess ||
+        hipHostMalloc((void **)&c->h_sadskip, (size_t)S) != hipSuccess ||
         hipHostMalloc((void **)&c->h_status, sizeof(int) * S) != hipSuccess ||
         hipHostMalloc((void **)&c->h_sad, sizeof(unsigned long long) * S) != hipSuccess) {
         ferhip_destroy(c);
         return FERHIP_E_HIP;
     }
     for (int i = 0; i < FER_HDR_SLOTS; i++)
-        if (hipEventCreateWithFlags(&c->hdr_ev[i], hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&c->hdr_ev[i], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&c->pres_ev[i], hipEventDisableTiming) != hipSuccess) {
             ferhip_destroy(c);
             return FERHIP_E_HIP;
         }
@@ -353,8 +368,12 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
     for (void *p : c->allocs) hipFree(p);
     if (c->h_hdr_ring) hipHostFree(c->h_hdr_ring);
     if (c->h_rate_ring) hipHostFree(c->h_rate_ring);
-    for (int i = 0; i < FER_HDR_SLOTS; i++)
+    for (int i = 0; i < FER_HDR_SLOTS; i++) {
         if (c->hdr_ev[i]) hipEventDestroy(c->hdr_ev[i]);
+        if (c->pres_ev[i]) hipEventDestroy(c->pres_ev[i]);
+    }
+    if (c->h_pres_ring) hipHostFree(c->h_pres_ring);
+    if (c->h_sadskip) hipHostFree(c->h_sadskip);
     if (c->h_len) hipHostFree(c->h_len);
     if (c->h_status) hipHostFree(c->h_status);
     if (c->h_sad) hipHostFree(c->h_sad);
@@ -379,10 +398,13 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
 // [S][Y|U|V] interleaved per stream  <->  plane-major [Y of all streams][U ...][V ...]
 // I420 pictures, stream-major [S][Y|Cb|Cr] <-> the context's plane-major picture set [plane][S][...], both in
 // device memory: one launch instead of three copies per stream.  16 bytes per thread (plane sizes are multiples of 64).
-__global__ __launch_bounds__(256) void k_repack(uint8_t *set, uint8_t *frames, size_t ysz, size_t csz, int S, int to_set)
+// present (device [S], or null = every stream): a stream whose byte is 0 is left out -- its slot of `frames` is never read
+__global__ __launch_bounds__(256) void k_repack(uint8_t *set, uint8_t *frames, size_t ysz, size_t csz, int S, int to_set,
+                                                const uint8_t *present)
 {
     const size_t fsz = ysz + 2 * csz;
     const int s = blockIdx.y;
+    if (present && !present[s]) return;
     for (size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; o < fsz; o += (size_t)gridDim.x * blockDim.x * 16) {
         size_t po;
         if (o < ysz)
@@ -399,16 +421,29 @@ __global__ __launch_bounds__(256) void k_repack(uint8_t *set, uint8_t *frames, s
     }
 }
 
-static int copy_frames(ferhip_ctx *c, uint8_t *set, const uint8_t *src, uint8_t *dst, hipMemcpyKind kind)
+// present (host [S], or null = every stream): only the pictures of streams with a non-zero byte are read from src
+static int copy_frames(ferhip_ctx *c, uint8_t *set, const uint8_t *src, uint8_t *dst, hipMemcpyKind kind,
+                       const uint8_t *present = nullptr)
 {
     FerDev &d = c->d;
     size_t fsz = d.ysz * 3 / 2;
     if (kind == hipMemcpyDeviceToDevice && (((uintptr_t)(src ? src : dst)) & 15) == 0) {
+        const uint8_t *d_mask = nullptr;
+        if (present) {  // the mask rides a pinned ring to the device, ordered before the repack on the context's stream
+            c->pres_slot = (c->pres_slot + 1) % FER_HDR_SLOTS;
+            CK(hipEventSynchronize(c->pres_ev[c->pres_slot]));
+            uint8_t *h = c->h_pres_ring + (size_t)c->pres_slot * d.S;
+            for (int s = 0; s < d.S; s++) h[s] = present[s] ? 1 : 0;
+            CK(hipMemcpyAsync(c->d_present, h, (size_t)d.S, hipMemcpyHostToDevice, c->st));
+            CK(hipEventRecord(c->pres_ev[c->pres_slot], c->st));
+            d_mask = c->d_present;
+        }
         hipLaunchKernelGGL(k_repack, dim3(256, d.S), dim3(256), 0, c->st, set, (uint8_t *)(src ? src : dst), d.ysz, d.csz, d.S,
-                           src ? 1 : 0);
+                           src ? 1 : 0, d_mask);
         return 0;
     }
     for (int s = 0; s < d.S; s++) {
+        if (present && !present[s]) continue;
         uint8_t *py = set + (size_t)s * d.ysz;
         uint8_t *pu = set + (size_t)d.S * d.ysz + (size_t)s * d.csz;
         uint8_t *pv = set + (size_t)d.S * (d.ysz + d.csz) + (size_t)s * d.csz;
@@ -438,12 +473,31 @@ extern "C" int ferhip_set_frames(ferhip_ctx *c, const void *src, int host)
     return 0;
 }
 
+// The pictures of the streams that have one in this call (present[s] != 0); the slots of the others are never read
+extern "C" int ferhip_set_frames_live(ferhip_ctx *c, const void *src, int host, const uint8_t *present)
+{
+    if (!c || !src || !present) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = copy_frames(c, c->planes[c->cur_set], (const uint8_t *)src, nullptr,
+                         host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, present);
+    if (rc) return rc;
+    if (host) CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
 // ---- asynchronous ingest: ReadFromY4M's successor for many streams (row f3) ----
 // ferhip_upload_frames starts the H2D copy of the NEXT pictures ([S][W*H*3/2], pinned host memory) on a copy stream
 // of its own and returns; up to two uploads may be in flight.  ferhip_set_frames_uploaded makes the oldest one the
 // current picture (the repack runs on the encode stream behind the copy).  So the upload of picture t + 1 overlaps
 // the encode of picture t.
-extern "C" int ferhip_upload_frames(ferhip_ctx *c, const void *pinned_src)
+static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *present);
+extern "C" int ferhip_upload_frames(ferhip_ctx *c, const void *pinned_src) { return upload_frames(c, pinned_src, nullptr); }
+extern "C" int ferhip_upload_frames_live(ferhip_ctx *c, const void *pinned_src, const uint8_t *present)
+{
+    if (!present) return FERHIP_E_ARG;
+    return upload_frames(c, pinned_src, present);
+}
+static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *present)
 {
     if (!c || !pinned_src) return FERHIP_E_ARG;
     (void)hipSetDevice(c->device);
@@ -472,7 +526,26 @@ extern "C" int ferhip_upload_frames(ferhip_ctx *c, const void *pinned_src)
     if (c->up_ready >= 2) return FERHIP_E_STATE;
     const int k = c->up_next;
     CK(hipStreamWaitEvent(c->st_copy, c->up_used[k], 0));  // the repack that last read this slot
-    CK(hipMemcpyAsync(c->stage[k], pinned_src, bytes, hipMemcpyHostToDevice, c->st_copy));
+    if (!present) {
+        c->up_mask[k].clear();
+        CK(hipMemcpyAsync(c->stage[k], pinned_src, bytes, hipMemcpyHostToDevice, c->st_copy));
+    } else {
+        // only the pictures of present streams cross the bus, one copy per run of neighbouring present streams; the mask
+        // stays with the staging slot until ferhip_set_frames_uploaded repacks it
+        c->up_mask[k].assign(present, present + d.S);
+        const size_t fsz = d.ysz * 3 / 2;
+        for (int s = 0; s < d.S;) {
+            if (!present[s]) {
+                s++;
+                continue;
+            }
+            int e = s;
+            while (e < d.S && present[e]) e++;
+            CK(hipMemcpyAsync(c->stage[k] + (size_t)s * fsz, (const uint8_t *)pinned_src + (size_t)s * fsz, (size_t)(e - s) * fsz,
+                              hipMemcpyHostToDevice, c->st_copy));
+            s = e;
+        }
+    }
     CK(hipEventRecord(c->up_done[k], c->st_copy));
     c->up_next ^= 1;
     c->up_ready++;
@@ -486,7 +559,8 @@ extern "C" int ferhip_set_frames_uploaded(ferhip_ctx *c)
     (void)hipSetDevice(c->device);
     const int k = (c->up_next + 2 - c->up_ready) & 1;  // oldest upload in flight
     CK(hipStreamWaitEvent(c->st, c->up_done[k], 0));
-    int rc = copy_frames(c, c->planes[c->cur_set], c->stage[k], nullptr, hipMemcpyDeviceToDevice);
+    int rc = copy_frames(c, c->planes[c->cur_set], c->stage[k], nullptr, hipMemcpyDeviceToDevice,
+                         c->up_mask[k].empty() ? nullptr : c->up_mask[k].data());
     if (rc) return rc;
     CK(hipEventRecord(c->up_used[k], c->st));
     c->up_ready--;
@@ -650,6 +724,12 @@ static void build_header(ferhip_ctx *c, int s, int nal_type)
 {
     StreamState &t = c->ss[s];
     int slice_type;
+    if (nal_type == FERHIP_NAL_NONE) {  // no picture of this stream in this call: its slice-level state stays
+        c->h_hdr[s * 4 + 0] = c->h_hdr[s * 4 + 1] = c->h_hdr[s * 4 + 2] = 0;
+        c->h_hdr[s * 4 + 3] = FER_PIC_ABSENT;
+        c->types[s] = FER_PIC_ABSENT;
+        return;
+    }
     if (nal_type == FERHIP_NAL_IDR) {  // F/rbsp_encoding.cpp:142-164
         slice_type = 2;
         if (!t.first_idr_done) {
@@ -751,34 +831,45 @@ static int quality_alloc(ferhip_ctx *c)
     return 0;
 }
 
-// selectNALUnitType, F/ref_frames.cpp:185-234: nt[s] in = request (AUTO / IDR / SLICE), out = decision
+// selectNALUnitType, F/ref_frames.cpp:185-234: nt[s] in = request (AUTO / IDR / SLICE / NONE), out = decision (NONE stays)
 static int decide_types(ferhip_ctx *c, const int *nal_type, std::vector<int> &nt)
 {
     FerDev &d = c->d;
     const int S = d.S;
     nt.assign(S, 0);
-    bool need_sad = false;
+    const int UNDECIDED = -2;
+    bool need_sad = false, any_none = false;
     for (int s = 0; s < S; s++) {
         int req = nal_type ? nal_type[s] : FERHIP_NAL_AUTO;
         StreamState &t = c->ss[s];
-        if (req == FERHIP_NAL_IDR || req == FERHIP_NAL_SLICE) {
+        if (req == FERHIP_NAL_NONE) {
+            nt[s] = FERHIP_NAL_NONE;
+            any_none = true;
+        } else if (req == FERHIP_NAL_IDR || req == FERHIP_NAL_SLICE) {
             nt[s] = (!t.have_dpb) ? FERHIP_NAL_IDR : req;
         } else if (!t.have_dpb || t.frames_done % c->p.intra_every == 0) {
             nt[s] = FERHIP_NAL_IDR;
         } else {
-            nt[s] = -1;
+            nt[s] = UNDECIDED;
             need_sad = true;
         }
     }
     if (need_sad) {
+        const uint8_t *skip = nullptr;
+        if (any_none) {
+            // absent streams take no part: with the SAD read-back waiting for the stream below, one pinned slot serves
+            for (int s = 0; s < S; s++) c->h_sadskip[s] = nt[s] == FERHIP_NAL_NONE;
+            CK(hipMemcpyAsync(c->d_sadskip, c->h_sadskip, (size_t)S, hipMemcpyHostToDevice, c->st));
+            skip = c->d_sadskip;
+        }
         {
             ProfScope ps(c, FERHIP_PH_FRAME_SAD, 1);
-            fer_launch_frame_sad(d, c->st);
+            fer_launch_frame_sad(d, skip, c->st);
         }
         CK(hipMemcpyAsync(c->h_sad, d.sad, sizeof(unsigned long long) * S, hipMemcpyDeviceToHost, c->st));
         CK(hipStreamSynchronize(c->st));
         for (int s = 0; s < S; s++)
-            if (nt[s] == -1) nt[s] = c->h_sad[s] > ((unsigned long long)d.nmb << 12) ? FERHIP_NAL_IDR : FERHIP_NAL_SLICE;
+            if (nt[s] == UNDECIDED) nt[s] = c->h_sad[s] > ((unsigned long long)d.nmb << 12) ? FERHIP_NAL_IDR : FERHIP_NAL_SLICE;
     }
     return 0;
 }
@@ -788,7 +879,10 @@ extern "C" int ferhip_select_nal_type(ferhip_ctx *c, int *nal_type_out)
     if (!c || !nal_type_out) return FERHIP_E_ARG;
     (void)hipSetDevice(c->device);
     std::vector<int> nt;
-    int rc = decide_types(c, nullptr, nt);
+    // on input FERHIP_NAL_NONE marks the streams that have no picture (they keep it); every other stream is decided as AUTO
+    std::vector<int> req(c->d.S);
+    for (int s = 0; s < c->d.S; s++) req[s] = nal_type_out[s] == FERHIP_NAL_NONE ? FERHIP_NAL_NONE : FERHIP_NAL_AUTO;
+    int rc = decide_types(c, req.data(), nt);
     if (rc) return rc;
     for (int s = 0; s < c->d.S; s++) nal_type_out[s] = nt[s];
     return 0;
@@ -801,16 +895,24 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
     std::vector<int> nt;
     int rc0 = decide_types(c, nal_type, nt);
     if (rc0) return rc0;
-    bool anyP = false, anyI = false;
+    bool anyP = false, anyI = false, anyNone = false;
     if (hdr_begin(c)) return FERHIP_E_HIP;
     for (int s = 0; s < S; s++) {
         build_header(c, s, nt[s]);
         if (nal_type) nal_type[s] = nt[s];
         anyP |= c->types[s] == 0;
         anyI |= c->types[s] == 2;
+        anyNone |= c->types[s] == FER_PIC_ABSENT;
     }
     if (hdr_upload(c)) return FERHIP_E_HIP;
     fer_launch_rc_plan(d, c->st);  // each stream's QP and slice_qp_delta, before anything reads qp[] or hdr[] (fer_rate.hip)
+    if (!anyP && !anyI) {
+        // every stream sat the call out: k_rc_plan has accounted what was pending and set every RBSP length to 0; no
+        // picture set is touched or swapped, nothing is measured, no stream's state moves
+        CK(hipGetLastError());
+        return 0;
+    }
+    if (anyNone) fer_launch_carry_ref(d, c->st);  // absent streams keep their reference picture across the swap below
     // quality measurement: the source is reconstructed in place, so it is kept before the first launch that reconstructs
     const int qflags = quality_flags(c);
     if (qflags) {
@@ -899,7 +1001,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
         fer_launch_cavlc(d, c->st);
     }
     if (qflags) {  // after entropy coding: the record carries the RBSP length (fer_quality.hip)
-        fer_launch_quality(d, qflags, (int)(c->q_count % FERHIP_QUALITY_RING), c->ss[0].frames_done, c->st);
+        fer_launch_quality(d, qflags, (int)(c->q_count % FERHIP_QUALITY_RING), c->st);
         c->q_count++;
     }
     CK(hipGetLastError());
@@ -908,6 +1010,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
     bind_planes(c);
     c->refprep_valid = false;
     for (int s = 0; s < S; s++) {
+        if (c->types[s] == FER_PIC_ABSENT) continue;
         c->ss[s].have_dpb = 1;
         c->ss[s].frames_done++;
     }
@@ -970,6 +1073,7 @@ extern "C" int ferhip_encode_picture(ferhip_ctx *c, int *nal_type, uint8_t *rbsp
         }
         rbsp_len[s] = c->h_len[s];
         if (c->h_len[s] > rbsp_stride) return FERHIP_E_ARG;
+        if (c->h_len[s] == 0) continue;  // FERHIP_NAL_NONE
         CK(hipMemcpyAsync(rbsp + (size_t)s * rbsp_stride, (const uint8_t *)d.bits + (size_t)s * d.bits_cap_words * 4,
                           c->h_len[s], hipMemcpyDeviceToHost, c->st));
     }
@@ -1069,6 +1173,21 @@ extern "C" int ferhip_set_rate(ferhip_ctx *c, int s, const ferhip_rate *r)
         if (c->ss[k].frames_done == 0) p.base = r->qp;
     }
     c->rate_dirty = true;
+    return 0;
+}
+
+// Slot s as in a freshly created context (a new feed takes the slot); the other slots are untouched.  The device half is
+// one small kernel on the context's stream, behind the slot's last picture; nothing waits.
+extern "C" int ferhip_reset_stream(ferhip_ctx *c, int s)
+{
+    if (!c || s < 0 || s >= c->d.S) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    c->ss[s] = StreamState{0, 0, 0, 0, 0, 0};
+    c->rate[s] = FerRcPar{FERHIP_RC_CQP, c->p.qp, 0, 51, 1, 0, c->p.intra_every, c->p.qp, 0, 0, 0};
+    c->rate_dirty = true;
+    c->types[s] = 2;
+    fer_launch_reset_stream(c->d, s, c->p.qp | k_qpc[c->p.qp] << 8, c->st);
+    CK(hipGetLastError());
     return 0;
 }
 

@@ -22,6 +22,7 @@ __global__ __launch_bounds__(64) void k_cavlc(FerDev d)
     const int mb = blockIdx.x * blockDim.x + threadIdx.x;
     if (mb > d.nmb) return;
     const int slice_type = (int)d.hdr[s * 4 + 3];
+    if (slice_type == FER_PIC_ABSENT) return;  // no picture of this stream: nothing is sized or written
     const int *mbt = d.mb_type + (size_t)s * d.nmb;
     uint32_t *sizes = d.mb_bits + (size_t)s * (d.nmb + 1);
     BitW w;
@@ -118,6 +119,10 @@ __global__ __launch_bounds__(256) void k_bits_scan(FerDev d)
 {
     __shared__ unsigned part[256];
     const int s = blockIdx.x, tid = threadIdx.x;
+    if (d.hdr[s * 4 + 3] == FER_PIC_ABSENT) {  // (uniform over the block) an absent stream's RBSP has length 0
+        if (tid == 0) d.out_bytes[s] = 0;
+        return;
+    }
     uint32_t *sizes = d.mb_bits + (size_t)s * (d.nmb + 1);
     const int n = d.nmb + 1;
     const int per = (n + 255) / 256;
@@ -148,6 +153,7 @@ __global__ __launch_bounds__(256) void k_bits_scan(FerDev d)
 __global__ __launch_bounds__(256) void k_bits_zero(FerDev d)
 {
     const int s = blockIdx.y;
+    if (d.hdr[s * 4 + 3] == FER_PIC_ABSENT) return;
     uint4 *buf = (uint4 *)(d.bits + (size_t)s * d.bits_cap_words);
     const size_t cap16 = d.bits_cap_words / 4;
     const size_t n16 = min(((size_t)d.out_bytes[s] + 15) / 16 + 2, cap16);  // + slack for the flush of the last words

@@ -56,7 +56,7 @@ struct FerRcState {
     int prev_type;           // type (0 = P, 1 = I) of the stream's last picture
     int pending;             // the last picture was coded in 1: ABR, 2: QUALITY, and is not accounted yet
     int gen;                 // FerRcPar::gen this state belongs to
-    int pad;
+    int npic;                // pictures the stream has coded (k_rc_plan counts; k_quality's `picture`)
     long long last_sse[2];   // QUALITY: luma SSE of the last picture of that type
 };
 
@@ -158,7 +158,7 @@ struct FerDev {
     uint32_t *mb_bits;   // [S][nmb+1] bit sizes, then exclusive offsets
     uint32_t *bits;      // [S][bits_cap_words] RBSP, big-endian bit order
     size_t bits_cap_words;
-    uint32_t *hdr;       // [S][4] slice header: bits hi, bits lo, nbits, slice_type(0=P,2=I)
+    uint32_t *hdr;       // [S][4] slice header: bits hi, bits lo, nbits, slice_type(0=P,2=I) or FER_PIC_ABSENT
     uint32_t *out_bytes; // [S] RBSP length
     int *status;         // [S] sticky error flags
     unsigned long long *sad; // [S] frame SAD for the IDR decision
@@ -189,6 +189,10 @@ struct DecBatch {
     const uint8_t *rbsp;  // all slices of the window
     const uint32_t *info; // [TW][S][6]: bytes, first bit of slice_data, slice_type % 5, SliceQPy, byte offset lo, hi
 };
+
+// hdr[s][3] of a stream that has no picture in this call (FERHIP_NAL_NONE): every kernel that tests for 0 (P) or 2 (I)
+// skips it as written; k_rc_plan, k_cavlc, k_bits_scan, k_bits_zero and k_quality test for it
+#define FER_PIC_ABSENT 3
 
 // bits 0 and 1 (stage-2 list overflow, zero-sum blocks) are no longer raised: both cases are handled exactly
 #define FER_ERR_BITS_OVERFLOW 4

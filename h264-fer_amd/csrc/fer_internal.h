@@ -21,7 +21,8 @@ void fer_launch_sort_keys(const FerDev &d, FerSortTmp &t, hipStream_t st);
 void fer_launch_sort_radix(const FerDev &d, FerSortTmp &t, hipStream_t st);
 void fer_launch_sort_finish(const FerDev &d, FerSortTmp &t, hipStream_t st);
 void fer_launch_me_walk(const FerDev &d, hipStream_t st);
-void fer_launch_frame_sad(const FerDev &d, hipStream_t st);
+// skip: device [S], non-zero = the stream takes no part (null = every stream does)
+void fer_launch_frame_sad(const FerDev &d, const uint8_t *skip, hipStream_t st);
 void fer_launch_me_pre(const FerDev &d, hipStream_t st);
 void fer_launch_me_spec(const FerDev &d, hipStream_t st);
 void fer_launch_me_resolve(const FerDev &d, hipStream_t st);
@@ -31,7 +32,9 @@ void fer_launch_intra(const FerDev &d, hipStream_t st);
 void fer_launch_cavlc(const FerDev &d, hipStream_t st);
 void fer_launch_rc_plan(const FerDev &d, hipStream_t st);
 int fer_quality_groups(const FerDev &d);
-void fer_launch_quality(const FerDev &d, int flags, int slot, int picture, hipStream_t st);
+void fer_launch_quality(const FerDev &d, int flags, int slot, hipStream_t st);
+void fer_launch_carry_ref(const FerDev &d, hipStream_t st);
+void fer_launch_reset_stream(const FerDev &d, int s, int qpw, hipStream_t st);
 void fer_launch_block_kat(int qP, const int32_t *in, int32_t *out, int keep_dc, int inverse, size_t n, hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);

@@ -23,9 +23,25 @@
 
 __device__ __forceinline__ unsigned dot4(unsigned a, unsigned b, unsigned c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 
-__global__ __launch_bounds__(64 * Q_WAVES) void k_quality(FerDev d, int flags, int slot, int picture)
+__global__ __launch_bounds__(64 * Q_WAVES) void k_quality(FerDev d, int flags, int slot)
 {
     const int s = blockIdx.y;
+    if (d.hdr[s * 4 + 3] == FER_PIC_ABSENT) {
+        // no picture of this stream in this call (uniform over the workgroup): the row's record says so, q_lsse[s] keeps
+        // the SSE of the stream's last picture for k_rc_plan
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            ferhip_quality r;
+            r.sse[0] = r.sse[1] = r.sse[2] = 0;
+            r.ssim_sum = 0.0;
+            r.ssim_windows = 0;
+            r.qp = d.qp[s] & 0xff;
+            r.nal_type = 0;
+            r.rbsp_bytes = 0;
+            r.picture = (uint32_t)d.rc[s].npic;  // pictures the stream has coded so far
+            d.qring[(size_t)slot * d.S + s] = r;
+        }
+        return;
+    }
     const int G = gridDim.x;
     const int g = (int)xcd_swizzle(blockIdx.x, gridDim.x);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -158,7 +174,7 @@ __global__ __launch_bounds__(64 * Q_WAVES) void k_quality(FerDev d, int flags, i
     r.qp = d.qp[s] & 0xff;
     r.nal_type = d.hdr[s * 4 + 3] == 2 ? FERHIP_NAL_IDR : FERHIP_NAL_SLICE;
     r.rbsp_bytes = d.out_bytes[s];
-    r.picture = (uint32_t)picture;
+    r.picture = (uint32_t)(d.rc[s].npic - 1);  // k_rc_plan has counted this picture
     d.qring[(size_t)slot * d.S + s] = r;
     d.q_lsse[s] = t.sse[0];
 }
@@ -171,7 +187,7 @@ int fer_quality_groups(const FerDev &d)
     return 8 * per;
 }
 
-void fer_launch_quality(const FerDev &d, int flags, int slot, int picture, hipStream_t st)
+void fer_launch_quality(const FerDev &d, int flags, int slot, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_quality, dim3(d.qgroups, d.S), dim3(64 * Q_WAVES), 0, st, d, flags, slot, picture);
+    hipLaunchKernelGGL(k_quality, dim3(d.qgroups, d.S), dim3(64 * Q_WAVES), 0, st, d, flags, slot);
 }

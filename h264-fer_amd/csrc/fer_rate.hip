@@ -41,7 +41,8 @@ __global__ __launch_bounds__(64) void k_rc_plan(FerDev d)
     if (s >= d.S) return;
     const FerRcPar p = d.rc_par[s];
     FerRcState r = d.rc[s];
-    const int y = d.hdr[s * 4 + 3] == 2 ? 1 : 0;  // 0 = P, 1 = I
+    const unsigned ptype = d.hdr[s * 4 + 3];
+    const int y = ptype == 2 ? 1 : 0;  // 0 = P, 1 = I
     if (p.mode != FERHIP_RC_CQP && r.gen != p.gen) {  // entering ABR or QUALITY
         r.err = 0;
         r.have[0] = r.have[1] = 0;
@@ -61,6 +62,15 @@ __global__ __launch_bounds__(64) void k_rc_plan(FerDev d)
         r.last_sse[yp] = (long long)d.q_lsse[s];
         r.last_qp[yp] = last_qp;
         r.have[yp] = 1;
+    }
+    if (ptype == FER_PIC_ABSENT) {
+        // the stream has no picture in this call: its last picture is accounted above, once (out_bytes[s] and q_lsse[s]
+        // belong to that picture only until the next call), no QP is chosen, qp[s] stays the QP of its last picture and
+        // nothing is appended to the header.  Its RBSP of this call has length 0.
+        r.pending = 0;
+        d.rc[s] = r;
+        d.out_bytes[s] = 0;
+        return;
     }
     // (b) this picture's QP
     int q = p.qp;
@@ -103,6 +113,7 @@ __global__ __launch_bounds__(64) void k_rc_plan(FerDev d)
     }
     r.pending = p.mode == FERHIP_RC_ABR ? 1 : (p.mode == FERHIP_RC_QUALITY ? 2 : 0);
     r.prev_type = y;
+    r.npic++;
     d.rc[s] = r;
     d.qp[s] = q | (int)c_qpc_tab[q] << 8;
     // (c) slice_qp_delta = QP - pic_init_qp closes the slice header (shd_write, F/headers_and_parameter_sets.cpp:232)

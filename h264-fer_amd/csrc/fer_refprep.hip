@@ -994,9 +994,10 @@ void fer_launch_refprep(const FerDev &d, FerSortTmp &t, const int *types, hipStr
 // ------------------------------------------------------------------ k_frame_sad
 // selectNALUnitType's whole-picture SAD (F/ref_frames.cpp:185-234): a pure stream of 2 bytes per luma sample, read as
 // 16-byte words, four of them in flight per lane
-__global__ __launch_bounds__(256) void k_frame_sad(FerDev d)
+__global__ __launch_bounds__(256) void k_frame_sad(FerDev d, const uint8_t *skip)
 {
     const int s = blockIdx.y;
+    if (skip && skip[s]) return;  // no picture in this call, or its type is decided already: sad[s] stays 0
     const uint4 *a = (const uint4 *)(d.curY + (size_t)s * d.ysz), *b = (const uint4 *)(d.refY + (size_t)s * d.ysz);
     const size_t n16 = d.ysz / 16, stride = (size_t)gridDim.x * blockDim.x;  // the luma plane is a multiple of 256 bytes
     unsigned acc0 = 0, acc1 = 0;
@@ -1023,9 +1024,9 @@ __global__ __launch_bounds__(256) void k_frame_sad(FerDev d)
     if ((threadIdx.x & 63) == 0) atomicAdd(&d.sad[s], (unsigned long long)(unsigned)v);
 }
 
-void fer_launch_frame_sad(const FerDev &d, hipStream_t st)
+void fer_launch_frame_sad(const FerDev &d, const uint8_t *skip, hipStream_t st)
 {
     hipMemsetAsync(d.sad, 0, sizeof(unsigned long long) * d.S, st);
     const int gx = (int)std::min<size_t>(64, std::max<size_t>(1, d.ysz / 16 / (256 * 8)));  // ~8 words of 16 bytes per lane
-    hipLaunchKernelGGL(k_frame_sad, dim3(gx, d.S), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(k_frame_sad, dim3(gx, d.S), dim3(256), 0, st, d, skip);
 }

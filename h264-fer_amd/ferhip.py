@@ -7,6 +7,7 @@ from pathlib import Path
 import numpy as np
 
 NAL_SLICE, NAL_IDR, NAL_AUTO = 1, 5, 0
+NAL_NONE = -1  # live contexts: the stream has no picture in this call
 
 BUF = dict(INTERP=1, FEAT=2, SORTPOS=3, KOLIKO=4, MBTYPE=5, MV=6, MVD=7, LEVELS=8, CBP=9, TC=10, I4MODE=11,
            CUR=12, REF=13, TIMING=14, ST2N=15, ST2=16, SPEC_STAT=17, MBSIZE=18,
@@ -94,6 +95,9 @@ def load_library():
     lib.ferhip_set_reference.argtypes = [vp, vp]
     lib.ferhip_upload_frames.argtypes = [vp, vp]
     lib.ferhip_set_frames_uploaded.argtypes = [vp]
+    lib.ferhip_set_frames_live.argtypes = [vp, vp, i, vp]
+    lib.ferhip_upload_frames_live.argtypes = [vp, vp, vp]
+    lib.ferhip_reset_stream.argtypes = [vp, i]
     lib.ferhip_encode_picture.argtypes = [vp, C.POINTER(i), vp, sz, C.POINTER(C.c_uint32)]
     lib.ferhip_encode_picture_dev.argtypes = [vp, C.POINTER(i), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
     lib.ferhip_select_nal_type.argtypes = [vp, C.POINTER(i)]
@@ -226,12 +230,56 @@ class FerHip:
     def set_frames_uploaded(self):
         _chk(self.lib.ferhip_set_frames_uploaded(self.ctx), "ferhip_set_frames_uploaded")
 
+    # --- live contexts: streams that sit out a picture, slots that change feeds
+    def _mask(self, present):
+        m = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8).reshape(-1)
+        if m.size != self.S:
+            raise ValueError(f"present has {m.size} entries, the context {self.S} streams")
+        return m
+
+    def set_frames_live(self, frames, present):
+        """ferhip_set_frames_live: the pictures of the streams with present[s] != 0; the other slots are never read.
+        frames: an [S][fsz] uint8 array (host), or an integer = a device pointer to that layout."""
+        m = self._mask(present)
+        if isinstance(frames, (int, np.integer)):
+            rc = self.lib.ferhip_set_frames_live(self.ctx, C.c_void_p(int(frames)), 0, m.ctypes.data)
+        else:
+            a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(self.S, self.fsz)
+            rc = self.lib.ferhip_set_frames_live(self.ctx, a.ctypes.data, 1, m.ctypes.data)
+        _chk(rc, "ferhip_set_frames_live")
+
+    def upload_frames_live(self, host_ptr, present):
+        """upload_frames for the present streams only (pinned host memory, [S][fsz]); set_frames_uploaded() follows"""
+        m = self._mask(present)
+        _chk(self.lib.ferhip_upload_frames_live(self.ctx, C.c_void_p(int(host_ptr)), m.ctypes.data), "ferhip_upload_frames_live")
+
+    def reset_stream(self, s):
+        """ferhip_reset_stream: slot s as in a freshly created context (a new feed takes the slot)"""
+        _chk(self.lib.ferhip_reset_stream(self.ctx, int(s)), "ferhip_reset_stream")
+
+    def encode_live(self, pictures, nal_types=None):
+        """One call of a live context.  pictures: length-S list, pictures[s] = the I420 picture of stream s (fsz bytes) or
+        None when stream s has none now.  -> (list of rbsp bytes, b"" for absent streams; nal types, NAL_NONE for them).
+        nal_types (optional) requests NAL_IDR / NAL_SLICE / NAL_AUTO for the present streams."""
+        if len(pictures) != self.S:
+            raise ValueError(f"{len(pictures)} pictures for {self.S} streams")
+        present = np.array([p is not None for p in pictures], np.uint8)
+        buf = np.empty((self.S, self.fsz), np.uint8)
+        for s, p in enumerate(pictures):
+            if p is not None:
+                buf[s] = np.asarray(p, np.uint8).reshape(self.fsz)
+        if present.any():
+            self.set_frames_live(buf, present)
+        nt = [NAL_NONE if not present[s] else (NAL_AUTO if nal_types is None else nal_types[s]) for s in range(self.S)]
+        return self.encode_picture(nt)
+
     def set_reference(self, frames):
         a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(self.S, self.fsz)
         _chk(self.lib.ferhip_set_reference(self.ctx, a.ctypes.data), "ferhip_set_reference")
 
     def encode_picture(self, nal_types=None):
-        """RBSP_encode for one picture of every stream -> (list of rbsp bytes, nal types)."""
+        """RBSP_encode for one picture of every stream -> (list of rbsp bytes, nal types).  A stream whose entry of
+        nal_types is NAL_NONE has no picture in this call: b"" and NAL_NONE come back for it."""
         nt = (C.c_int * self.S)(*([NAL_AUTO] * self.S if nal_types is None else nal_types))
         stride = self.nmb * 1024 + 4096
         buf = np.empty((self.S, stride), np.uint8)

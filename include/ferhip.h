@@ -34,6 +34,7 @@ extern "C" {
 #define FERHIP_NAL_SLICE 1 /* NAL_UNIT_TYPE_NOT_IDR, F/h264_globals.h:84 */
 #define FERHIP_NAL_IDR 5   /* NAL_UNIT_TYPE_IDR */
 #define FERHIP_NAL_AUTO 0  /* decide like selectNALUnitType() */
+#define FERHIP_NAL_NONE -1 /* live contexts: the stream has no picture in this call (see "live encoder" below) */
 
 typedef struct ferhip_ctx ferhip_ctx;
 
@@ -73,8 +74,34 @@ int ferhip_set_frames(ferhip_ctx *c, const void *src, int host);
 int ferhip_upload_frames(ferhip_ctx *c, const void *pinned_src);
 int ferhip_set_frames_uploaded(ferhip_ctx *c);
 
+/* ---- live encoder: streams that sit out a picture, and slots that change feeds ----
+ * The S streams of a context need not tick together.  nal_type[s] = FERHIP_NAL_NONE in ferhip_encode_picture,
+ * ferhip_encode_picture_dev or (on input) ferhip_select_nal_type means "stream s has no picture in this call": nothing of
+ * that stream is coded or written, nal_type[s] stays FERHIP_NAL_NONE, rbsp_len[s] and the device length are 0, and the
+ * stream keeps its reference picture (ferhip_get_recon: its last reconstruction), macroblock types and vectors, frame_num,
+ * POC, idr_pic_id, its count of coded pictures (IntraEvery counts a stream's own pictures), brojTipova and the QP of its last
+ * picture.  Rate control accounts a stream's previous picture at the first call after it, present or not, exactly once,
+ * and chooses no QP for an absent stream.  So a stream's output is a function of the pictures it was given alone: it equals
+ * the encode of exactly those pictures, whatever calls it sat out and whatever the other streams did.  A call in which
+ * every stream is FERHIP_NAL_NONE returns 0 and changes nothing (no quality row either).  The AUTO decision's SAD
+ * read-back is still the only host synchronisation per picture; absent streams take no part in it.
+ *
+ * ferhip_set_frames_live: ferhip_set_frames for the streams with present[s] != 0 only.  The slots of the other streams in
+ * src ([nstreams][W*H*3/2]) are never read -- a host buffer with holes, or the unwritten slots of ferhip_decs_decode's
+ * device output -- and none of their bytes cross the bus.
+ * ferhip_upload_frames_live: the same for the double-buffered pinned ingest; the mask stays with the staging slot until
+ * ferhip_set_frames_uploaded makes that upload current.
+ * ferhip_reset_stream: slot s becomes what it is in a freshly created context (a new feed takes the slot): no reference
+ * picture, frame_num / POC / idr_pic_id / picture count cleared -- so ferhip_set_rate may set base[s] again --, macroblock
+ * types zeroed, rate settings back to CQP at params.qp with base = params.qp, controller state, brojTipova, sticky
+ * status bits and the quality `picture` index cleared.  The other slots are untouched.  Ordered on the context's stream
+ * behind the slot's last picture; nothing waits.  FERHIP_E_ARG for s outside 0..S-1. */
+int ferhip_set_frames_live(ferhip_ctx *c, const void *src, int host, const uint8_t *present);
+int ferhip_upload_frames_live(ferhip_ctx *c, const void *pinned_src, const uint8_t *present);
+int ferhip_reset_stream(ferhip_ctx *c, int s);
+
 /* ---- RBSP_encode for slice NAL units (F/rbsp_encoding.cpp:139-323) ----
- * nal_type[s]: FERHIP_NAL_IDR / FERHIP_NAL_SLICE / FERHIP_NAL_AUTO per stream on input, the
+ * nal_type[s]: FERHIP_NAL_IDR / FERHIP_NAL_SLICE / FERHIP_NAL_AUTO / FERHIP_NAL_NONE per stream on input, the
  * type actually used on output (NULL = AUTO for all).  After the call the picture buffers
  * hold the reconstruction (like the reference's `frame`) and become the reference picture.
  * rbsp (host): nstreams * rbsp_stride bytes; rbsp_len[s] receives NumBytesInRBSP. */
@@ -82,7 +109,8 @@ int ferhip_encode_picture(ferhip_ctx *c, int *nal_type, uint8_t *rbsp, size_t rb
 
 /* selectNALUnitType() (F/ref_frames.cpp:185-234) for the pictures set by ferhip_set_frames: IDR for the
  * first picture, every IntraEvery-th picture and when the luma SAD against the reference picture
- * exceeds 16 per pixel (evaluated on the device); writes FERHIP_NAL_IDR / FERHIP_NAL_SLICE per stream. */
+ * exceeds 16 per pixel (evaluated on the device); writes FERHIP_NAL_IDR / FERHIP_NAL_SLICE per stream.  A stream whose
+ * entry holds FERHIP_NAL_NONE on input has no picture: it is left out and keeps FERHIP_NAL_NONE. */
 int ferhip_select_nal_type(ferhip_ctx *c, int *nal_type_out);
 
 /* Same, but leaves the RBSP in device memory (no D2H): *d_rbsp receives the device base,
@@ -189,9 +217,11 @@ typedef struct ferhip_quality {
     uint64_t sse[3];       /* Y, Cb, Cr over the coded picture (measured whenever the picture is) */
     double ssim_sum;       /* sum of the per-window SSIM values above; 0 without FERHIP_QM_SSIM */
     uint32_t ssim_windows; /* 0 without FERHIP_QM_SSIM */
-    int32_t qp, nal_type;  /* the picture's QP and FERHIP_NAL_IDR / FERHIP_NAL_SLICE */
+    int32_t qp, nal_type;  /* the picture's QP and FERHIP_NAL_IDR / FERHIP_NAL_SLICE; nal_type 0 = the stream had no picture
+                              in this call (FERHIP_NAL_NONE): sse, ssim_*, rbsp_bytes are 0, qp is its last picture's */
     uint32_t rbsp_bytes;
-    uint32_t picture;      /* index of the picture in its stream (0 = first picture encoded) */
+    uint32_t picture;      /* index of the picture in its own stream (0 = first picture encoded); for a stream without a
+                              picture in this call: the number of pictures it has coded so far */
 } ferhip_quality;
 /* flags: 0 (default) = off, else FERHIP_QM_SSE | FERHIP_QM_SSIM; applies from the next picture.  FERHIP_E_ARG for other
  * bits, FERHIP_E_HIP when the buffers cannot be allocated. */
