@@ -70,6 +70,19 @@ struct ferhip_ctx {
     hipEvent_t pres_ev[FER_HDR_SLOTS];
     int pres_slot;
     std::vector<uint8_t> up_mask[2];  // ferhip_upload_frames_live: the mask of each staging slot (empty = every stream)
+    // NAL framing on the device (ferhip_pack_nal, ferhip_fetch_nal): everything is allocated on first use, the parameter
+    // set table and its pinned ring (like the header ring) only once FERHIP_AU_PARAM_SETS was asked for
+    bool nal_ready;                    // a picture call has been made: hdr and out_bytes describe a picture
+    int nal_nchmax;
+    uint4 *nal_summ;
+    uint2 *nal_cin, *nal_ent;
+    ferhip_au *nal_index, *h_nal_index;  // device / pinned [S + 1]: ferhip_fetch_nal's index
+    uint8_t *nal_buf;                  // ferhip_fetch_nal's device buffer, grown when a picture needs more
+    size_t nal_buf_cap;
+    uint8_t *d_ps, *h_ps_ring;         // device [S][FER_NAL_PS_ROW]; pinned [FER_HDR_SLOTS][S][FER_NAL_PS_ROW]
+    hipEvent_t ps_ev[FER_HDR_SLOTS];
+    int ps_slot;
+    std::vector<uint8_t> ps_dirty;     // [S] the stream's row must be sent (empty until the table exists)
     // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof;
     struct Span { int phase; hipEvent_t a, b; long launches; };
@@ -192,6 +205,15 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     for (int i = 0; i < FER_HDR_SLOTS; i++) c->hdr_ev[i] = c->pres_ev[i] = nullptr;
     c->d_present = c->d_sadskip = c->h_pres_ring = c->h_sadskip = nullptr;
     c->pres_slot = 0;
+    c->nal_ready = false;
+    c->nal_nchmax = 0;
+    c->nal_summ = nullptr;
+    c->nal_cin = c->nal_ent = nullptr;
+    c->nal_index = c->h_nal_index = nullptr;
+    c->nal_buf = c->d_ps = c->h_ps_ring = nullptr;
+    c->nal_buf_cap = 0;
+    for (int i = 0; i < FER_HDR_SLOTS; i++) c->ps_ev[i] = nullptr;
+    c->ps_slot = 0;
     c->planes[0] = c->planes[1] = nullptr;
     c->st_copy = nullptr;
     c->stage[0] = c->stage[1] = nullptr;
@@ -373,6 +395,11 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
         if (c->pres_ev[i]) hipEventDestroy(c->pres_ev[i]);
     }
     if (c->h_pres_ring) hipHostFree(c->h_pres_ring);
+    if (c->h_nal_index) hipHostFree(c->h_nal_index);
+    if (c->h_ps_ring) hipHostFree(c->h_ps_ring);
+    if (c->nal_buf) hipFree(c->nal_buf);
+    for (int i = 0; i < FER_HDR_SLOTS; i++)
+        if (c->ps_ev[i]) hipEventDestroy(c->ps_ev[i]);
     if (c->h_sadskip) hipHostFree(c->h_sadskip);
     if (c->h_len) hipHostFree(c->h_len);
     if (c->h_status) hipHostFree(c->h_status);
@@ -905,6 +932,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
         anyNone |= c->types[s] == FER_PIC_ABSENT;
     }
     if (hdr_upload(c)) return FERHIP_E_HIP;
+    c->nal_ready = true;
     fer_launch_rc_plan(d, c->st);  // each stream's QP and slice_qp_delta, before anything reads qp[] or hdr[] (fer_rate.hip)
     if (!anyP && !anyI) {
         // every stream sat the call out: k_rc_plan has accounted what was pending and set every RBSP length to 0; no
@@ -1047,6 +1075,215 @@ extern "C" int ferhip_copy_rbsp(ferhip_ctx *c, void *dst, size_t dst_stride, siz
     return 0;
 }
 
+// ---- NAL framing on the device (fer_nalpack.hip)
+static int nal_alloc(ferhip_ctx *c)
+{
+    if (c->nal_nchmax) return 0;
+    FerDev &d = c->d;
+    const int nchmax = (int)((d.bits_cap_words * 4 + 4095) / 4096);
+    // every member is set as soon as it exists, so a call after a failed one allocates only what is still missing
+    // (device buffers belong to c->allocs, the pinned index is freed by ferhip_destroy)
+    if ((!c->nal_summ && dalloc(c, &c->nal_summ, (size_t)d.S * nchmax)) || (!c->nal_cin && dalloc(c, &c->nal_cin, (size_t)d.S * nchmax)) ||
+        (!c->nal_ent && dalloc(c, &c->nal_ent, (size_t)d.S)) || (!c->nal_index && dalloc(c, &c->nal_index, (size_t)d.S + 1)) ||
+        (!c->h_nal_index && hipHostMalloc((void **)&c->h_nal_index, sizeof(ferhip_au) * (d.S + 1)) != hipSuccess) ||
+        hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
+        (void)hipGetLastError();
+        fprintf(stderr, "ferhip: could not allocate the NAL framing buffers\n");
+        return FERHIP_E_HIP;
+    }
+    c->nal_nchmax = nchmax;
+    return 0;
+}
+
+// FERHIP_AU_PARAM_SETS: the framed SPS + PPS of every stream in the device table.  Rows that can have changed are built
+// into the next slot of a pinned ring and sent from there on the context's stream (a pinned source is read when the copy
+// executes, so a slot is rewritten only after the copy that last used it has run).
+static int ps_refresh(ferhip_ctx *c)
+{
+    const int S = c->d.S;
+    if (c->ps_dirty.empty()) {
+        // as in nal_alloc: what exists is kept in the context, a call after a failed one creates only the rest
+        if ((!c->d_ps && (dalloc(c, &c->d_ps, (size_t)S * FER_NAL_PS_ROW) || hipDeviceSynchronize() != hipSuccess)) ||
+            (!c->h_ps_ring && hipHostMalloc((void **)&c->h_ps_ring, (size_t)S * FER_NAL_PS_ROW * FER_HDR_SLOTS) != hipSuccess)) {
+            (void)hipGetLastError();
+            return FERHIP_E_HIP;
+        }
+        for (int i = 0; i < FER_HDR_SLOTS; i++)
+            if (!c->ps_ev[i]) CK(hipEventCreateWithFlags(&c->ps_ev[i], hipEventDisableTiming));
+        c->ps_dirty.assign(S, 1);
+    }
+    bool any = false;
+    for (int s = 0; s < S; s++) any |= c->ps_dirty[s] != 0;
+    if (!any) return 0;
+    c->ps_slot = (c->ps_slot + 1) % FER_HDR_SLOTS;
+    CK(hipEventSynchronize(c->ps_ev[c->ps_slot]));
+    uint8_t *slot = c->h_ps_ring + (size_t)c->ps_slot * S * FER_NAL_PS_ROW;
+    for (int s = 0; s < S; s++) {
+        if (!c->ps_dirty[s]) continue;
+        uint8_t rbsp[64], nal[2 * (5 + 96)];
+        size_t n = ferhip_write_sps(c, rbsp, sizeof rbsp);
+        size_t m = ferhip_write_nal(1, 7, rbsp, n, nal);
+        n = ferhip_write_pps_stream(c, s, rbsp, sizeof rbsp);
+        m += ferhip_write_nal(1, 8, rbsp, n, nal + m);
+        if (m > FER_NAL_PS_ROW - 1) return FERHIP_E_UNSUP;
+        uint8_t *row = slot + (size_t)s * FER_NAL_PS_ROW;
+        memset(row, 0, FER_NAL_PS_ROW);
+        memcpy(row, nal, m);
+        row[FER_NAL_PS_ROW - 1] = (uint8_t)m;
+    }
+    for (int s = 0; s < S;) {  // one copy per run of rows
+        if (!c->ps_dirty[s]) {
+            s++;
+            continue;
+        }
+        int e = s;
+        while (e < S && c->ps_dirty[e]) c->ps_dirty[e++] = 0;
+        CK(hipMemcpyAsync(c->d_ps + (size_t)s * FER_NAL_PS_ROW, slot + (size_t)s * FER_NAL_PS_ROW, (size_t)(e - s) * FER_NAL_PS_ROW,
+                          hipMemcpyHostToDevice, c->st));
+        s = e;
+    }
+    CK(hipEventRecord(c->ps_ev[c->ps_slot], c->st));
+    return 0;
+}
+
+static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
+{
+    if (!c->nal_ready) return FERHIP_E_STATE;
+    (void)hipSetDevice(c->device);
+    if (nal_alloc(c)) return FERHIP_E_HIP;
+    if (flags & FERHIP_AU_PARAM_SETS) {
+        int rc = ps_refresh(c);
+        if (rc) return rc;
+    }
+    FerDev &d = c->d;
+    j.src = (const uint8_t *)d.bits;
+    j.src_stride = d.bits_cap_words * 4;
+    j.lens = d.out_bytes;
+    j.hdr = d.hdr;
+    j.types = nullptr;
+    j.ps = (flags & FERHIP_AU_PARAM_SETS) ? c->d_ps : nullptr;
+    j.n = d.S;
+    j.nchmax = c->nal_nchmax;
+    j.summ = c->nal_summ;
+    j.cin = c->nal_cin;
+    j.ent = c->nal_ent;
+    j.index = c->nal_index;
+    j.dst = nullptr;
+    j.cap = 0;
+    return 0;
+}
+
+extern "C" int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap, ferhip_au *d_index)
+{
+    if (!c || !d_index || (flags & ~FERHIP_AU_PARAM_SETS) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_index & 7) || (!d_dst && cap))
+        return FERHIP_E_ARG;
+    FerNalJob j;
+    int rc = nal_prepare(c, flags, j);
+    if (rc) return rc;
+    j.index = d_index;
+    j.dst = (uint8_t *)d_dst;
+    j.cap = cap;
+    fer_launch_nal_plan(j, c->st);
+    fer_launch_nal_emit(j, c->st);
+    CK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_au *h_index)
+{
+    if (!c || !h_index || (flags & ~FERHIP_AU_PARAM_SETS) || (!h_dst && cap)) return FERHIP_E_ARG;
+    FerNalJob j;
+    int rc = nal_prepare(c, flags, j);
+    if (rc) return rc;
+    const int S = c->d.S;
+    j.cap = cap;
+    fer_launch_nal_plan(j, c->st);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(c->h_nal_index, c->nal_index, sizeof(ferhip_au) * (S + 1), hipMemcpyDeviceToHost, c->st));
+    CK(hipStreamSynchronize(c->st));
+    memcpy(h_index, c->h_nal_index, sizeof(ferhip_au) * (S + 1));
+    const size_t total = (size_t)c->h_nal_index[S].offset;
+    if (total > cap) return FERHIP_E_ARG;
+    if (total == 0) return 0;
+    if (c->nal_buf_cap < total) {
+        if (c->nal_buf) CK(hipFree(c->nal_buf));
+        c->nal_buf = nullptr;
+        c->nal_buf_cap = 0;
+        const size_t want = (total + total / 4 + 65535) & ~(size_t)65535;
+        CK(hipMalloc((void **)&c->nal_buf, want));
+        CK(hipMemsetAsync(c->nal_buf, 0, want, c->st));  // the bytes between entries are copied out too
+        c->nal_buf_cap = want;
+    }
+    j.dst = c->nal_buf;
+    j.cap = total;
+    fer_launch_nal_emit(j, c->st);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(h_dst, c->nal_buf, total, hipMemcpyDeviceToHost, c->st));
+    CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// known-answer surface: host payloads through the same kernels, on the null stream with buffers of its own
+extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
+                                       size_t n, uint8_t *out, size_t cap, ferhip_au *index)
+{
+    if (!lens || !nal_type || !index || n == 0 || n > 65535 || (!out && cap)) return FERHIP_E_ARG;
+    uint32_t maxlen = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (lens[i] > stride || (lens[i] && !payloads)) return FERHIP_E_ARG;
+        maxlen = std::max(maxlen, lens[i]);
+    }
+    const size_t pitch = std::max<size_t>(((size_t)maxlen + 15) & ~(size_t)15, 16);
+    const int nchmax = (int)std::max<size_t>(((size_t)maxlen + 4095) / 4096, 1);
+    uint8_t *src = nullptr, *dst = nullptr;
+    uint32_t *dl = nullptr;
+    int32_t *dt = nullptr;
+    uint4 *summ = nullptr;
+    uint2 *cin = nullptr, *ent = nullptr;
+    ferhip_au *idx = nullptr;
+    auto body = [&]() -> int {
+        CK(hipMalloc((void **)&src, pitch * n));
+        CK(hipMalloc((void **)&dst, std::max<size_t>(cap, 16)));
+        CK(hipMalloc((void **)&dl, sizeof(uint32_t) * n));
+        CK(hipMalloc((void **)&dt, sizeof(int32_t) * n));
+        CK(hipMalloc((void **)&summ, sizeof(uint4) * n * nchmax));
+        CK(hipMalloc((void **)&cin, sizeof(uint2) * n * nchmax));
+        CK(hipMalloc((void **)&ent, sizeof(uint2) * n));
+        CK(hipMalloc((void **)&idx, sizeof(ferhip_au) * (n + 1)));
+        CK(hipMemset(src, 0, pitch * n));
+        if (maxlen) CK(hipMemcpy2D(src, pitch, payloads, stride, maxlen, n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dl, lens, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dt, nal_type, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+        if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
+        FerNalJob j;
+        j.src = src;
+        j.src_stride = pitch;
+        j.lens = dl;
+        j.hdr = nullptr;
+        j.types = dt;
+        j.ps = nullptr;
+        j.n = (int)n;
+        j.nchmax = nchmax;
+        j.summ = summ;
+        j.cin = cin;
+        j.ent = ent;
+        j.index = idx;
+        j.dst = dst;
+        j.cap = cap;
+        fer_launch_nal_plan(j, nullptr);
+        fer_launch_nal_emit(j, nullptr);
+        CK(hipGetLastError());
+        CK(hipDeviceSynchronize());
+        if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(index, idx, sizeof(ferhip_au) * (n + 1), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = body();
+    for (void *p : {(void *)src, (void *)dst, (void *)dl, (void *)dt, (void *)summ, (void *)cin, (void *)ent, (void *)idx})
+        if (p) hipFree(p);
+    return rc;
+}
+
 extern "C" int ferhip_sync(ferhip_ctx *c)
 {
     if (!c) return FERHIP_E_ARG;
@@ -1170,7 +1407,10 @@ extern "C" int ferhip_set_rate(ferhip_ctx *c, int s, const ferhip_rate *r)
             p.target = r->target_bits;
         }
         if (r->mode == FERHIP_RC_QUALITY) p.tsse = r->target_sse;
-        if (c->ss[k].frames_done == 0) p.base = r->qp;
+        if (c->ss[k].frames_done == 0) {
+            p.base = r->qp;
+            if (!c->ps_dirty.empty()) c->ps_dirty[k] = 1;  // its PPS changes
+        }
     }
     c->rate_dirty = true;
     return 0;
@@ -1185,6 +1425,7 @@ extern "C" int ferhip_reset_stream(ferhip_ctx *c, int s)
     c->ss[s] = StreamState{0, 0, 0, 0, 0, 0};
     c->rate[s] = FerRcPar{FERHIP_RC_CQP, c->p.qp, 0, 51, 1, 0, c->p.intra_every, c->p.qp, 0, 0, 0};
     c->rate_dirty = true;
+    if (!c->ps_dirty.empty()) c->ps_dirty[s] = 1;
     c->types[s] = 2;
     fer_launch_reset_stream(c->d, s, c->p.qp | k_qpc[c->p.qp] << 8, c->st);
     CK(hipGetLastError());

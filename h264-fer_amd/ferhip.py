@@ -15,6 +15,7 @@ BUF = dict(INTERP=1, FEAT=2, SORTPOS=3, KOLIKO=4, MBTYPE=5, MV=6, MVD=7, LEVELS=
 TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT = 1, 2, 3, 4
 RC_CQP, RC_ABR, RC_QUALITY = 0, 1, 2
 QM_SSE, QM_SSIM, QUALITY_RING = 1, 2, 64
+AU_PARAM_SETS = 1  # pack_nal / fetch_nal: SPS and the stream's own PPS in front of every IDR slice
 _BUF_DTYPE = {1: np.uint8, 2: np.uint16, 3: np.uint32, 4: np.int32, 5: np.int32, 6: np.int16, 7: np.int16,
               8: np.int16, 9: np.uint8, 10: np.uint8, 11: np.uint8, 12: np.uint8, 13: np.uint8, 14: np.int64, 15: np.int32, 16: np.int32,
               17: np.uint64, 18: np.int32, 19: np.int32, 20: np.int32, 21: np.int32, 22: np.int32, 23: np.int32, 24: np.int32,
@@ -45,6 +46,10 @@ class QualityRec(C.Structure):
 _QREC = np.dtype([("sse", np.uint64, 3), ("ssim_sum", np.float64), ("ssim_windows", np.uint32), ("qp", np.int32),
                   ("nal_type", np.int32), ("rbsp_bytes", np.uint32), ("picture", np.uint32)], align=True)
 assert _QREC.itemsize == C.sizeof(QualityRec)
+
+# ferhip_au of include/ferhip.h: one entry of the index of ferhip_pack_nal / ferhip_fetch_nal / ferhip_frame_nal_blocks
+AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.int32)])
+assert AU.itemsize == 16
 
 
 class Quality:
@@ -117,6 +122,9 @@ def load_library():
     lib.ferhip_write_nal.argtypes = [i, i, vp, sz, vp]
     lib.ferhip_write_nal.restype = sz
     lib.ferhip_encode_streams.argtypes = [vp, vp, i, vp, sz, C.POINTER(sz), vp]
+    lib.ferhip_pack_nal.argtypes = [vp, i, vp, sz, vp]
+    lib.ferhip_fetch_nal.argtypes = [vp, i, vp, sz, vp]
+    lib.ferhip_frame_nal_blocks.argtypes = [vp, sz, vp, vp, sz, vp, sz, vp]
     lib.ferhip_get_stats.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_status.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_fill_interpolated.argtypes = [vp]
@@ -364,6 +372,35 @@ class FerHip:
         m = self.lib.ferhip_write_nal(1, nal_type, r.ctypes.data, len(rbsp), o.ctypes.data)
         return bytes(o[:m])
 
+    # --- NAL framing on the device
+    def pack_nal_device(self, dst_ptr, index_ptr, cap, flags=0):
+        """ferhip_pack_nal: the last picture's Annex-B NAL units -> device memory at dst_ptr (16-byte aligned, cap bytes) and
+        their index (S + 1 records of dtype AU) at index_ptr, on the library's stream (asynchronous; sync() before reading)."""
+        _chk(self.lib.ferhip_pack_nal(self.ctx, int(flags), C.c_void_p(int(dst_ptr) if dst_ptr else None), int(cap),
+                                      C.c_void_p(int(index_ptr))), "ferhip_pack_nal")
+
+    def fetch_nal_raw(self, cap, flags=0):
+        """ferhip_fetch_nal into a new host buffer of cap bytes -> (return code, buffer, index [S + 1] of dtype AU)"""
+        buf = np.empty(max(int(cap), 1), np.uint8)
+        idx = np.zeros(self.S + 1, AU)
+        rc = self.lib.ferhip_fetch_nal(self.ctx, int(flags), buf.ctypes.data, int(cap), idx.ctypes.data)
+        return rc, buf, idx
+
+    def fetch_nal(self, flags=0, cap=None):
+        """The last picture of every stream as Annex-B NAL units (waits) -> (list of bytes per stream, b"" for the streams
+        without a picture; NAL unit types, 0 for them).  With AU_PARAM_SETS an IDR entry is SPS + PPS + slice.
+        cap: size of the host buffer; None = one that grows to what the pictures need."""
+        grow = cap is None
+        if grow:
+            cap = getattr(self, "_nal_cap", 1 << 20)
+        rc, buf, idx = self.fetch_nal_raw(cap, flags)
+        if grow and rc == -1 and int(idx["offset"][self.S]) > cap:  # FERHIP_E_ARG with a true index: the buffer was too small
+            cap = self._nal_cap = 2 * int(idx["offset"][self.S])
+            rc, buf, idx = self.fetch_nal_raw(cap, flags)
+        _chk(rc, "ferhip_fetch_nal")
+        return ([bytes(buf[int(idx["offset"][s]): int(idx["offset"][s]) + int(idx["bytes"][s])]) for s in range(self.S)],
+                [int(t) for t in idx["nal_type"][: self.S]])
+
     # --- rate control
     def set_rate(self, stream=-1, mode=RC_CQP, qp=None, qp_min=0, qp_max=51, max_step=2, ip_offset=3, window=0,
                  target_bits=0, target_sse=0, target_psnr=None):
@@ -514,6 +551,34 @@ def cavlc_blocks(coef, nC, max_num_coeff):
     lib.ferhip_cavlc_blocks.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 3
     _chk(lib.ferhip_cavlc_blocks(c.ctypes.data, nc.ctypes.data, mx.ctypes.data, n, bits.ctypes.data, nb.ctypes.data, tc.ctypes.data), "ferhip_cavlc_blocks")
     return bits, nb, tc
+
+
+def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5):
+    """ferhip_frame_nal_blocks on a list of payloads (bytes or uint8 arrays) -> (return code, out [cap] pre-filled with
+    `fill`, index [n + 1] of dtype AU).  cap None = room for every payload with every second byte escaped."""
+    lib = load_library()
+    n = len(payloads)
+    lens = np.array([len(p) for p in payloads], np.uint32)
+    stride = max(int(lens.max()) if n else 0, 1)
+    src = np.zeros((n, stride), np.uint8)
+    for k, p in enumerate(payloads):
+        src[k, : len(p)] = np.frombuffer(bytes(p), np.uint8) if not isinstance(p, np.ndarray) else p
+    if cap is None:
+        cap = int(sum(((int(m) * 3 // 2 + 6 + 15) & ~15) for m in lens))
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    idx = np.zeros(n + 1, AU)
+    nt = np.ascontiguousarray(nal_types, np.int32)
+    rc = lib.ferhip_frame_nal_blocks(src.ctypes.data, stride, lens.ctypes.data, nt.ctypes.data, n, out.ctypes.data, int(cap),
+                                     idx.ctypes.data)
+    return rc, out, idx
+
+
+def frame_nal_blocks(payloads, nal_types):
+    """Annex-B framing (start code, header byte 1 << 5 | type, emulation prevention) of every payload by the kernels of
+    ferhip_pack_nal -> list of bytes"""
+    rc, out, idx = frame_nal_blocks_raw(payloads, nal_types)
+    _chk(rc, "ferhip_frame_nal_blocks")
+    return [bytes(out[int(e["offset"]): int(e["offset"]) + int(e["bytes"])]) for e in idx[:-1]]
 
 
 def mc_sub_mb_parts(ref_i420, width, height, desc):

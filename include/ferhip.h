@@ -134,6 +134,41 @@ size_t ferhip_write_sps(ferhip_ctx *c, uint8_t *rbsp, size_t cap);
 size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap);  /* pic_init_qp = 14 + params.qp; see ferhip_write_pps_stream */
 size_t ferhip_write_nal(int nal_ref_idc, int nal_type, const uint8_t *rbsp, size_t n, uint8_t *out);
 
+/* ---- NAL framing on the device: the coded pictures as Annex-B NAL units with an offset table ----
+ * For every stream that coded a picture in the context's last ferhip_encode_picture[_dev] call the output holds exactly what
+ * ferhip_write_nal(1, type, rbsp, len, ...) writes: 00 00 00 01, the header byte 1 << 5 | type (5 for an I picture, 1 for a
+ * P picture, taken from the device's own slice headers) and the payload with its emulation prevention bytes.  With
+ * FERHIP_AU_PARAM_SETS the framed SPS and the stream's own PPS (ferhip_write_pps_stream) stand in front of every IDR
+ * unit, and the three form one entry.
+ * Layout: entries in stream order, every offset a multiple of 16; the bytes between an entry's end and the next offset
+ * are not written.  index[s] = (offset, bytes, NAL unit type of the slice); a stream without a picture (FERHIP_NAL_NONE)
+ * has bytes 0 and nal_type 0.  index[S].offset = the total (the end of the last entry rounded up to 16), index[S].bytes =
+ * the number of entries written.
+ * Overflow is not an error: the index always holds the true offsets and sizes, an entry is written only if it ends within
+ * cap together with its rounding to 16 (offset + bytes rounded up to 16 <= cap: an entry owns whole 16-byte slots, so a
+ * buffer one byte short of the total never holds the last entry), and no byte at or beyond cap is touched.  ferhip_pack_nal then still returns 0 -- compare index[S].offset with cap --
+ * and ferhip_fetch_nal fills h_index and returns FERHIP_E_ARG.
+ * Call order as for ferhip_copy_rbsp: behind the last picture, before the next one.  FERHIP_E_STATE before the context's
+ * first picture; after a call in which every stream was absent the total is 0.  Packing changes nothing the encoder reads
+ * (RBSP, lengths, rate and quality state) and may be repeated.  A slot that ferhip_reset_stream cleared has no entry until its
+ * next picture.
+ * ferhip_pack_nal: device to device (d_dst 16-byte aligned, d_index 8-byte aligned, else FERHIP_E_ARG), asynchronous on the
+ * context's stream; nothing waits, except that a context's first call, and its first call with the flag, allocate their
+ * buffers and wait for the device once.  ferhip_fetch_nal: the same bytes in host memory; it waits, reads the index, grows an
+ * internal device buffer when needed and makes exactly one device-to-host copy of `total` bytes.
+ * The parameter sets are built on the host and kept in a small device table that exists only once the flag was used; a
+ * stream's row is sent again only when it can have changed (its first use, ferhip_set_rate before the stream's first
+ * picture, ferhip_reset_stream). */
+#define FERHIP_AU_PARAM_SETS 1
+typedef struct { uint64_t offset; uint32_t bytes; int32_t nal_type; } ferhip_au; /* 16 bytes */
+int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap, ferhip_au *d_index /* [S+1] */);
+int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_au *h_index /* [S+1] */);
+/* Known-answer surface, context-free like ferhip_cavlc_blocks: n host payloads [n][stride] of lens[n] bytes and NAL unit type
+ * nal_type[n], framed by the same kernels (a payload of length 0 gives its five prefix bytes); out (host, cap bytes: bytes
+ * the kernels do not write keep the caller's values) and index[n + 1] as above.  n <= 65535. */
+int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
+                            size_t n, uint8_t *out, size_t cap, ferhip_au *index /* [n+1] */);
+
 /* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134), each stream with its own PPS:
  * frames host [T][S][W*H*3/2]; out host [S][out_stride] Annex-B; out_len[S].
  * recon (optional) host [T][S][W*H*3/2]. */
