@@ -1,115 +1,10 @@
-// fer_api.hip -- the C ABI of libferhip (include/ferhip.h): context, HBM layout, picture
-// driver (the RBSP_encode sequence of F/rbsp_encoding.cpp:139-323 expressed as kernel
-// launches), host-side slice / parameter-set headers (F/headers_and_parameter_sets.cpp) and
-// NAL framing (F/nal.cpp:261-299).  Host code is C-style C++; nothing here runs the hot path
-// on the CPU.
-#include "../../include/ferhip.h"
-#include "fer_internal.h"
-#include <stdio.h>
+// fer_api.hip -- the encoder side of the C ABI of libferhip (include/ferhip.h): the context and its HBM layout, ingest,
+// the picture driver (the RBSP_encode sequence of F/rbsp_encoding.cpp:139-323 expressed as kernel launches), getters and
+// setters.  Headers are in fer_headers.hip, NAL framing in fer_nalpack.hip, the decoder's host side in fer_decode_host.hip.
+// Host code is C-style C++; nothing here runs the hot path on the CPU.
+#include "fer_ctx.h"
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
-#include <utility>
-#include <chrono>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-#define CK(x)                                                                                         \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) {                                                                       \
-            fprintf(stderr, "ferhip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return FERHIP_E_HIP;                                                                      \
-        }                                                                                             \
-    } while (0)
-
-#define FER_HDR_SLOTS 8
-struct StreamState {  // slice-level state of one stream (globals `shd`, statics of RBSP_encode)
-    int frame_num, poc_lsb, idr_pic_id, first_idr_done, frames_done, have_dpb;
-};
-
-struct ferhip_ctx {
-    FerDev d;
-    ferhip_params p;
-    hipStream_t st;
-    hipStream_t st_hi;   // high-priority stream for the latency-bound per-diagonal chains
-    hipStream_t st_aux;  // the sort of the reference picture's positions runs here, beside k_me_pre (run_picture)
-    hipEvent_t ev_a, ev_b, ev_c, ev_d;
-    int overlap_sort;    // ferhip_tune: 1 / 2 = the HBM-bound sort is enqueued beside the VALU-bound stage-3 search (st_aux / st_hi)
-    int device;  // HIP device the context lives on; every entry point re-selects it (callers may use any thread)
-    std::vector<StreamState> ss;
-    std::vector<void *> allocs;
-    FerSortTmp sort;
-    uint32_t *h_hdr;       // pinned [S][4]: the slot of the header ring that the next picture fills
-    uint32_t *h_hdr_ring;  // pinned [FER_HDR_SLOTS][S][4]; a pinned source is read when the copy executes, not when it is
-    hipEvent_t hdr_ev[8];  // enqueued, so a slot is rewritten only after the copy that last used it has run
-    int hdr_slot;
-    std::vector<FerRcPar> rate;  // ferhip_set_rate: the settings of every stream, sent with the next picture's headers
-    bool rate_dirty;
-    FerRcPar *h_rate_ring;       // pinned [FER_HDR_SLOTS][S], the header ring's companion
-    int qflags;                  // ferhip_set_quality
-    long long q_count;           // pictures measured so far: the next record goes to ring slot q_count % FERHIP_QUALITY_RING
-    uint32_t *h_len;       // pinned [S]
-    int *h_status;         // pinned [S]
-    unsigned long long *h_sad;
-    std::vector<int> types;
-    uint8_t *planes[2];    // two picture sets, swapped after every picture
-    // asynchronous ingest (ferhip_upload_frames): pinned host pictures -> stage[k] on a copy stream, double buffered
-    hipStream_t st_copy;
-    uint8_t *stage[2];
-    hipEvent_t up_done[2], up_used[2];
-    int up_next, up_ready;  // slot the next upload fills; uploads waiting to be made current
-    int cur_set;
-    bool refprep_valid;
-    // live contexts: presence masks.  An ingest mask goes to the device through a pinned ring of its own (like the header
-    // ring: a pinned source is read when the copy executes); the mask of k_frame_sad needs one slot only, because the
-    // read-back of the SADs waits for the stream
-    uint8_t *d_present, *d_sadskip;   // device [S]
-    uint8_t *h_pres_ring, *h_sadskip; // pinned [FER_HDR_SLOTS][S], [S]
-    hipEvent_t pres_ev[FER_HDR_SLOTS];
-    int pres_slot;
-    std::vector<uint8_t> up_mask[2];  // ferhip_upload_frames_live: the mask of each staging slot (empty = every stream)
-    // NAL framing on the device (ferhip_pack_nal, ferhip_fetch_nal): everything is allocated on first use, the parameter
-    // set table and its pinned ring (like the header ring) only once FERHIP_AU_PARAM_SETS was asked for
-    bool nal_ready;                    // a picture call has been made: hdr and out_bytes describe a picture
-    int nal_nchmax;
-    uint4 *nal_summ;
-    uint2 *nal_cin, *nal_ent;
-    ferhip_au *nal_index, *h_nal_index;  // device / pinned [S + 1]: ferhip_fetch_nal's index
-    uint8_t *nal_buf;                  // ferhip_fetch_nal's device buffer, grown when a picture needs more
-    size_t nal_buf_cap;
-    uint8_t *d_ps, *h_ps_ring;         // device [S][FER_NAL_PS_ROW]; pinned [FER_HDR_SLOTS][S][FER_NAL_PS_ROW]
-    hipEvent_t ps_ev[FER_HDR_SLOTS];
-    int ps_slot;
-    std::vector<uint8_t> ps_dirty;     // [S] the stream's row must be sent (empty until the table exists)
-    // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
-    bool prof;
-    struct Span { int phase; hipEvent_t a, b; long launches; };
-    std::vector<Span> spans;
-    double prof_ms[FERHIP_NPHASE];
-    long prof_launches[FERHIP_NPHASE];
-};
-
-struct ProfScope {
-    ferhip_ctx *c;
-    int idx;
-    hipStream_t s;
-    ProfScope(ferhip_ctx *c_, int phase, long launches, hipStream_t s_ = nullptr) : c(c_), idx(-1), s(s_ ? s_ : c_->st)
-    {
-        if (!c->prof) return;
-        ferhip_ctx::Span sp{phase, nullptr, nullptr, launches};
-        hipEventCreate(&sp.a);
-        hipEventCreate(&sp.b);
-        hipEventRecord(sp.a, s);
-        c->spans.push_back(sp);
-        idx = (int)c->spans.size() - 1;
-    }
-    ~ProfScope()
-    {
-        if (idx >= 0) hipEventRecord(c->spans[idx].b, s);
-    }
-};
 
 static const int k_qpc[52] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17,
                               18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32, 32, 33,
@@ -118,21 +13,45 @@ static const int k_qpc[52] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12
 // qPiToQPc (F/inttransform.cpp:8-14) for chroma_qp_index_offset 0: what the per-macroblock shims of fer_legacy.hip need
 extern "C" int ferhip_chroma_qp(int qpy) { return k_qpc[qpy < 0 ? 0 : (qpy > 51 ? 51 : qpy)]; }
 
-template <typename T>
-static int dalloc(ferhip_ctx *c, T **p, size_t n)
+int PinnedRing::create(size_t bytes_per_slot, size_t second_bytes)
 {
-    void *v = nullptr;
-    if (hipMalloc(&v, n * sizeof(T) + 256) != hipSuccess) return FERHIP_E_HIP;
-    if (hipMemset(v, 0, n * sizeof(T) + 256) != hipSuccess) return FERHIP_E_HIP;
-    c->allocs.push_back(v);
-    *p = (T *)v;
+    slot_bytes = bytes_per_slot + second_bytes;
+    second_off = bytes_per_slot;
+    if (!mem) CK(hipHostMalloc((void **)&mem, slot_bytes * FER_HDR_SLOTS));
+    for (int i = 0; i < FER_HDR_SLOTS; i++)
+        if (!ev[i]) CK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    return 0;
+}
+void *PinnedRing::next()
+{
+    slot = (slot + 1) % FER_HDR_SLOTS;
+    if (hipEventSynchronize(ev[slot]) != hipSuccess) return nullptr;
+    return mem + (size_t)slot * slot_bytes;
+}
+int PinnedRing::sent(hipStream_t st)
+{
+    CK(hipEventRecord(ev[slot], st));
+    return 0;
+}
+void PinnedRing::destroy()
+{
+    if (mem) hipHostFree(mem);
+    for (hipEvent_t &e : ev)
+        if (e) hipEventDestroy(e);
+    *this = PinnedRing();
+}
+
+int ealloc(ferhip_ctx *c, hipEvent_t *e)
+{
+    if (*e) return 0;
+    CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    c->events.push_back(*e);
     return 0;
 }
 
-static void bind_planes(ferhip_ctx *c)
+void bind_planes(ferhip_ctx *c)
 {
     FerDev &d = c->d;
-    size_t fsz = d.ysz + 2 * d.csz;
     uint8_t *cur = c->planes[c->cur_set], *ref = c->planes[c->cur_set ^ 1];
     d.curY = cur;
     d.curCb = cur + (size_t)d.S * d.ysz;
@@ -140,7 +59,6 @@ static void bind_planes(ferhip_ctx *c)
     d.refY = ref;
     d.refCb = ref + (size_t)d.S * d.ysz;
     d.refCr = ref + (size_t)d.S * (d.ysz + d.csz);
-    (void)fsz;
 }
 
 extern "C" const char *ferhip_version(void) { return "ferhip 0.2 (gfx950)"; }
@@ -173,13 +91,11 @@ extern "C" int ferhip_mem_copy(void *dst, const void *src, size_t bytes)
     return 0;
 }
 
-static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p, bool decode_only);
 extern "C" int ferhip_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p)
 {
     return ctx_create(out, W, H, S, p, false);
 }
-// decode_only: the encoder-side structures (interpolated planes, features, sort, search lists, RBSP) stay empty
-static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p, bool decode_only)
+int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p, bool decode_only)
 {
     if (!out || !p || W <= 0 || H <= 0 || (W & 15) || (H & 15) || S <= 0 || W > 16384 || H > 16384) return FERHIP_E_ARG;
     if (p->qp < 0 || p->qp > 51 || p->window < 16 || p->intra_every <= 0) return FERHIP_E_ARG;
@@ -193,32 +109,6 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
     }
     ferhip_ctx *c = new ferhip_ctx();
     memset(&c->d, 0, sizeof c->d);
-    c->st = c->st_hi = c->st_aux = nullptr;
-    c->ev_a = c->ev_b = c->ev_c = c->ev_d = nullptr;
-    c->overlap_sort = 0;  // measured: kernels of two HIP streams do not share the GPU here (the sort stretches to k_me_pre's length)
-    c->h_hdr = c->h_hdr_ring = c->h_len = nullptr;
-    c->h_rate_ring = nullptr;
-    c->qflags = 0;
-    c->q_count = 0;
-    c->h_status = nullptr;
-    c->h_sad = nullptr;
-    for (int i = 0; i < FER_HDR_SLOTS; i++) c->hdr_ev[i] = c->pres_ev[i] = nullptr;
-    c->d_present = c->d_sadskip = c->h_pres_ring = c->h_sadskip = nullptr;
-    c->pres_slot = 0;
-    c->nal_ready = false;
-    c->nal_nchmax = 0;
-    c->nal_summ = nullptr;
-    c->nal_cin = c->nal_ent = nullptr;
-    c->nal_index = c->h_nal_index = nullptr;
-    c->nal_buf = c->d_ps = c->h_ps_ring = nullptr;
-    c->nal_buf_cap = 0;
-    for (int i = 0; i < FER_HDR_SLOTS; i++) c->ps_ev[i] = nullptr;
-    c->ps_slot = 0;
-    c->planes[0] = c->planes[1] = nullptr;
-    c->st_copy = nullptr;
-    c->stage[0] = c->stage[1] = nullptr;
-    c->up_done[0] = c->up_done[1] = c->up_used[0] = c->up_used[1] = nullptr;
-    c->up_next = c->up_ready = 0;
     c->p = *p;
     FerDev &d = c->d;
     d.W = W;
@@ -247,10 +137,7 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
             hipStreamCreateWithPriority(&c->st, hipStreamNonBlocking, lo) != hipSuccess ||
             hipStreamCreateWithPriority(&c->st_hi, hipStreamNonBlocking, hi) != hipSuccess ||
             hipStreamCreateWithPriority(&c->st_aux, hipStreamNonBlocking, lo) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_c, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_d, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_a, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming) != hipSuccess) {
+            ealloc(c, &c->ev_c) || ealloc(c, &c->ev_d) || ealloc(c, &c->ev_a) || ealloc(c, &c->ev_b)) {
             ferhip_destroy(c);
             return FERHIP_E_HIP;
         }
@@ -333,29 +220,16 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
         ferhip_destroy(c);
         return FERHIP_E_HIP;
     }
-    if (hipHostMalloc((void **)&c->h_hdr_ring, sizeof(uint32_t) * 4 * S * FER_HDR_SLOTS) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_rate_ring, sizeof(FerRcPar) * S * FER_HDR_SLOTS) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_len, sizeof(uint32_t) * S) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_pres_ring, (size_t)S * FER_HDR_SLOTS) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_sadskip, (size_t)S) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_status, sizeof(int) * S) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_sad, sizeof(unsigned long long) * S) != hipSuccess) {
+    if (c->hdr_ring.create(sizeof(uint32_t) * 4 * S, sizeof(FerRcPar) * S) || c->pres_ring.create((size_t)S) ||
+        halloc(c, &c->h_len, (size_t)S) || halloc(c, &c->h_sadskip, (size_t)S) || halloc(c, &c->h_status, (size_t)S) ||
+        halloc(c, &c->h_sad, (size_t)S)) {
         ferhip_destroy(c);
         return FERHIP_E_HIP;
     }
-    for (int i = 0; i < FER_HDR_SLOTS; i++)
-        if (hipEventCreateWithFlags(&c->hdr_ev[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->pres_ev[i], hipEventDisableTiming) != hipSuccess) {
-            ferhip_destroy(c);
-            return FERHIP_E_HIP;
-        }
-    c->hdr_slot = 0;
-    c->h_hdr = c->h_hdr_ring;
     c->ss.assign(S, StreamState{0, 0, 0, 0, 0, 0});
     // every stream starts in constant QP at params.qp, which is also the QP of its PPS; chroma_qp_index_offset == 0
     // (F/headers_and_parameter_sets.cpp:490)
     c->rate.assign(S, FerRcPar{FERHIP_RC_CQP, p->qp, 0, 51, 1, 0, p->intra_every, p->qp, 0, 0, 0});
-    c->rate_dirty = true;
     {
         std::vector<int> q0(S, p->qp | k_qpc[p->qp] << 8);
         if (hipMemcpy(d.qp, q0.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess) {
@@ -364,11 +238,6 @@ static int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params
         }
     }
     c->types.assign(S, 2);
-    c->cur_set = 0;
-    c->refprep_valid = false;
-    c->prof = false;
-    memset(c->prof_ms, 0, sizeof c->prof_ms);
-    memset(c->prof_launches, 0, sizeof c->prof_launches);
     bind_planes(c);
     // the buffers were cleared on the null stream, which the context's non-blocking streams do not wait for: without
     // this the clearing of a large buffer can land after the first picture's kernels have written into it
@@ -387,38 +256,14 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
     if (c->st) hipStreamSynchronize(c->st);
     if (c->st_hi) hipStreamSynchronize(c->st_hi);
     if (c->st_aux) hipStreamSynchronize(c->st_aux);
+    if (c->st_copy) hipStreamSynchronize(c->st_copy);
     for (void *p : c->allocs) hipFree(p);
-    if (c->h_hdr_ring) hipHostFree(c->h_hdr_ring);
-    if (c->h_rate_ring) hipHostFree(c->h_rate_ring);
-    for (int i = 0; i < FER_HDR_SLOTS; i++) {
-        if (c->hdr_ev[i]) hipEventDestroy(c->hdr_ev[i]);
-        if (c->pres_ev[i]) hipEventDestroy(c->pres_ev[i]);
-    }
-    if (c->h_pres_ring) hipHostFree(c->h_pres_ring);
-    if (c->h_nal_index) hipHostFree(c->h_nal_index);
-    if (c->h_ps_ring) hipHostFree(c->h_ps_ring);
     if (c->nal_buf) hipFree(c->nal_buf);
-    for (int i = 0; i < FER_HDR_SLOTS; i++)
-        if (c->ps_ev[i]) hipEventDestroy(c->ps_ev[i]);
-    if (c->h_sadskip) hipHostFree(c->h_sadskip);
-    if (c->h_len) hipHostFree(c->h_len);
-    if (c->h_status) hipHostFree(c->h_status);
-    if (c->h_sad) hipHostFree(c->h_sad);
-    if (c->st_copy) {
-        hipStreamSynchronize(c->st_copy);
-        hipStreamDestroy(c->st_copy);
-    }
-    for (int i = 0; i < 2; i++) {
-        if (c->up_done[i]) hipEventDestroy(c->up_done[i]);
-        if (c->up_used[i]) hipEventDestroy(c->up_used[i]);
-    }
-    if (c->st) hipStreamDestroy(c->st);
-    if (c->st_hi) hipStreamDestroy(c->st_hi);
-    if (c->st_aux) hipStreamDestroy(c->st_aux);
-    if (c->ev_c) hipEventDestroy(c->ev_c);
-    if (c->ev_d) hipEventDestroy(c->ev_d);
-    if (c->ev_a) hipEventDestroy(c->ev_a);
-    if (c->ev_b) hipEventDestroy(c->ev_b);
+    for (void *p : c->pinned) hipHostFree(p);
+    for (hipEvent_t e : c->events) hipEventDestroy(e);
+    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring}) r->destroy();
+    for (hipStream_t st : {c->st, c->st_hi, c->st_aux, c->st_copy})
+        if (st) hipStreamDestroy(st);
     delete c;
 }
 
@@ -457,12 +302,11 @@ static int copy_frames(ferhip_ctx *c, uint8_t *set, const uint8_t *src, uint8_t 
     if (kind == hipMemcpyDeviceToDevice && (((uintptr_t)(src ? src : dst)) & 15) == 0) {
         const uint8_t *d_mask = nullptr;
         if (present) {  // the mask rides a pinned ring to the device, ordered before the repack on the context's stream
-            c->pres_slot = (c->pres_slot + 1) % FER_HDR_SLOTS;
-            CK(hipEventSynchronize(c->pres_ev[c->pres_slot]));
-            uint8_t *h = c->h_pres_ring + (size_t)c->pres_slot * d.S;
+            uint8_t *h = (uint8_t *)c->pres_ring.next();
+            if (!h) return FERHIP_E_HIP;
             for (int s = 0; s < d.S; s++) h[s] = present[s] ? 1 : 0;
             CK(hipMemcpyAsync(c->d_present, h, (size_t)d.S, hipMemcpyHostToDevice, c->st));
-            CK(hipEventRecord(c->pres_ev[c->pres_slot], c->st));
+            if (c->pres_ring.sent(c->st)) return FERHIP_E_HIP;
             d_mask = c->d_present;
         }
         hipLaunchKernelGGL(k_repack, dim3(256, d.S), dim3(256), 0, c->st, set, (uint8_t *)(src ? src : dst), d.ysz, d.csz, d.S,
@@ -536,11 +380,8 @@ static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *p
         hipStream_t stc = nullptr;
         CK(hipStreamCreateWithFlags(&stc, hipStreamNonBlocking));
         bool ok = true;
-        for (int i = 0; i < 2 && ok; i++) {
-            if (!c->stage[i]) ok = dalloc(c, &c->stage[i], bytes) == 0;
-            if (ok && !c->up_done[i]) ok = hipEventCreateWithFlags(&c->up_done[i], hipEventDisableTiming) == hipSuccess;
-            if (ok && !c->up_used[i]) ok = hipEventCreateWithFlags(&c->up_used[i], hipEventDisableTiming) == hipSuccess;
-        }
+        for (int i = 0; i < 2 && ok; i++)
+            ok = !dalloc(c, &c->stage[i], bytes) && !ealloc(c, &c->up_done[i]) && !ealloc(c, &c->up_used[i]);
         if (ok) ok = hipDeviceSynchronize() == hipSuccess;  // dalloc clears on the null stream
         if (!ok) {
             (void)hipGetLastError();
@@ -618,205 +459,24 @@ extern "C" int ferhip_get_recon(ferhip_ctx *c, void *dst, int host)
     return 0;
 }
 
-// ---- host bit writer for headers (MSB first, F/rbsp_IO.cpp:123)
-struct HBits {
-    unsigned long long v;
-    int n;
-    void put(int k, unsigned x)
-    {
-        v = (v << k) | (unsigned long long)x;
-        n += k;
-    }
-    void ue(unsigned x)
-    {
-        int p = 0;
-        while (((x + 1) >> (p + 1)) != 0) p++;
-        put(p, 0);
-        put(1, 1);
-        if (p) put(p, x + 1 - (1u << p));
-    }
-    void se(int x) { ue(x <= 0 ? (unsigned)(-x) * 2u : (unsigned)x * 2u - 1u); }
-};
-
-struct ByteW {
-    uint8_t *b;
-    size_t cap, nbits;
-    void put(int k, unsigned x)
-    {
-        for (int i = k - 1; i >= 0; i--) {
-            size_t by = nbits >> 3;
-            if (by < cap) {
-                if ((nbits & 7) == 0) b[by] = 0;
-                b[by] |= (uint8_t)(((x >> i) & 1u) << (7 - (nbits & 7)));
-            }
-            nbits++;
-        }
-    }
-    void ue(unsigned x)
-    {
-        int p = 0;
-        while (((x + 1) >> (p + 1)) != 0) p++;
-        put(p, 0);
-        put(1, 1);
-        if (p) put(p, x + 1 - (1u << p));
-    }
-    void se(int x) { ue(x <= 0 ? (unsigned)(-x) * 2u : (unsigned)x * 2u - 1u); }
-    size_t trailing()
-    {
-        put(1, 1);
-        while (nbits & 7) put(1, 0);
-        return nbits >> 3;
-    }
-};
-
-// sps_write, F/headers_and_parameter_sets.cpp:305-391
-extern "C" size_t ferhip_write_sps(ferhip_ctx *c, uint8_t *rbsp, size_t cap)
-{
-    ByteW w{rbsp, cap, 0};
-    w.put(8, 66);
-    w.put(1, 1);
-    w.put(1, 1);
-    w.put(1, 0);
-    w.put(5, 0);
-    w.put(8, 41);
-    w.ue(0);
-    w.ue(5);  // log2_max_frame_num 9
-    w.ue(0);
-    w.ue(6);  // log2_max_pic_order_cnt_lsb 10
-    w.ue(1);
-    w.put(1, 0);
-    w.ue((unsigned)(c->d.mbw - 1));
-    w.ue((unsigned)(c->d.mbh - 1));
-    w.put(1, 1);
-    w.put(1, 1);
-    w.put(1, 0);
-    w.put(1, 0);
-    return w.trailing();
-}
-
-// pps_write, F/headers_and_parameter_sets.cpp:478-513 (weighted_bipred_idc field carries the value 1)
-static size_t write_pps(int qp, uint8_t *rbsp, size_t cap)
-{
-    ByteW w{rbsp, cap, 0};
-    w.ue(0);
-    w.ue(0);
-    w.put(1, 0);
-    w.put(1, 0);
-    w.ue(0);
-    w.ue(0);
-    w.ue(0);
-    w.put(1, 0);
-    w.put(2, 1);
-    w.se(14 + qp - 26);
-    w.se(0);
-    w.se(0);
-    w.put(1, 0);
-    w.put(1, 0);
-    w.put(1, 0);
-    return w.trailing();
-}
-
-extern "C" size_t ferhip_write_pps(ferhip_ctx *c, uint8_t *rbsp, size_t cap) { return write_pps(c->p.qp, rbsp, cap); }
-
-// the PPS of stream s: pic_init_qp = 14 + base[s] (0 for a bad argument)
-extern "C" size_t ferhip_write_pps_stream(ferhip_ctx *c, int s, uint8_t *rbsp, size_t cap)
-{
-    if (!c || !rbsp || s < 0 || s >= c->d.S) return 0;
-    return write_pps(c->rate[s].base, rbsp, cap);
-}
-
-// writeNAL, F/nal.cpp:261-299
-extern "C" size_t ferhip_write_nal(int nal_ref_idc, int nal_type, const uint8_t *rbsp, size_t n, uint8_t *out)
-{
-    size_t pos = 0;
-    out[pos++] = 0;
-    out[pos++] = 0;
-    out[pos++] = 0;
-    out[pos++] = 1;
-    out[pos++] = (uint8_t)((nal_ref_idc << 5) | (nal_type & 31));
-    int zc = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (zc >= 2 && rbsp[i] <= 3) {
-            out[pos++] = 3;
-            zc = 0;
-        }
-        out[pos++] = rbsp[i];
-        zc = rbsp[i] == 0 ? zc + 1 : 0;
-    }
-    return pos;
-}
-
-// slice header of stream s for this picture: shd_write, F/headers_and_parameter_sets.cpp:172-239
-static void build_header(ferhip_ctx *c, int s, int nal_type)
-{
-    StreamState &t = c->ss[s];
-    int slice_type;
-    if (nal_type == FERHIP_NAL_NONE) {  // no picture of this stream in this call: its slice-level state stays
-        c->h_hdr[s * 4 + 0] = c->h_hdr[s * 4 + 1] = c->h_hdr[s * 4 + 2] = 0;
-        c->h_hdr[s * 4 + 3] = FER_PIC_ABSENT;
-        c->types[s] = FER_PIC_ABSENT;
-        return;
-    }
-    if (nal_type == FERHIP_NAL_IDR) {  // F/rbsp_encoding.cpp:142-164
-        slice_type = 2;
-        if (!t.first_idr_done) {
-            t.first_idr_done = 1;
-            t.idr_pic_id = 0;
-        } else if (t.frame_num == 0) {
-            t.idr_pic_id++;
-        } else {
-            t.idr_pic_id = 0;
-        }
-        t.frame_num = 0;
-        t.poc_lsb = 0;
-    } else {
-        slice_type = 0;
-        t.frame_num++;
-        t.poc_lsb += 2;
-    }
-    HBits h{0, 0};
-    h.ue(0);
-    h.ue((unsigned)slice_type);
-    h.ue(0);
-    h.put(9, (unsigned)t.frame_num & 511u);
-    if (nal_type == FERHIP_NAL_IDR) h.ue((unsigned)t.idr_pic_id);
-    h.put(10, (unsigned)t.poc_lsb & 1023u);
-    if (slice_type == 0) {
-        h.put(1, 0);  // num_ref_idx_active_override_flag
-        h.put(1, 0);  // ref_pic_list_modification_flag_l0
-        h.put(1, 0);  // adaptive_ref_pic_marking_mode_flag
-    } else {
-        h.put(1, 0);  // no_output_of_prior_pics_flag
-        h.put(1, 0);  // long_term_reference_flag
-    }
-    // slice_qp_delta is appended on the device by k_rc_plan once the picture's QP is known (fer_rate.hip)
-    c->h_hdr[s * 4 + 0] = (uint32_t)(h.v >> 32);
-    c->h_hdr[s * 4 + 1] = (uint32_t)h.v;
-    c->h_hdr[s * 4 + 2] = (uint32_t)h.n;
-    c->h_hdr[s * 4 + 3] = (uint32_t)slice_type;
-    c->types[s] = slice_type;
-}
 
 // Start filling the next slot of the header ring (waits for the copy that used it FER_HDR_SLOTS pictures ago) ...
 static int hdr_begin(ferhip_ctx *c)
 {
-    c->hdr_slot = (c->hdr_slot + 1) % FER_HDR_SLOTS;
-    CK(hipEventSynchronize(c->hdr_ev[c->hdr_slot]));
-    c->h_hdr = c->h_hdr_ring + (size_t)c->hdr_slot * 4 * c->d.S;
-    return 0;
+    c->h_hdr = (uint32_t *)c->hdr_ring.next();
+    return c->h_hdr ? 0 : FERHIP_E_HIP;
 }
 // ... and send it, with the rate settings when they changed
 static int hdr_upload(ferhip_ctx *c)
 {
     CK(hipMemcpyAsync(c->d.hdr, c->h_hdr, sizeof(uint32_t) * 4 * c->d.S, hipMemcpyHostToDevice, c->st));
     if (c->rate_dirty) {
-        FerRcPar *h = c->h_rate_ring + (size_t)c->hdr_slot * c->d.S;
+        FerRcPar *h = (FerRcPar *)c->hdr_ring.second();
         memcpy(h, c->rate.data(), sizeof(FerRcPar) * c->d.S);
         CK(hipMemcpyAsync(c->d.rc_par, h, sizeof(FerRcPar) * c->d.S, hipMemcpyHostToDevice, c->st));
         c->rate_dirty = false;
     }
-    CK(hipEventRecord(c->hdr_ev[c->hdr_slot], c->st));
-    return 0;
+    return c->hdr_ring.sent(c->st);
 }
 
 // Quality measurement: what run_picture measures -- the flags of ferhip_set_quality, and at least the SSE when a stream is in
@@ -1075,214 +735,6 @@ extern "C" int ferhip_copy_rbsp(ferhip_ctx *c, void *dst, size_t dst_stride, siz
     return 0;
 }
 
-// ---- NAL framing on the device (fer_nalpack.hip)
-static int nal_alloc(ferhip_ctx *c)
-{
-    if (c->nal_nchmax) return 0;
-    FerDev &d = c->d;
-    const int nchmax = (int)((d.bits_cap_words * 4 + 4095) / 4096);
-    // every member is set as soon as it exists, so a call after a failed one allocates only what is still missing
-    // (device buffers belong to c->allocs, the pinned index is freed by ferhip_destroy)
-    if ((!c->nal_summ && dalloc(c, &c->nal_summ, (size_t)d.S * nchmax)) || (!c->nal_cin && dalloc(c, &c->nal_cin, (size_t)d.S * nchmax)) ||
-        (!c->nal_ent && dalloc(c, &c->nal_ent, (size_t)d.S)) || (!c->nal_index && dalloc(c, &c->nal_index, (size_t)d.S + 1)) ||
-        (!c->h_nal_index && hipHostMalloc((void **)&c->h_nal_index, sizeof(ferhip_au) * (d.S + 1)) != hipSuccess) ||
-        hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
-        (void)hipGetLastError();
-        fprintf(stderr, "ferhip: could not allocate the NAL framing buffers\n");
-        return FERHIP_E_HIP;
-    }
-    c->nal_nchmax = nchmax;
-    return 0;
-}
-
-// FERHIP_AU_PARAM_SETS: the framed SPS + PPS of every stream in the device table.  Rows that can have changed are built
-// into the next slot of a pinned ring and sent from there on the context's stream (a pinned source is read when the copy
-// executes, so a slot is rewritten only after the copy that last used it has run).
-static int ps_refresh(ferhip_ctx *c)
-{
-    const int S = c->d.S;
-    if (c->ps_dirty.empty()) {
-        // as in nal_alloc: what exists is kept in the context, a call after a failed one creates only the rest
-        if ((!c->d_ps && (dalloc(c, &c->d_ps, (size_t)S * FER_NAL_PS_ROW) || hipDeviceSynchronize() != hipSuccess)) ||
-            (!c->h_ps_ring && hipHostMalloc((void **)&c->h_ps_ring, (size_t)S * FER_NAL_PS_ROW * FER_HDR_SLOTS) != hipSuccess)) {
-            (void)hipGetLastError();
-            return FERHIP_E_HIP;
-        }
-        for (int i = 0; i < FER_HDR_SLOTS; i++)
-            if (!c->ps_ev[i]) CK(hipEventCreateWithFlags(&c->ps_ev[i], hipEventDisableTiming));
-        c->ps_dirty.assign(S, 1);
-    }
-    bool any = false;
-    for (int s = 0; s < S; s++) any |= c->ps_dirty[s] != 0;
-    if (!any) return 0;
-    c->ps_slot = (c->ps_slot + 1) % FER_HDR_SLOTS;
-    CK(hipEventSynchronize(c->ps_ev[c->ps_slot]));
-    uint8_t *slot = c->h_ps_ring + (size_t)c->ps_slot * S * FER_NAL_PS_ROW;
-    for (int s = 0; s < S; s++) {
-        if (!c->ps_dirty[s]) continue;
-        uint8_t rbsp[64], nal[2 * (5 + 96)];
-        size_t n = ferhip_write_sps(c, rbsp, sizeof rbsp);
-        size_t m = ferhip_write_nal(1, 7, rbsp, n, nal);
-        n = ferhip_write_pps_stream(c, s, rbsp, sizeof rbsp);
-        m += ferhip_write_nal(1, 8, rbsp, n, nal + m);
-        if (m > FER_NAL_PS_ROW - 1) return FERHIP_E_UNSUP;
-        uint8_t *row = slot + (size_t)s * FER_NAL_PS_ROW;
-        memset(row, 0, FER_NAL_PS_ROW);
-        memcpy(row, nal, m);
-        row[FER_NAL_PS_ROW - 1] = (uint8_t)m;
-    }
-    for (int s = 0; s < S;) {  // one copy per run of rows
-        if (!c->ps_dirty[s]) {
-            s++;
-            continue;
-        }
-        int e = s;
-        while (e < S && c->ps_dirty[e]) c->ps_dirty[e++] = 0;
-        CK(hipMemcpyAsync(c->d_ps + (size_t)s * FER_NAL_PS_ROW, slot + (size_t)s * FER_NAL_PS_ROW, (size_t)(e - s) * FER_NAL_PS_ROW,
-                          hipMemcpyHostToDevice, c->st));
-        s = e;
-    }
-    CK(hipEventRecord(c->ps_ev[c->ps_slot], c->st));
-    return 0;
-}
-
-static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
-{
-    if (!c->nal_ready) return FERHIP_E_STATE;
-    (void)hipSetDevice(c->device);
-    if (nal_alloc(c)) return FERHIP_E_HIP;
-    if (flags & FERHIP_AU_PARAM_SETS) {
-        int rc = ps_refresh(c);
-        if (rc) return rc;
-    }
-    FerDev &d = c->d;
-    j.src = (const uint8_t *)d.bits;
-    j.src_stride = d.bits_cap_words * 4;
-    j.lens = d.out_bytes;
-    j.hdr = d.hdr;
-    j.types = nullptr;
-    j.ps = (flags & FERHIP_AU_PARAM_SETS) ? c->d_ps : nullptr;
-    j.n = d.S;
-    j.nchmax = c->nal_nchmax;
-    j.summ = c->nal_summ;
-    j.cin = c->nal_cin;
-    j.ent = c->nal_ent;
-    j.index = c->nal_index;
-    j.dst = nullptr;
-    j.cap = 0;
-    return 0;
-}
-
-extern "C" int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap, ferhip_au *d_index)
-{
-    if (!c || !d_index || (flags & ~FERHIP_AU_PARAM_SETS) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_index & 7) || (!d_dst && cap))
-        return FERHIP_E_ARG;
-    FerNalJob j;
-    int rc = nal_prepare(c, flags, j);
-    if (rc) return rc;
-    j.index = d_index;
-    j.dst = (uint8_t *)d_dst;
-    j.cap = cap;
-    fer_launch_nal_plan(j, c->st);
-    fer_launch_nal_emit(j, c->st);
-    CK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_au *h_index)
-{
-    if (!c || !h_index || (flags & ~FERHIP_AU_PARAM_SETS) || (!h_dst && cap)) return FERHIP_E_ARG;
-    FerNalJob j;
-    int rc = nal_prepare(c, flags, j);
-    if (rc) return rc;
-    const int S = c->d.S;
-    j.cap = cap;
-    fer_launch_nal_plan(j, c->st);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(c->h_nal_index, c->nal_index, sizeof(ferhip_au) * (S + 1), hipMemcpyDeviceToHost, c->st));
-    CK(hipStreamSynchronize(c->st));
-    memcpy(h_index, c->h_nal_index, sizeof(ferhip_au) * (S + 1));
-    const size_t total = (size_t)c->h_nal_index[S].offset;
-    if (total > cap) return FERHIP_E_ARG;
-    if (total == 0) return 0;
-    if (c->nal_buf_cap < total) {
-        if (c->nal_buf) CK(hipFree(c->nal_buf));
-        c->nal_buf = nullptr;
-        c->nal_buf_cap = 0;
-        const size_t want = (total + total / 4 + 65535) & ~(size_t)65535;
-        CK(hipMalloc((void **)&c->nal_buf, want));
-        CK(hipMemsetAsync(c->nal_buf, 0, want, c->st));  // the bytes between entries are copied out too
-        c->nal_buf_cap = want;
-    }
-    j.dst = c->nal_buf;
-    j.cap = total;
-    fer_launch_nal_emit(j, c->st);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(h_dst, c->nal_buf, total, hipMemcpyDeviceToHost, c->st));
-    CK(hipStreamSynchronize(c->st));
-    return 0;
-}
-
-// known-answer surface: host payloads through the same kernels, on the null stream with buffers of its own
-extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
-                                       size_t n, uint8_t *out, size_t cap, ferhip_au *index)
-{
-    if (!lens || !nal_type || !index || n == 0 || n > 65535 || (!out && cap)) return FERHIP_E_ARG;
-    uint32_t maxlen = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (lens[i] > stride || (lens[i] && !payloads)) return FERHIP_E_ARG;
-        maxlen = std::max(maxlen, lens[i]);
-    }
-    const size_t pitch = std::max<size_t>(((size_t)maxlen + 15) & ~(size_t)15, 16);
-    const int nchmax = (int)std::max<size_t>(((size_t)maxlen + 4095) / 4096, 1);
-    uint8_t *src = nullptr, *dst = nullptr;
-    uint32_t *dl = nullptr;
-    int32_t *dt = nullptr;
-    uint4 *summ = nullptr;
-    uint2 *cin = nullptr, *ent = nullptr;
-    ferhip_au *idx = nullptr;
-    auto body = [&]() -> int {
-        CK(hipMalloc((void **)&src, pitch * n));
-        CK(hipMalloc((void **)&dst, std::max<size_t>(cap, 16)));
-        CK(hipMalloc((void **)&dl, sizeof(uint32_t) * n));
-        CK(hipMalloc((void **)&dt, sizeof(int32_t) * n));
-        CK(hipMalloc((void **)&summ, sizeof(uint4) * n * nchmax));
-        CK(hipMalloc((void **)&cin, sizeof(uint2) * n * nchmax));
-        CK(hipMalloc((void **)&ent, sizeof(uint2) * n));
-        CK(hipMalloc((void **)&idx, sizeof(ferhip_au) * (n + 1)));
-        CK(hipMemset(src, 0, pitch * n));
-        if (maxlen) CK(hipMemcpy2D(src, pitch, payloads, stride, maxlen, n, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dl, lens, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dt, nal_type, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
-        FerNalJob j;
-        j.src = src;
-        j.src_stride = pitch;
-        j.lens = dl;
-        j.hdr = nullptr;
-        j.types = dt;
-        j.ps = nullptr;
-        j.n = (int)n;
-        j.nchmax = nchmax;
-        j.summ = summ;
-        j.cin = cin;
-        j.ent = ent;
-        j.index = idx;
-        j.dst = dst;
-        j.cap = cap;
-        fer_launch_nal_plan(j, nullptr);
-        fer_launch_nal_emit(j, nullptr);
-        CK(hipGetLastError());
-        CK(hipDeviceSynchronize());
-        if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(index, idx, sizeof(ferhip_au) * (n + 1), hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    for (void *p : {(void *)src, (void *)dst, (void *)dl, (void *)dt, (void *)summ, (void *)cin, (void *)ent, (void *)idx})
-        if (p) hipFree(p);
-    return rc;
-}
 
 extern "C" int ferhip_sync(ferhip_ctx *c)
 {
@@ -1618,7 +1070,7 @@ extern "C" size_t ferhip_read_buffer(ferhip_ctx *c, int which, void *dst, size_t
         // is built here on request from the interpolated planes (parity tests of row a16)
         n = d.ysz * 96 * d.S * 2;
         if (n > cap) return 0;
-        if (!d.feat && dalloc(c, &d.feat, d.ysz * 96 * d.S)) return 0;
+        if (dalloc(c, &d.feat, d.ysz * 96 * d.S)) return 0;
         if (hipDeviceSynchronize() != hipSuccess) return 0;
         fer_launch_features(d, c->st);
         src = d.feat;
@@ -1673,1116 +1125,3 @@ extern "C" size_t ferhip_read_buffer(ferhip_ctx *c, int which, void *dst, size_t
     return n;
 }
 
-
-// =====================================================================================
-// Decoder driver: decode() / RBSP_decode() of F/fer_h264.cpp:26-53, F/rbsp_decoding.cpp:17-367.
-// Host side: Annex-B scan + emulation-prevention removal (F/nal.cpp:68-223), parameter sets and
-// slice header (F/headers_and_parameter_sets.cpp:245-298,398-537) -- a few dozen bits per NAL.
-// The macroblock loop runs on the device (fer_decode.hip).
-// =====================================================================================
-struct HostBR {
-    const uint8_t *b;
-    size_t n, pos;
-    unsigned bit()
-    {
-        size_t by = pos >> 3;
-        unsigned v = by < n ? (b[by] >> (7 - (pos & 7))) & 1u : 0u;
-        pos++;
-        return v;
-    }
-    unsigned bits(int k)
-    {
-        unsigned v = 0;
-        for (int i = 0; i < k; i++) v = (v << 1) | bit();
-        return v;
-    }
-    unsigned ue()
-    {
-        int z = 0;
-        while (z < 24 && bit() == 0) z++;  // the reference searches a 24-bit window (F/expgolomb.cpp:122)
-        return (1u << z) - 1u + bits(z);
-    }
-    int se()
-    {
-        int v = (int)ue();
-        return (v & 1) ? (v + 1) / 2 : -v / 2;
-    }
-};
-
-struct DecHdr {
-    int have_sps, have_pps, W, H, log2_max_frame_num, poc_type, log2_max_poc_lsb;
-    int pic_init_qp, chroma_qp_offset, deblock_ctl, constrained_intra;
-    // slice-header state the reference keeps in globals between slices: the active reference count is only ever set
-    // by an override (never reset to the PPS default), the list-modification flag and its entry count only by P slices
-    int nref_active_minus1, mod_flag, mod_copies;
-};
-
-// seq_parameter_set_rbsp, F/headers_and_parameter_sets.cpp:398-470.  Returns 0, or FERHIP_E_UNSUP for syntax the
-// slice parser does not implement (the reference would mis-decode it silently).
-static int dec_parse_sps(DecHdr &h, HostBR &r)
-{
-    const unsigned profile_idc = r.bits(8);
-    r.bits(16);
-    r.ue();
-    if (profile_idc >= 100) return FERHIP_E_UNSUP;  // High profiles carry chroma_format_idc ... here
-    h.log2_max_frame_num = (int)r.ue() + 4;
-    h.poc_type = (int)r.ue();
-    h.log2_max_poc_lsb = 0;
-    if (h.poc_type == 0) {
-        h.log2_max_poc_lsb = (int)r.ue() + 4;
-    } else if (h.poc_type == 1) {
-        r.bits(1);
-        r.se();
-        r.se();
-        int n = (int)r.ue();
-        for (int i = 0; i < n; i++) r.se();
-    }
-    r.ue();
-    r.bits(1);
-    int wmb = (int)r.ue() + 1, hmu = (int)r.ue() + 1, fmo = (int)r.bits(1);
-    if (!fmo) return FERHIP_E_UNSUP;  // field / MBAFF coding
-    h.W = wmb * 16;
-    h.H = hmu * 16;
-    h.have_sps = 1;
-    return 0;
-}
-
-// pic_parameter_set_rbsp, F/headers_and_parameter_sets.cpp:520-537
-static int dec_parse_pps(DecHdr &h, HostBR &r)
-{
-    r.ue();
-    r.ue();
-    if (r.bits(1)) return FERHIP_E_UNSUP;  // entropy_coding_mode_flag: CABAC
-    r.bits(1);
-    if (r.ue() > 0) return FERHIP_E_UNSUP;  // slice groups
-    if (r.ue() > 0) return FERHIP_E_UNSUP;  // num_ref_idx_l0_default_active_minus1: several reference indices
-    r.ue();
-    r.bits(3);
-    h.pic_init_qp = r.se() + 26;
-    r.se();
-    h.chroma_qp_offset = r.se();
-    h.deblock_ctl = (int)r.bits(1);
-    h.constrained_intra = (int)r.bits(1);
-    h.have_pps = 1;
-    return 0;
-}
-
-// slice header -> info[4] = {rbsp bytes, first bit of slice_data, slice_type % 5, SliceQPy}; returns 0 or error
-static int dec_parse_slice_header(DecHdr &h, const uint8_t *rbsp, size_t n, int nal_type, int ref_idc, uint32_t *info,
-                                  int &override_flag)
-{
-    if (!h.have_sps || !h.have_pps) return FERHIP_E_STATE;
-    HostBR r{rbsp, n, 0};
-    r.ue();
-    int st = (int)r.ue() % 5;
-    r.ue();
-    r.bits(h.log2_max_frame_num);
-    if (nal_type == 5) r.ue();
-    r.bits(h.log2_max_poc_lsb);
-    if (st == 0 || st == 1 || st == 3) {
-        override_flag = (int)r.bits(1);
-        if (override_flag) h.nref_active_minus1 = (int)r.ue();  // only tells the macroblock layer whether ref_idx is coded
-    }
-    if (st != 2 && st != 4) {  // ref_pic_list_modification (F/headers_and_parameter_sets.cpp:196-215)
-        h.mod_flag = (int)r.bits(1);
-        h.mod_copies = 0;
-        if (h.mod_flag) {
-            unsigned idc;
-            int guard = 0;
-            do {
-                idc = r.ue();
-                if (idc <= 2) {
-                    r.ue();
-                    h.mod_copies++;
-                }
-            } while (idc != 3 && ++guard < 64 && r.pos < n * 8);
-        }
-    }
-    if (ref_idc != 0) {
-        if (nal_type == 5) {
-            r.bits(2);
-        } else if (r.bits(1)) {
-            unsigned op;
-            do {
-                op = r.ue();
-                if (op == 1 || op == 3) r.ue();
-                if (op == 2) r.ue();
-                if (op == 3 || op == 6) r.ue();
-                if (op == 4) r.ue();
-            } while (op != 0);
-        }
-    }
-    int qp = h.pic_init_qp + r.se();
-    if (h.deblock_ctl == 1) {
-        if (r.ue() != 1) {
-            r.se();
-            r.se();
-        }
-    }
-    if (st != 0 && st != 2) return FERHIP_E_UNSUP;
-    info[0] = (uint32_t)n;
-    info[1] = (uint32_t)r.pos;
-    // slice type | ref_idx coded in sub-macroblock prediction (the reference tests the override FLAG there,
-    // F/rbsp_decoding.cpp:156) << 8 | active reference count - 1 (what it tests in mb_pred, :217) << 16
-    info[2] = (uint32_t)st | ((uint32_t)(override_flag ? 1 : 0) << 8) | ((uint32_t)std::min(h.nref_active_minus1, 255) << 16);
-    info[3] = (uint32_t)qp;
-    return 0;
-}
-
-// split an Annex-B stream like findNALstart/findNALend/parseNAL (4-byte start codes only)
-struct ByteView {  // bytes owned elsewhere: a stream's RBSP store (split_stream) or the caller's buffer (ferhip_dec_nal)
-    const uint8_t *p = nullptr;
-    size_t n = 0;
-    const uint8_t *data() const { return p; }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-};
-struct NalRef {
-    int type, ref_idc;
-    ByteView rbsp;
-};
-// next position i in [from, n - 2) with s[i] == 0, s[i+1] == 0 and s[i+2] in `third` (two allowed values), or npos;
-// zero bytes are rare in entropy-coded data, so the scan is driven by memchr
-static size_t find_zz(const uint8_t *s, size_t from, size_t n, uint8_t t0, uint8_t t1)
-{
-    while (from + 2 < n) {
-        const uint8_t *p = (const uint8_t *)memchr(s + from, 0, n - 2 - from);
-        if (!p) break;
-        size_t i = (size_t)(p - s);
-        if (s[i + 1] == 0 && (s[i + 2] == t0 || s[i + 2] == t1)) return i;
-        from = i + 1;
-    }
-    return (size_t)-1;
-}
-// `store` receives the RBSP of every NAL unit back to back (never more than the stream itself) and must outlive `out`
-static void split_stream(const uint8_t *s, size_t n, std::vector<NalRef> &out, std::vector<uint8_t> &store)
-{
-    if (store.size() < n) store.resize(n);
-    uint8_t *w = store.data();
-    size_t pos = 0;
-    for (;;) {
-        size_t st = (size_t)-1;
-        for (size_t i = pos; i + 3 < n;) {  // 00 00 00 01
-            size_t z = find_zz(s, i, n - 1, 0, 0);
-            if (z == (size_t)-1) break;
-            if (s[z + 3] == 1) {
-                st = z + 4;
-                break;
-            }
-            i = z + 1;
-        }
-        if (st == (size_t)-1) break;
-        size_t en = find_zz(s, st, n, 0, 1);
-        if (en == (size_t)-1) en = n;
-        pos = en;
-        if (en <= st) continue;
-        NalRef nal;
-        nal.ref_idc = (s[st] & 0x7f) >> 5;
-        nal.type = s[st] & 0x1f;
-        uint8_t *w0 = w;
-        size_t from = st + 1;
-        for (;;) {  // drop the emulation prevention byte of every 00 00 03
-            size_t z = find_zz(s, from, en, 3, 3);
-            if (z == (size_t)-1) break;
-            memcpy(w, s + from, z + 2 - from);
-            w += z + 2 - from;
-            from = z + 3;
-        }
-        if (from < en) {
-            memcpy(w, s + from, en - from);
-            w += en - from;
-        }
-        nal.rbsp.p = w0;
-        nal.rbsp.n = (size_t)(w - w0);
-        if (nal.rbsp.empty()) break;
-        out.push_back(std::move(nal));
-    }
-}
-
-// Window buffers of the decode twin.  ferhip_decode_streams keeps one arena per process between calls (releasing
-// tens of GB costs more than a window's reconstruction); it is tied to the HIP device it was allocated on and
-// can be dropped with ferhip_decode_release().  A streaming decoder (ferhip_dec_*) owns a small one of its own.
-struct DecArena {
-    void *dev = nullptr;
-    size_t bytes = 0;
-    int device = -1;
-    uint8_t *d_rbsp = nullptr, *h_rbsp = nullptr;  // slices of a window: device buffer and pinned staging
-    size_t rbsp_cap = 0;
-    bool busy = false, cached = false;
-};
-static DecArena g_dec_arena;
-static std::mutex g_dec_arena_mu;
-static thread_local std::vector<std::vector<uint8_t>> tl_rbsp_store;  // ferhip_decode_streams: the streams' RBSP, per calling thread
-static void dec_arena_free(DecArena *a)
-{
-    if (a->dev) hipFree(a->dev);
-    if (a->d_rbsp) hipFree(a->d_rbsp);
-    if (a->h_rbsp) hipHostFree(a->h_rbsp);
-    a->dev = nullptr;
-    a->d_rbsp = a->h_rbsp = nullptr;
-    a->bytes = a->rbsp_cap = 0;
-    a->device = -1;
-}
-static DecArena *dec_arena_acquire(size_t need, int device, bool use_cache)
-{
-    DecArena *a = nullptr;
-    if (use_cache) {
-        std::lock_guard<std::mutex> lk(g_dec_arena_mu);
-        if (!g_dec_arena.busy) {
-            a = &g_dec_arena;
-            a->busy = true;
-            a->cached = true;
-        }
-    }
-    if (!a) {
-        a = new DecArena();
-        a->busy = true;
-    }
-    if (a->device != device && a->device >= 0) {  // allocated on another device: its pointers are useless here
-        int cur = device;
-        (void)hipSetDevice(a->device);
-        dec_arena_free(a);
-        (void)hipSetDevice(cur);
-    }
-    a->device = device;
-    if (a->bytes < need) {
-        if (a->dev) hipFree(a->dev);
-        a->dev = nullptr;
-        a->bytes = 0;
-        if (hipMalloc(&a->dev, need) != hipSuccess) {
-            (void)hipGetLastError();
-            a->dev = nullptr;
-            std::lock_guard<std::mutex> lk(g_dec_arena_mu);
-            if (a->cached)
-                a->busy = false;
-            else
-                delete a;
-            return nullptr;
-        }
-        a->bytes = need;
-    }
-    return a;
-}
-static void dec_arena_release(DecArena *a)
-{
-    if (!a) return;
-    if (a->cached) {
-        std::lock_guard<std::mutex> lk(g_dec_arena_mu);
-        a->busy = false;
-    } else {
-        dec_arena_free(a);
-        delete a;
-    }
-}
-
-extern "C" int ferhip_decode_release(void)
-{
-    std::vector<std::vector<uint8_t>>().swap(tl_rbsp_store);
-    std::lock_guard<std::mutex> lk(g_dec_arena_mu);
-    if (g_dec_arena.busy) return FERHIP_E_STATE;
-    if (g_dec_arena.device >= 0) {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(g_dec_arena.device);
-        dec_arena_free(&g_dec_arena);
-        (void)hipSetDevice(cur);
-    }
-    return 0;
-}
-
-// One decoding session: S streams of one picture size, a window of up to TWmax pictures per stream parsed by one
-// launch, parameter sets and the state the reference keeps in globals (mb_qp_delta, ChromaACLevel) per stream.
-struct DecSession {
-    ferhip_ctx *c = nullptr;
-    int S = 0;
-    std::vector<DecHdr> hs;  // parameter sets of every stream (the QP of this codec lives in the PPS)
-    DecArena *ar = nullptr;
-    DecBatch B;
-    uint32_t *d_info = nullptr;
-    size_t TWmax = 0, nm = 0, fsz = 0;
-    std::vector<uint32_t> info, hdr;
-    std::vector<char> anyP, anyAny, keep, pres;  // pres[t * S + s]: stream s has a picture at step t of the window
-    // A picture whose slice carries an empty reference-list modification is NOT stored as the reference picture
-    // (modificationProcess, F/ref_frames.cpp:130-183): the stream's last decoded picture (what `frame` holds, what a
-    // slice that ends early leaves in place) then differs from its reference picture and waits in `hold`.
-    uint8_t *hold = nullptr;
-    std::vector<char> held;
-    double t_pack = 0, t_parse = 0, t_recon = 0;
-};
-
-static double dec_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-static void dec_session_close(DecSession &ss)
-{
-    if (ss.c) {
-        (void)hipSetDevice(ss.c->device);
-        hipStreamSynchronize(ss.c->st);
-    }
-    dec_arena_release(ss.ar);
-    ss.ar = nullptr;
-    if (ss.hold) hipFree(ss.hold);
-    ss.hold = nullptr;
-    if (ss.c) ferhip_destroy(ss.c);
-    ss.c = nullptr;
-}
-
-// T = pictures per stream the caller expects (sizes the window); use_cache = take the process-wide arena
-static int dec_session_open(DecSession &ss, int W, int H, int S, size_t T, bool use_cache)
-{
-    ferhip_params p = {26, 0, 16, 3, 1 << 30};
-    int rc = ctx_create(&ss.c, W, H, S, &p, true);
-    if (rc) return rc;
-    FerDev &d = ss.c->d;
-    ss.S = S;
-    ss.nm = (size_t)S * d.nmb;
-    ss.fsz = (size_t)W * H * 3 / 2;
-    const size_t nm = ss.nm;
-    const size_t per_pic = nm * (4 + 16 + 2 + 24 + 16 + 16 + 1 + FER_LEVELS * 2 + 1 + 1);
-    size_t budget = (size_t)48e9, freeb = 0, totalb = 0;
-    if (hipMemGetInfo(&freeb, &totalb) == hipSuccess) {
-        std::lock_guard<std::mutex> lk(g_dec_arena_mu);
-        if (use_cache && !g_dec_arena.busy && g_dec_arena.device == ss.c->device) freeb += g_dec_arena.bytes;
-        budget = std::min(budget, freeb / 2);
-    }
-    size_t TWmax = std::min<size_t>(std::max<size_t>(budget / per_pic, 1), 256);
-    TWmax = std::max<size_t>(std::min(TWmax, T), 1);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    uint8_t *base = nullptr;
-    size_t sizes[16];
-    for (;;) {  // halve the window until its buffers fit
-        const size_t sz[16] = {TWmax * nm * 4, TWmax * nm * 16, TWmax * nm * 2, TWmax * nm * 24, TWmax * nm * 16, TWmax * nm * 16,
-                               TWmax * nm, TWmax * nm * FER_LEVELS * 2, TWmax * nm, TWmax * nm, TWmax * S * 16, TWmax * S * 16,
-                               TWmax * S * 16, TWmax * S * 256, TWmax * S * 256, TWmax * S * 24};
-        size_t need = 0;
-        for (int i = 0; i < 16; i++) {
-            sizes[i] = sz[i];
-            need += up(sz[i]) + 256;
-        }
-        ss.ar = dec_arena_acquire(need, ss.c->device, use_cache);
-        if (ss.ar) break;
-        if (TWmax == 1) {
-            dec_session_close(ss);
-            return FERHIP_E_HIP;
-        }
-        TWmax = (TWmax + 1) / 2;
-    }
-    ss.TWmax = TWmax;
-    base = (uint8_t *)ss.ar->dev;
-    size_t off = 0;
-    auto wmalloc = [&](size_t bytes) -> void * {
-        void *v = base + off;
-        off += up(bytes) + 256;
-        return v;
-    };
-    DecBatch &B = ss.B;
-    B.mb_type = (int *)wmalloc(sizes[0]);
-    B.mv = (short *)wmalloc(sizes[1]);
-    B.cbp = (uint8_t *)wmalloc(sizes[2]);
-    B.tc = (uint8_t *)wmalloc(sizes[3]);
-    B.i4mode = (uint8_t *)wmalloc(sizes[4]);
-    B.i4flag = (uint8_t *)wmalloc(sizes[5]);
-    B.chroma_mode = (uint8_t *)wmalloc(sizes[6]);
-    B.levels = (int16_t *)wmalloc(sizes[7]);
-    B.dec_qp = (uint8_t *)wmalloc(sizes[8]);
-    B.carry = (uint8_t *)wmalloc(sizes[9]);
-    B.hdr = (uint32_t *)wmalloc(sizes[10]);
-    B.state = (int *)wmalloc(sizes[11]);
-    B.summ = (int *)wmalloc(sizes[12]);
-    B.cac_in = (int16_t *)wmalloc(sizes[13]);
-    B.cac_out = (int16_t *)wmalloc(sizes[14]);
-    ss.d_info = (uint32_t *)wmalloc(sizes[15]);
-    ss.hs.assign(S, DecHdr{});
-    ss.held.assign(S, 0);
-    return 0;
-}
-
-// the three planes of stream s from one plane-major picture set to another (same stream order)
-static int dec_copy_stream(ferhip_ctx *c, uint8_t *dst, const uint8_t *src, int s)
-{
-    const FerDev &d = c->d;
-    const size_t S = (size_t)d.S;
-    const size_t off[3] = {(size_t)s * d.ysz, S * d.ysz + (size_t)s * d.csz, S * (d.ysz + d.csz) + (size_t)s * d.csz};
-    const size_t len[3] = {d.ysz, d.csz, d.csz};
-    for (int k = 0; k < 3; k++)
-        if (hipMemcpyAsync(dst + off[k], src + off[k], len[k], hipMemcpyDeviceToDevice, c->st) != hipSuccess) return FERHIP_E_HIP;
-    return 0;
-}
-
-// Per-stream error isolation of a window (the live decoder, ferhip_decs_*).  Without it the first stream that fails
-// fails the window.  With it a stream's fault ends that stream's part of the window: the faulted picture and the ones
-// after it are not reconstructed, status[s] records the FERHIP_E_* and the other streams go on.  The output then goes
-// through k_dec_out, which writes only the slots of pictures that were decoded.
-struct DecIsolate {
-    int *status = nullptr;       // [S] 0, or the first fault of stream s in this call
-    std::vector<char> stop;      // [S] stream s faulted inside a window: it takes no more pictures in this call
-    uint8_t *out = nullptr;      // [max_pictures][S][fsz]: picture k of stream s at (k * S + s) * fsz, or NULL
-    bool out_dev = false;        // out is device memory
-    int2 *d_map = nullptr;       // [TWmax][S] device: the (stream, slot) pairs of every step for k_dec_out
-    std::vector<int2> map;       // ... host side
-    std::vector<int> nmap;       // [TW] pairs per step
-    std::vector<size_t> fin;     // host output: slot (k * S + s) of the caller's buffer of every staged picture, in order
-    uint8_t *d_stage = nullptr, *h_stage = nullptr;  // host output: the window's pictures, packed, on the device and pinned
-    size_t stage_cap = 0;        // pictures
-};
-
-// After the parse of an isolated window: find each faulted stream's first faulted picture (B.state[pic * 4 + 3]), drop it
-// and the stream's later pictures from the window (macroblocks reached = 0, so the reconstruction leaves them alone),
-// clear the sticky status, then lay out the output of the pictures that remain.  pictures[s] = pictures of stream s
-// before this window.
-static int dec_isolate_faults(DecSession &ss, size_t TW, DecIsolate &iso, const int *pictures)
-{
-    ferhip_ctx *c = ss.c;
-    const int S = ss.S;
-    bool any = false;
-    for (int s = 0; s < S; s++) any |= c->h_status[s] != 0;
-    if (any) {
-        std::vector<int> st(TW * S * 4);
-        if (hipMemcpyAsync(st.data(), ss.B.state, st.size() * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
-            hipStreamSynchronize(c->st) != hipSuccess)
-            return FERHIP_E_HIP;
-        for (int s = 0; s < S; s++) {
-            if (!c->h_status[s]) continue;
-            bool hit = false;
-            for (size_t t = 0; t < TW; t++) {
-                const size_t pic = t * S + s;
-                if (!ss.pres[pic]) continue;
-                if (!hit && st[pic * 4 + 3]) {
-                    hit = true;
-                    iso.stop[s] = 1;
-                    iso.status[s] = (st[pic * 4 + 3] & FER_ERR_DEC_UNSUPPORTED) ? FERHIP_E_UNSUP : FERHIP_E_DEVICE;
-                }
-                if (hit) {
-                    ss.pres[pic] = 0;
-                    st[pic * 4 + 1] = 0;
-                }
-            }
-            if (!hit) return FERHIP_E_HIP;  // a status bit without a faulted picture: the device state is not to be trusted
-        }
-        if (hipMemcpyAsync(ss.B.state, st.data(), st.size() * 4, hipMemcpyHostToDevice, c->st) != hipSuccess ||
-            hipMemsetAsync(c->d.status, 0, sizeof(int) * S, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)
-            return FERHIP_E_HIP;
-        for (size_t t = 0; t < TW; t++) {
-            ss.anyP[t] = ss.anyAny[t] = 0;
-            for (int s = 0; s < S; s++)
-                if (ss.pres[t * S + s]) {
-                    ss.anyAny[t] = 1;
-                    ss.anyP[t] |= ss.hdr[(t * S + s) * 4 + 3] == 0;
-                }
-        }
-    }
-    if (!iso.out) return 0;
-    // output: step t writes map[t * S + k], k < nmap[t] = (stream, slot); the slot is the caller's (picture * S + stream)
-    // for device output, the next free picture of the staging buffer for host output
-    iso.map.resize(TW * S);
-    iso.nmap.assign(TW, 0);
-    iso.fin.clear();
-    for (size_t t = 0; t < TW; t++)
-        for (int s = 0; s < S; s++) {
-            if (!ss.pres[t * S + s]) continue;
-            const size_t slot = (size_t)(pictures[s] + (int)t) * S + s;
-            int2 &e = iso.map[t * S + iso.nmap[t]++];
-            e.x = s;
-            e.y = iso.out_dev ? (int)slot : (int)iso.fin.size();
-            if (!iso.out_dev) iso.fin.push_back(slot);
-        }
-    if (!iso.out_dev && iso.fin.size() > iso.stage_cap) {  // grows to the largest window seen, then stays
-        if (iso.d_stage) hipFree(iso.d_stage);
-        if (iso.h_stage) hipHostFree(iso.h_stage);
-        iso.d_stage = iso.h_stage = nullptr;
-        iso.stage_cap = 0;
-        const size_t cap = std::min(std::max(iso.fin.size(), (size_t)S), ss.TWmax * S);
-        if (hipMalloc((void **)&iso.d_stage, cap * ss.fsz) != hipSuccess || hipHostMalloc((void **)&iso.h_stage, cap * ss.fsz) != hipSuccess)
-            return FERHIP_E_HIP;
-        iso.stage_cap = cap;
-    }
-    if (hipMemcpyAsync(iso.d_map, iso.map.data(), TW * S * sizeof(int2), hipMemcpyHostToDevice, c->st) != hipSuccess) return FERHIP_E_HIP;
-    return 0;
-}
-
-// Decode pictures [t0, t0 + TW) of every stream: slices[s][t] = the slice NAL of picture t of stream s (streams may
-// be shorter; nullptr = no picture at that step).  out (host, may be NULL) receives picture t of stream s at
-// (t * S + s) * fsz; pictures[s] counts.  iso: see DecIsolate (out is then unused).
-static int dec_session_window(DecSession &ss, const std::vector<std::vector<const NalRef *>> &slices, size_t t0, size_t TW,
-                              uint8_t *out, int *pictures, DecIsolate *iso = nullptr)
-{
-    ferhip_ctx *c = ss.c;
-    FerDev &d = c->d;
-    const int S = ss.S;
-    const size_t nm = ss.nm;
-    DecBatch &B = ss.B;
-    DecArena *ar = ss.ar;
-    double ta = dec_now();
-    ss.info.assign(TW * S * 6, 0);
-    ss.hdr.assign(TW * S * 4, 0);
-    ss.anyP.assign(TW, 0);
-    ss.anyAny.assign(TW, 0);
-    ss.keep.assign(TW * S, 1);
-    ss.pres.assign(TW * S, 0);
-    // slice headers and the offsets of the slices in the window's RBSP buffer
-    size_t total = 0;
-    for (size_t t = 0; t < TW; t++)
-        for (int s = 0; s < S; s++) {
-            uint32_t *in = &ss.info[(t * S + s) * 6];
-            uint32_t *hd = &ss.hdr[(t * S + s) * 4];
-            hd[3] = 2;
-            if (t0 + t >= slices[s].size() || !slices[s][t0 + t] || (iso && iso->stop[s])) continue;
-            const NalRef &n = *slices[s][t0 + t];
-            int ov = 0;
-            int rc = dec_parse_slice_header(ss.hs[s], n.rbsp.data(), n.rbsp.size(), n.type, n.ref_idc, in, ov);
-            // a header that runs past the end of its NAL unit, or a SliceQPY outside 0..51: damaged
-            if (!rc && iso && (in[1] > n.rbsp.size() * 8 || in[3] > 51)) rc = FERHIP_E_ARG;
-            if (rc) {
-                if (!iso) return rc;
-                iso->status[s] = rc;
-                iso->stop[s] = 1;
-                for (int k = 0; k < 6; k++) in[k] = 0;
-                continue;
-            }
-            ss.pres[t * S + s] = 1;
-            in[4] = (uint32_t)total;
-            in[5] = (uint32_t)(total >> 32);
-            total += (n.rbsp.size() + 15) & ~(size_t)15;
-            // what the kernels need of this stream's PPS travels with the picture
-            hd[0] = (uint32_t)ss.hs[s].chroma_qp_offset;
-            hd[1] = (uint32_t)ss.hs[s].constrained_intra;
-            hd[3] = in[2] & 255u;
-            ss.anyP[t] |= (in[2] & 255u) == 0;
-            ss.anyAny[t] = 1;
-            ss.keep[t * S + s] = !ss.hs[s].mod_flag || ss.hs[s].mod_copies > 0;
-        }
-    if (total + 64 > ar->rbsp_cap) {
-        if (ar->d_rbsp) hipFree(ar->d_rbsp);
-        if (ar->h_rbsp) hipHostFree(ar->h_rbsp);
-        ar->d_rbsp = ar->h_rbsp = nullptr;
-        ar->rbsp_cap = total + total / 4 + 4096;
-        if (hipMalloc((void **)&ar->d_rbsp, ar->rbsp_cap) != hipSuccess || hipHostMalloc((void **)&ar->h_rbsp, ar->rbsp_cap) != hipSuccess) {
-            ar->rbsp_cap = 0;
-            return FERHIP_E_HIP;
-        }
-    }
-    {  // gather the slices into the pinned staging buffer with a few threads, then one H2D copy
-        const int nth = std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
-        auto gather = [&](int k) {
-            for (int s = k; s < S; s += nth)
-                for (size_t t = 0; t < TW; t++) {
-                    if (!ss.pres[t * S + s]) continue;
-                    const NalRef &n = *slices[s][t0 + t];
-                    const uint32_t *in = &ss.info[(t * S + s) * 6];
-                    memcpy(ar->h_rbsp + (((size_t)in[5] << 32) | in[4]), n.rbsp.data(), n.rbsp.size());
-                }
-        };
-        if (nth == 1) {
-            gather(0);
-        } else {
-            std::vector<std::thread> th;
-            for (int k = 0; k < nth; k++) th.emplace_back(gather, k);
-            for (auto &x : th) x.join();
-        }
-    }
-    if (hipMemcpyAsync(ar->d_rbsp, ar->h_rbsp, total, hipMemcpyHostToDevice, c->st) != hipSuccess ||
-        hipMemcpyAsync(ss.d_info, ss.info.data(), ss.info.size() * 4, hipMemcpyHostToDevice, c->st) != hipSuccess ||
-        hipMemcpyAsync(B.hdr, ss.hdr.data(), ss.hdr.size() * 4, hipMemcpyHostToDevice, c->st) != hipSuccess)
-        return FERHIP_E_HIP;
-    B.TW = (int)TW;
-    B.rbsp = ar->d_rbsp;
-    B.info = ss.d_info;
-    ss.t_pack += dec_now() - ta;
-    ta = dec_now();
-    fer_launch_decode_parse(d, B, c->st);
-    // the host vectors above are read by the copies when they execute: the synchronisation below covers them
-    if (hipMemcpyAsync(c->h_status, d.status, sizeof(int) * S, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
-        hipStreamSynchronize(c->st) != hipSuccess || hipGetLastError() != hipSuccess)
-        return FERHIP_E_HIP;
-    if (iso) {
-        int rc = dec_isolate_faults(ss, TW, *iso, pictures);
-        if (rc) return rc;
-    } else {
-        for (int s = 0; s < S; s++)
-            if (c->h_status[s]) {
-                fprintf(stderr, "ferhip: stream %d decode status 0x%x\n", s, c->h_status[s]);
-                return (c->h_status[s] & FER_ERR_DEC_UNSUPPORTED) ? FERHIP_E_UNSUP : FERHIP_E_DEVICE;
-            }
-    }
-    ss.t_parse += dec_now() - ta;
-    ta = dec_now();
-    for (size_t t = 0; t < TW; t++) {
-        if (!ss.anyAny[t]) break;
-        // `frame` keeps the previous picture where the parser does not reach (F/rbsp_decoding.cpp:77)
-        if (hipMemcpyAsync(c->planes[c->cur_set], c->planes[c->cur_set ^ 1], d.ysz * 3 / 2 * S, hipMemcpyDeviceToDevice, c->st) !=
-            hipSuccess)
-            return FERHIP_E_HIP;
-        for (int s = 0; s < S; s++)  // ... which, for a stream whose last picture was not stored as reference, waits in `hold`
-            if (ss.held[s] && (!iso || ss.pres[t * S + s]) && dec_copy_stream(c, c->planes[c->cur_set], ss.hold, s)) return FERHIP_E_HIP;
-        FerDev ds = d;  // this picture's slice of the window
-        const size_t o = t * nm;
-        ds.mb_type = B.mb_type + o;
-        ds.mv = B.mv + o * 8;
-        ds.cbp = B.cbp + o * 2;
-        ds.tc = B.tc + o * 24;
-        ds.i4mode = B.i4mode + o * 16;
-        ds.i4flag = B.i4flag + o * 16;
-        ds.chroma_mode = B.chroma_mode + o;
-        ds.levels = B.levels + o * FER_LEVELS;
-        ds.dec_qp = B.dec_qp + o;
-        ds.hdr = B.hdr + t * S * 4;
-        ds.dec_state = B.state + t * S * 4;
-        fer_launch_decode_recon(ds, ss.anyP[t] != 0, true, c->st);
-        c->cur_set ^= 1;  // the decoded picture becomes the reference (modificationProcess -> frameDeepCopy)
-        bind_planes(c);
-        if (iso) {
-            if (iso->out)
-                fer_launch_decode_out(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], iso->out_dev ? iso->out : iso->d_stage,
-                                      c->st);
-        } else if (out) {
-            int rc = ferhip_get_recon(c, out + (t0 + t) * S * ss.fsz, 1);
-            if (rc) return rc;
-        }
-        for (int s = 0; s < S; s++) {
-            if (!ss.pres[t * S + s]) continue;
-            if (!ss.keep[t * S + s]) {
-                // not stored: the picture moves to `hold`, the stream's reference picture (still intact in the other
-                // set) moves back into the reference set
-                if (!ss.hold) {
-                    if (hipMalloc((void **)&ss.hold, d.ysz * 3 / 2 * S + 256) != hipSuccess) return FERHIP_E_HIP;
-                }
-                if (dec_copy_stream(c, ss.hold, c->planes[c->cur_set ^ 1], s) ||
-                    dec_copy_stream(c, c->planes[c->cur_set ^ 1], c->planes[c->cur_set], s))
-                    return FERHIP_E_HIP;
-                ss.held[s] = 1;
-            } else {
-                ss.held[s] = 0;
-            }
-        }
-        if (pictures)
-            for (int s = 0; s < S; s++)
-                if (ss.pres[t * S + s]) pictures[s]++;
-    }
-    size_t staged = 0;
-    if (iso && iso->out && !iso->out_dev) {
-        for (size_t t = 0; t < TW; t++) staged += (size_t)iso->nmap[t];
-        if (staged && hipMemcpyAsync(iso->h_stage, iso->d_stage, staged * ss.fsz, hipMemcpyDeviceToHost, c->st) != hipSuccess)
-            return FERHIP_E_HIP;
-    }
-    if (hipStreamSynchronize(c->st) != hipSuccess || hipGetLastError() != hipSuccess) return FERHIP_E_HIP;
-    if (staged) {  // the staged pictures to their slots of the caller's buffer (nothing else of it is written)
-        const size_t fsz = ss.fsz;
-        auto scatter = [&](size_t j0, size_t j1) {
-            for (size_t j = j0; j < j1; j++) memcpy(iso->out + iso->fin[j] * fsz, iso->h_stage + j * fsz, fsz);
-        };
-        const size_t nth = std::min<size_t>(std::min<size_t>(staged * fsz >> 23, 16), std::max(1u, std::thread::hardware_concurrency()));
-        if (nth <= 1) {
-            scatter(0, staged);
-        } else {
-            std::vector<std::thread> th;
-            for (size_t k = 0; k < nth; k++) th.emplace_back(scatter, staged * k / nth, staged * (k + 1) / nth);
-            for (auto &x : th) x.join();
-        }
-    }
-    ss.t_recon += dec_now() - ta;
-    return 0;
-}
-
-// decode() for S Annex-B streams side by side.  All streams must carry the same picture size.
-// out: host [T][S][W*H*3/2] (T = max_pictures); pictures[s] = pictures decoded of stream s.
-extern "C" int ferhip_decode_streams(const uint8_t *const *streams, const size_t *lens, int S, uint8_t *out,
-                                     int max_pictures, int *pictures, int *W_out, int *H_out)
-{
-    if (!streams || !lens || S <= 0 || !pictures) return FERHIP_E_ARG;
-    if (out && max_pictures <= 0) return FERHIP_E_ARG;  // `out` holds max_pictures pictures per stream: its size must be known
-    const bool verbose = getenv("FER_DEC_TIMING") != nullptr;
-    double t_start = dec_now();
-    std::vector<std::vector<NalRef>> nals(S);
-    // the RBSP of every stream, kept by the calling thread between calls like the device arena: 240 MB of fresh heap per
-    // call (128 1080p GOPs) cost 0.25 s in page faults and unmapping, a fifth of the decode itself
-    std::vector<std::vector<uint8_t>> &rbsp_store = tl_rbsp_store;
-    if ((int)rbsp_store.size() < S) rbsp_store.resize(S);
-    {  // NAL splitting is host work per stream: spread it over a few threads
-        const int nth = std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
-        std::vector<std::thread> th;
-        std::vector<std::vector<uint8_t>> &store = rbsp_store;
-        for (int k = 0; k < nth; k++)
-            th.emplace_back([&, k]() {
-                for (int s = k; s < S; s += nth) split_stream(streams[s], lens[s], nals[s], store[s]);
-            });
-        for (auto &x : th) x.join();
-    }
-    // parameter sets per stream (the last SPS / PPS of a stream wins, as in the reference, which keeps one of each)
-    std::vector<DecHdr> hs(S, DecHdr{});
-    for (int s = 0; s < S; s++) {
-        for (auto &n : nals[s]) {
-            HostBR r{n.rbsp.data(), n.rbsp.size(), 0};
-            int rc = 0;
-            if (n.type == 7)
-                rc = dec_parse_sps(hs[s], r);
-            else if (n.type == 8)
-                rc = dec_parse_pps(hs[s], r);
-            if (rc) return rc;
-        }
-        if (!hs[s].have_sps || !hs[s].have_pps) return FERHIP_E_ARG;
-        if (hs[s].W != hs[0].W || hs[s].H != hs[0].H) return FERHIP_E_ARG;
-    }
-    if (W_out) *W_out = hs[0].W;
-    if (H_out) *H_out = hs[0].H;
-    const double t_split = dec_now();
-    // the slice NALs of every stream, in order
-    std::vector<std::vector<const NalRef *>> slices(S);
-    size_t T = 0;
-    for (int s = 0; s < S; s++) {
-        for (auto &n : nals[s])
-            if (n.type == 1 || n.type == 5) slices[s].push_back(&n);
-        T = std::max(T, slices[s].size());
-        pictures[s] = 0;
-    }
-    if (max_pictures > 0) T = std::min(T, (size_t)max_pictures);
-    for (int s = 0; s < S; s++)
-        if (slices[s].size() > T) slices[s].resize(T);
-    DecSession ss;
-    int rc = dec_session_open(ss, hs[0].W, hs[0].H, S, T, true);
-    if (rc) return rc;
-    ss.hs = hs;
-    const double t_open = dec_now();
-    // Slice data is bit-serial, so the parser's parallelism is pictures: a window of TW pictures of all streams is
-    // parsed by one launch (one wavefront each), then reconstructed picture by picture.
-    for (size_t t0 = 0; t0 < T && rc == 0; t0 += ss.TWmax) rc = dec_session_window(ss, slices, t0, std::min(ss.TWmax, T - t0), out, pictures);
-    if (verbose)
-        fprintf(stderr, "ferhip_decode_streams: %d streams, %zu pictures, window %zu: split %.3f s, context + buffers %.3f s, "
-                        "pack+H2D %.3f s, parse %.3f s, reconstruction %.3f s\n", S, T, ss.TWmax, t_split - t_start, t_open - t_split,
-                ss.t_pack, ss.t_parse, ss.t_recon);
-#ifdef FER_PROBE
-    {
-        long long tm[64];
-        hipDeviceSynchronize();
-        hipMemcpy(tm, ss.c->d.timing, sizeof tm, hipMemcpyDeviceToHost);
-        double n = tm[52] > 0 ? (double)tm[52] : 1.0;
-        fprintf(stderr, "k_dec_parse stream 0: %lld MBs, us per MB: header %.2f residual %.2f tail %.2f skip/loop %.2f\n", tm[52],
-                tm[48] / n / 100, tm[49] / n / 100, tm[50] / n / 100, tm[51] / n / 100);
-    }
-#endif
-    const double t_free0 = dec_now();
-    dec_session_close(ss);
-    if (verbose) fprintf(stderr, "ferhip_decode_streams: release %.3f s, total %.3f s\n", dec_now() - t_free0, dec_now() - t_start);
-    return rc;
-}
-
-// ---- streaming decoder: RBSP_decode(NALunit) of F/rbsp_decoding.cpp:17 for one stream, NAL unit by NAL unit ----
-struct ferhip_dec {
-    DecSession ss;
-    DecHdr h{};
-    bool open = false;
-    int pictures = 0;
-};
-
-extern "C" int ferhip_dec_create(ferhip_dec **out)
-{
-    if (!out) return FERHIP_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        fprintf(stderr, "ferhip: no HIP device; the hot path has no CPU fallback\n");
-        return FERHIP_E_HIP;
-    }
-    *out = new ferhip_dec();
-    return 0;
-}
-
-extern "C" void ferhip_dec_destroy(ferhip_dec *dc)
-{
-    if (!dc) return;
-    if (dc->open) dec_session_close(dc->ss);
-    delete dc;
-}
-
-extern "C" int ferhip_dec_nal(ferhip_dec *dc, int nal_unit_type, int nal_ref_idc, const uint8_t *rbsp, size_t n, uint8_t *picture,
-                              int *got_picture, int *width, int *height)
-{
-    if (!dc || !rbsp || n == 0) return FERHIP_E_ARG;
-    if (got_picture) *got_picture = 0;
-    HostBR r{rbsp, n, 0};
-    if (nal_unit_type == 7) {  // fill_sps + init_h264_structures + AllocateMemory
-        DecHdr hn = dc->h;
-        int rc = dec_parse_sps(hn, r);
-        if (rc) return rc;
-        if (dc->open && (hn.W != dc->h.W || hn.H != dc->h.H)) {
-            dec_session_close(dc->ss);
-            dc->open = false;
-        }
-        dc->h = hn;
-        if (!dc->open) {
-            dc->ss = DecSession();
-            rc = dec_session_open(dc->ss, hn.W, hn.H, 1, 1, false);
-            if (rc) return rc;
-            dc->open = true;
-        }
-    } else if (nal_unit_type == 8) {
-        int rc = dec_parse_pps(dc->h, r);
-        if (rc) return rc;
-    } else if (nal_unit_type == 5 || nal_unit_type == 1) {
-        if (!dc->open) return FERHIP_E_STATE;
-        (void)hipSetDevice(dc->ss.c->device);
-        dc->ss.hs[0] = dc->h;
-        NalRef nal;
-        nal.type = nal_unit_type;
-        nal.ref_idc = nal_ref_idc;
-        nal.rbsp.p = rbsp;
-        nal.rbsp.n = n;
-        std::vector<std::vector<const NalRef *>> slices(1);
-        slices[0].push_back(&nal);
-        int rc = dec_session_window(dc->ss, slices, 0, 1, picture, nullptr);
-        if (rc) return rc;
-        dc->h = dc->ss.hs[0];  // the slice header leaves state behind (reference count override, list modification)
-        dc->pictures++;
-        if (got_picture) *got_picture = 1;
-    }  // every other NAL unit type (SEI, AUD ...) is ignored, as in the reference
-    if (width) *width = dc->h.W;
-    if (height) *height = dc->h.H;
-    return 0;
-}
-
-// ---- live decoder: S streams that arrive piece by piece, one window of all of them per call ----
-struct ferhip_decs {
-    DecSession ss;
-    int S = 0, W = 0, H = 0, P = 0;
-    std::vector<std::vector<uint8_t>> store;  // RBSP of each stream's chunk (kept between calls)
-    std::vector<std::vector<NalRef>> nals;
-    std::vector<size_t> cursor;               // next NAL unit of each stream's chunk
-    std::vector<int> queued;                  // slice NAL units taken from each stream's chunk in this call
-    std::vector<char> need_idr;               // after a fault: P slices are refused until an IDR slice
-    DecIsolate iso;
-};
-
-// Stream s back to the state of a new decoder; forget_ps = also forget its parameter sets, else keep them and refuse
-// P slices until the next IDR slice
-static int decs_reset(ferhip_decs *d, int s, bool forget_ps)
-{
-    ferhip_ctx *c = d->ss.c;
-    const FerDev &dv = c->d;
-    const size_t S = (size_t)d->S;
-    hipError_t e = hipMemsetAsync(dv.dec_state + s * 4, 0, 4 * sizeof(int), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.dec_cac + s * 128, 0, 128 * sizeof(int16_t), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.status + s, 0, sizeof(int), c->st);
-    const size_t off[3] = {(size_t)s * dv.ysz, S * dv.ysz + (size_t)s * dv.csz, S * (dv.ysz + dv.csz) + (size_t)s * dv.csz};
-    const size_t len[3] = {dv.ysz, dv.csz, dv.csz};
-    for (int set = 0; set < 2; set++)
-        for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMemsetAsync(c->planes[set] + off[k], 0, len[k], c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) return FERHIP_E_HIP;
-    d->ss.held[s] = 0;
-    DecHdr &h = d->ss.hs[s];
-    if (forget_ps) {
-        h = DecHdr{};
-    } else {
-        h.nref_active_minus1 = h.mod_flag = h.mod_copies = 0;
-    }
-    d->need_idr[s] = !forget_ps;
-    return 0;
-}
-
-extern "C" int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, int height, int max_pictures)
-{
-    if (!out) return FERHIP_E_ARG;
-    *out = nullptr;
-    if (nstreams <= 0 || width <= 0 || height <= 0 || width % 16 || height % 16 || max_pictures <= 0) return FERHIP_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        fprintf(stderr, "ferhip: no HIP device; the hot path has no CPU fallback\n");
-        return FERHIP_E_HIP;
-    }
-    ferhip_decs *d = new ferhip_decs();
-    int rc = dec_session_open(d->ss, width, height, nstreams, (size_t)max_pictures, false);
-    if (rc) {
-        delete d;
-        return rc;
-    }
-    d->S = nstreams;
-    d->W = width;
-    d->H = height;
-    d->P = max_pictures;
-    d->store.resize(nstreams);
-    d->nals.resize(nstreams);
-    d->cursor.assign(nstreams, 0);
-    d->queued.assign(nstreams, 0);
-    d->need_idr.assign(nstreams, 0);
-    if (hipMalloc((void **)&d->iso.d_map, d->ss.TWmax * nstreams * sizeof(int2)) != hipSuccess) {
-        ferhip_decs_destroy(d);
-        return FERHIP_E_HIP;
-    }
-    *out = d;
-    return 0;
-}
-
-extern "C" void ferhip_decs_destroy(ferhip_decs *d)
-{
-    if (!d) return;
-    if (d->ss.c) {
-        (void)hipSetDevice(d->ss.c->device);
-        hipStreamSynchronize(d->ss.c->st);
-    }
-    if (d->iso.d_map) hipFree(d->iso.d_map);
-    if (d->iso.d_stage) hipFree(d->iso.d_stage);
-    if (d->iso.h_stage) hipHostFree(d->iso.h_stage);
-    dec_session_close(d->ss);
-    delete d;
-}
-
-extern "C" int ferhip_decs_reset_stream(ferhip_decs *d, int s)
-{
-    if (!d || s < 0 || s >= d->S) return FERHIP_E_ARG;
-    (void)hipSetDevice(d->ss.c->device);
-    return decs_reset(d, s, true);
-}
-
-// Take stream s's next NAL units up to the first parameter set that follows a slice (that one belongs to the next
-// window: a slice is parsed with the parameter sets that precede it), appending its slices to `slices`.
-static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices, int *status)
-{
-    DecHdr &h = d->ss.hs[s];
-    std::vector<NalRef> &nals = d->nals[s];
-    for (size_t &i = d->cursor[s]; i < nals.size() && !status[s]; i++) {
-        const NalRef &n = nals[i];
-        HostBR r{n.rbsp.data(), n.rbsp.size(), 0};
-        if (n.type == 7 || n.type == 8) {
-            if (!slices.empty()) return;
-            DecHdr hn = h;
-            int rc = n.type == 7 ? dec_parse_sps(hn, r) : dec_parse_pps(hn, r);
-            if (!rc && n.type == 7 && (hn.W != d->W || hn.H != d->H)) rc = FERHIP_E_UNSUP;  // one picture size per decoder
-            if (rc)
-                status[s] = rc;
-            else
-                h = hn;
-        } else if (n.type == 1 || n.type == 5) {
-            if (!h.have_sps || !h.have_pps || (n.type == 1 && d->need_idr[s]))
-                status[s] = FERHIP_E_STATE;
-            else if (d->queued[s] >= d->P)
-                status[s] = FERHIP_E_ARG;
-            else {
-                slices.push_back(&n);
-                d->queued[s]++;
-                if (n.type == 5) d->need_idr[s] = 0;
-            }
-        }  // every other NAL unit type (SEI, AUD ...) is ignored, as in the reference
-    }
-}
-
-extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
-                                  int *pictures, int *status)
-{
-    if (!d || !chunks || !lens || !pictures || !status) return FERHIP_E_ARG;
-    const int S = d->S;
-    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
-    size_t bytes = 0;
-    for (int s = 0; s < S; s++) {
-        pictures[s] = status[s] = 0;
-        d->nals[s].clear();
-        d->cursor[s] = 0;
-        d->queued[s] = 0;
-        if (chunks[s] && lens[s]) bytes += lens[s];
-    }
-    {  // NAL splitting: a few threads when there is much of it
-        const int nth = bytes < ((size_t)1 << 20) ? 1 : std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
-        auto split = [&](int k) {
-            for (int s = k; s < S; s += nth)
-                if (chunks[s] && lens[s]) split_stream(chunks[s], lens[s], d->nals[s], d->store[s]);
-        };
-        if (nth == 1) {
-            split(0);
-        } else {
-            std::vector<std::thread> th;
-            for (int k = 0; k < nth; k++) th.emplace_back(split, k);
-            for (auto &x : th) x.join();
-        }
-    }
-    d->iso.status = status;
-    d->iso.stop.assign(S, 0);
-    d->iso.out = out;
-    d->iso.out_dev = out_on_device != 0;
-    std::vector<std::vector<const NalRef *>> slices(S);
-    int rc = 0;
-    for (;;) {  // one window per call, unless a chunk carries a parameter set behind one of its slices
-        size_t T = 0;
-        for (int s = 0; s < S; s++) {
-            slices[s].clear();
-            decs_take(d, s, slices[s], status);
-            T = std::max(T, slices[s].size());
-        }
-        if (T == 0) break;
-        for (size_t t0 = 0; t0 < T && !rc; t0 += d->ss.TWmax) rc = dec_session_window(d->ss, slices, t0, std::min(d->ss.TWmax, T - t0), nullptr, pictures, &d->iso);
-        if (rc) break;
-    }
-    for (int s = 0; s < S && !rc; s++)
-        if (status[s]) rc = decs_reset(d, s, false);
-    return rc;
-}
-
-// ---- block-level KATs: the reference's per-block entry points (F/quantizationTransform.h, F/scaleTransform.h) as
-// batched device calls over the SAME device functions the production kernels use (fer_dev.h)
-#define KAT_FWD_RESIDUAL 0
-#define KAT_INV_RESIDUAL 1
-#define KAT_FWD_DC_LUMA 2
-#define KAT_INV_DC_LUMA 3
-#define KAT_FWD_DC_CHROMA 4
-#define KAT_INV_DC_CHROMA 5
-#define KAT_SCAN 6
-#define KAT_INV_SCAN 7
-__global__ void k_block_kat(int op, int qP, const int32_t *in, int32_t *out, int flag, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int a[16], t[16], b[16];
-    for (int k = 0; k < 16; k++) {
-        a[k] = in[i * 16 + k];
-        b[k] = 0;
-    }
-    switch (op) {
-    case KAT_FWD_RESIDUAL:
-        fwd4x4(a, t);
-        quant4x4(t, b, qP, flag != 0);
-        break;
-    case KAT_INV_RESIDUAL: inv4x4(a, b, qP, flag != 0); break;
-    case KAT_FWD_DC_LUMA: fwd_dc_luma(a, b, qP); break;
-    case KAT_INV_DC_LUMA: inv_dc_luma(a, b, qP); break;
-    case KAT_FWD_DC_CHROMA: fwd_dc_chroma(a, b, qP); break;   // 2x2 raster in slots 0..3
-    case KAT_INV_DC_CHROMA: inv_dc_chroma(a, b, qP); break;
-    case KAT_SCAN:  // transformScan: flag = Intra16x16AC (15 entries from index 1)
-        for (int k = flag ? 1 : 0; k < 16; k++) b[k - (flag ? 1 : 0)] = a[c_zz[k]];
-        break;
-    default:  // transformInverseScan
-        for (int k = 0; k < 16; k++) b[c_zz[k]] = a[k];
-        break;
-    }
-    for (int k = 0; k < 16; k++) out[i * 16 + k] = b[k];
-}
-
-static int block_kat(int op, int qP, const int32_t *in, int32_t *out, int flag, size_t n)
-{
-    if (!in || !out || qP < 0 || qP > 51) return FERHIP_E_ARG;
-    if (n == 0) return 0;
-    int32_t *di = nullptr, *dout = nullptr;
-    CK(hipMalloc((void **)&di, n * 64));
-    if (hipMalloc((void **)&dout, n * 64) != hipSuccess) {
-        hipFree(di);
-        return FERHIP_E_HIP;
-    }
-    int rc = 0;
-    if (hipMemcpy(di, in, n * 64, hipMemcpyHostToDevice) != hipSuccess) rc = FERHIP_E_HIP;
-    if (!rc) {
-        hipLaunchKernelGGL(k_block_kat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, qP, di, dout, flag, n);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, n * 64, hipMemcpyDeviceToHost) != hipSuccess) rc = FERHIP_E_HIP;
-    }
-    hipFree(di);
-    hipFree(dout);
-    return rc;
-}
-
-extern "C" int ferhip_forward_residual(int qP, const int32_t *in, int32_t *out, int keep_dc, size_t n)
-{
-    return block_kat(KAT_FWD_RESIDUAL, qP, in, out, keep_dc, n);
-}
-extern "C" int ferhip_inverse_residual(int qP, const int32_t *in, int32_t *out, int keep_dc, size_t n)
-{
-    return block_kat(KAT_INV_RESIDUAL, qP, in, out, keep_dc, n);
-}
-extern "C" int ferhip_forward_dc_luma_intra(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_FWD_DC_LUMA, qP, in, out, 0, n); }
-extern "C" int ferhip_inverse_dc_luma_intra(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_INV_DC_LUMA, qP, in, out, 0, n); }
-extern "C" int ferhip_forward_dc_chroma(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_FWD_DC_CHROMA, qP, in, out, 0, n); }
-extern "C" int ferhip_inverse_dc_chroma(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_INV_DC_CHROMA, qP, in, out, 0, n); }
-extern "C" int ferhip_transform_scan(const int32_t *in, int32_t *out, int intra16x16_ac, size_t n) { return block_kat(KAT_SCAN, 0, in, out, intra16x16_ac, n); }
-extern "C" int ferhip_transform_inverse_scan(const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_INV_SCAN, 0, in, out, 0, n); }

@@ -36,29 +36,6 @@ int fer_quality_groups(const FerDev &d);
 void fer_launch_quality(const FerDev &d, int flags, int slot, hipStream_t st);
 void fer_launch_carry_ref(const FerDev &d, hipStream_t st);
 void fer_launch_reset_stream(const FerDev &d, int s, int qpw, hipStream_t st);
-// Annex-B framing on the device (fer_nalpack.hip): n payloads, payload s = lens[s] bytes at src + s * src_stride (16-byte
-// aligned, every slot readable up to its length rounded up to 16).  hdr != null: an encoder context's slice headers say
-// which payloads are there and give the NAL unit type; else types[n] does and every payload is there.  ps (optional):
-// [n][FER_NAL_PS_ROW] framed SPS + PPS of every payload, the row's last byte = their length; they go in front of IDR units.
-#define FER_NAL_PS_ROW 64
-struct FerNalJob {
-    const uint8_t *src;
-    size_t src_stride;
-    const uint32_t *lens;
-    const uint32_t *hdr;
-    const int32_t *types;
-    const uint8_t *ps;
-    int n, nchmax;       // payloads; 4096-byte chunks a payload can have (the pitch of summ and cin)
-    uint4 *summ;         // [n][nchmax] what each chunk does to writeNAL's counter (k_nal_count)
-    uint2 *cin;          // [n][nchmax] each chunk's incoming counter and the 03 bytes in front of it (k_nal_plan)
-    uint2 *ent;          // [n] entry size, NAL unit type
-    ferhip_au *index;    // [n + 1] device
-    uint8_t *dst;
-    unsigned long long cap;
-};
-void fer_launch_nal_plan(const FerNalJob &j, hipStream_t st);
-void fer_launch_nal_emit(const FerNalJob &j, hipStream_t st);
-void fer_launch_block_kat(int qP, const int32_t *in, int32_t *out, int keep_dc, int inverse, size_t n, hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);
 // map[j] = (stream, slot): picture of stream map[j].x in `set` -> dst + map[j].y * W*H*3/2 (I420), for j < n

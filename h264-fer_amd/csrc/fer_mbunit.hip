@@ -8,22 +8,10 @@
 //   transformDecodingP_Skip                     F/inttransform.cpp:215-231            MBU_SKIP
 //   residual_block_cavlc_write / _size          F/residual.cpp:374-666 / :673-957     k_cavlc_blocks
 //   MotionCompensateSubMBPart                   F/mocomp.cpp:152-195                  k_mc_parts
+//   forward / inverse residual, DC, scan        F/quantizationTransform.h, scaleTransform.h  k_block_kat
 // Not a fast path: one wavefront per job, records of plain int32.  The legacy-name shims are in fer_legacy.hip.
-#include "../../include/ferhip.h"
 #include "fer_cavlc_dev.h"
-#include "fer_internal.h"
-#include <stdio.h>
-#include <vector>
-
-#define CKU(x)                                                                                         \
-    do {                                                                                               \
-        hipError_t e_ = (x);                                                                           \
-        if (e_ != hipSuccess) {                                                                        \
-            fprintf(stderr, "ferhip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = FERHIP_E_HIP;                                                                         \
-            goto done;                                                                                 \
-        }                                                                                              \
-    } while (0)
+#include "fer_ctx.h"
 
 // list[k] = c[zig-zag k] (transformScan, F/quantizationTransform.cpp:310-325); the Intra16x16AC / chroma AC form drops the DC
 __device__ __forceinline__ void mbu_scan(const int c[16], int32_t *list, bool ac)
@@ -195,19 +183,21 @@ __global__ __launch_bounds__(64) void k_mb_unit(const ferhip_mb_job *jobs, ferhi
 extern "C" int ferhip_mb_unit(const ferhip_mb_job *jobs, ferhip_mb_result *results, size_t n)
 {
     if (!jobs || !results || n == 0) return FERHIP_E_ARG;
-    int rc = 0;
     ferhip_mb_job *dj = nullptr;
     ferhip_mb_result *dr = nullptr;
-    CKU(hipMalloc((void **)&dj, n * sizeof *dj));
-    CKU(hipMalloc((void **)&dr, n * sizeof *dr));
-    CKU(hipMemcpy(dj, jobs, n * sizeof *dj, hipMemcpyHostToDevice));
-    CKU(hipMemset(dr, 0, n * sizeof *dr));
-    hipLaunchKernelGGL(k_mb_unit, dim3((unsigned)n), dim3(64), 0, 0, dj, dr, (int)n);
-    CKU(hipGetLastError());
-    CKU(hipMemcpy(results, dr, n * sizeof *dr, hipMemcpyDeviceToHost));
-done:
-    if (dj) hipFree(dj);
-    if (dr) hipFree(dr);
+    auto body = [&]() -> int {
+        CK(hipMalloc((void **)&dj, n * sizeof *dj));
+        CK(hipMalloc((void **)&dr, n * sizeof *dr));
+        CK(hipMemcpy(dj, jobs, n * sizeof *dj, hipMemcpyHostToDevice));
+        CK(hipMemset(dr, 0, n * sizeof *dr));
+        hipLaunchKernelGGL(k_mb_unit, dim3((unsigned)n), dim3(64), 0, 0, dj, dr, (int)n);
+        CK(hipGetLastError());
+        CK(hipMemcpy(results, dr, n * sizeof *dr, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = body();
+    hipFree(dj);
+    hipFree(dr);
     return rc;
 }
 
@@ -243,34 +233,35 @@ extern "C" int ferhip_cavlc_blocks(const int32_t *coef, const int32_t *nC, const
                                    uint32_t *nbits, int32_t *total_coeff)
 {
     if (!coef || !nC || !max_num_coeff || !bits || !nbits || !total_coeff || n == 0) return FERHIP_E_ARG;
-    int rc = 0;
     int32_t *dc = nullptr, *dn = nullptr, *dm = nullptr, *dt = nullptr;
     uint32_t *db = nullptr, *dl = nullptr, *ds = nullptr;
     std::vector<uint32_t> sz(n);
-    CKU(hipMalloc((void **)&dc, n * 64));
-    CKU(hipMalloc((void **)&dn, n * 4));
-    CKU(hipMalloc((void **)&dm, n * 4));
-    CKU(hipMalloc((void **)&dt, n * 4));
-    CKU(hipMalloc((void **)&db, n * 64));
-    CKU(hipMalloc((void **)&dl, n * 4));
-    CKU(hipMalloc((void **)&ds, n * 4));
-    CKU(hipMemcpy(dc, coef, n * 64, hipMemcpyHostToDevice));
-    CKU(hipMemcpy(dn, nC, n * 4, hipMemcpyHostToDevice));
-    CKU(hipMemcpy(dm, max_num_coeff, n * 4, hipMemcpyHostToDevice));
-    CKU(hipMemset(db, 0, n * 64));
-    hipLaunchKernelGGL(k_cavlc_blocks, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, dc, dn, dm, (int)n, db, dl, dt, ds);
-    CKU(hipGetLastError());
-    CKU(hipMemcpy(bits, db, n * 64, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(nbits, dl, n * 4, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(total_coeff, dt, n * 4, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(sz.data(), ds, n * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++)
-        if (sz[i] != nbits[i]) {
-            fprintf(stderr, "ferhip_cavlc_blocks: block %zu: the counting form gives %u bits, the writer %u\n", i, sz[i], nbits[i]);
-            rc = FERHIP_E_DEVICE;
-            break;
-        }
-done:
+    auto body = [&]() -> int {
+        CK(hipMalloc((void **)&dc, n * 64));
+        CK(hipMalloc((void **)&dn, n * 4));
+        CK(hipMalloc((void **)&dm, n * 4));
+        CK(hipMalloc((void **)&dt, n * 4));
+        CK(hipMalloc((void **)&db, n * 64));
+        CK(hipMalloc((void **)&dl, n * 4));
+        CK(hipMalloc((void **)&ds, n * 4));
+        CK(hipMemcpy(dc, coef, n * 64, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dn, nC, n * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dm, max_num_coeff, n * 4, hipMemcpyHostToDevice));
+        CK(hipMemset(db, 0, n * 64));
+        hipLaunchKernelGGL(k_cavlc_blocks, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, dc, dn, dm, (int)n, db, dl, dt, ds);
+        CK(hipGetLastError());
+        CK(hipMemcpy(bits, db, n * 64, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(nbits, dl, n * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(total_coeff, dt, n * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(sz.data(), ds, n * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++)
+            if (sz[i] != nbits[i]) {
+                fprintf(stderr, "ferhip_cavlc_blocks: block %zu: the counting form gives %u bits, the writer %u\n", i, sz[i], nbits[i]);
+                return FERHIP_E_DEVICE;
+            }
+        return 0;
+    };
+    const int rc = body();
     hipFree(dc);
     hipFree(dn);
     hipFree(dm);
@@ -320,34 +311,35 @@ extern "C" int ferhip_mc_sub_mb_parts(const uint8_t *ref_i420, int width, int he
 {
     if (!ref_i420 || !desc || !predL || !predCb || !predCr || n == 0 || width <= 0 || height <= 0 || (width & 15) || (height & 15))
         return FERHIP_E_ARG;
-    int rc = 0;
     const size_t fsz = (size_t)width * height * 3 / 2;
     uint8_t *dref = nullptr;
     int32_t *dd = nullptr, *dl = nullptr, *db = nullptr, *dr = nullptr, *rb = nullptr, *rr = nullptr;
     std::vector<int32_t> hb(n * 4), hr(n * 4);
-    CKU(hipMalloc((void **)&dref, fsz + 256));
-    CKU(hipMalloc((void **)&dd, n * 20));
-    CKU(hipMalloc((void **)&dl, n * 64));
-    CKU(hipMalloc((void **)&db, n * 16));
-    CKU(hipMalloc((void **)&dr, n * 16));
-    CKU(hipMalloc((void **)&rb, n * 16));
-    CKU(hipMalloc((void **)&rr, n * 16));
-    CKU(hipMemcpy(dref, ref_i420, fsz, hipMemcpyHostToDevice));
-    CKU(hipMemcpy(dd, desc, n * 20, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mc_parts, dim3((unsigned)n), dim3(64), 0, 0, dref, width, height, dd, (int)n, dl, db, dr, rb, rr);
-    CKU(hipGetLastError());
-    CKU(hipMemcpy(predL, dl, n * 64, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(predCb, db, n * 16, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(predCr, dr, n * 16, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(hb.data(), rb, n * 16, hipMemcpyDeviceToHost));
-    CKU(hipMemcpy(hr.data(), rr, n * 16, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n * 4; i++)
-        if (hb[i] != predCb[i] || hr[i] != predCr[i]) {
-            fprintf(stderr, "ferhip_mc_sub_mb_parts: the row form of the chroma interpolation differs at sub-block %zu\n", i / 4);
-            rc = FERHIP_E_DEVICE;
-            break;
-        }
-done:
+    auto body = [&]() -> int {
+        CK(hipMalloc((void **)&dref, fsz + 256));
+        CK(hipMalloc((void **)&dd, n * 20));
+        CK(hipMalloc((void **)&dl, n * 64));
+        CK(hipMalloc((void **)&db, n * 16));
+        CK(hipMalloc((void **)&dr, n * 16));
+        CK(hipMalloc((void **)&rb, n * 16));
+        CK(hipMalloc((void **)&rr, n * 16));
+        CK(hipMemcpy(dref, ref_i420, fsz, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dd, desc, n * 20, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_mc_parts, dim3((unsigned)n), dim3(64), 0, 0, dref, width, height, dd, (int)n, dl, db, dr, rb, rr);
+        CK(hipGetLastError());
+        CK(hipMemcpy(predL, dl, n * 64, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(predCb, db, n * 16, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(predCr, dr, n * 16, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(hb.data(), rb, n * 16, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(hr.data(), rr, n * 16, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n * 4; i++)
+            if (hb[i] != predCb[i] || hr[i] != predCr[i]) {
+                fprintf(stderr, "ferhip_mc_sub_mb_parts: the row form of the chroma interpolation differs at sub-block %zu\n", i / 4);
+                return FERHIP_E_DEVICE;
+            }
+        return 0;
+    };
+    const int rc = body();
     hipFree(dref);
     hipFree(dd);
     hipFree(dl);
@@ -357,3 +349,78 @@ done:
     hipFree(rr);
     return rc;
 }
+
+// ---- block-level KATs: the reference's per-block entry points (F/quantizationTransform.h, F/scaleTransform.h) as
+// batched device calls over the SAME device functions the production kernels use (fer_dev.h)
+#define KAT_FWD_RESIDUAL 0
+#define KAT_INV_RESIDUAL 1
+#define KAT_FWD_DC_LUMA 2
+#define KAT_INV_DC_LUMA 3
+#define KAT_FWD_DC_CHROMA 4
+#define KAT_INV_DC_CHROMA 5
+#define KAT_SCAN 6
+#define KAT_INV_SCAN 7
+__global__ void k_block_kat(int op, int qP, const int32_t *in, int32_t *out, int flag, size_t n)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int a[16], t[16], b[16];
+    for (int k = 0; k < 16; k++) {
+        a[k] = in[i * 16 + k];
+        b[k] = 0;
+    }
+    switch (op) {
+    case KAT_FWD_RESIDUAL:
+        fwd4x4(a, t);
+        quant4x4(t, b, qP, flag != 0);
+        break;
+    case KAT_INV_RESIDUAL: inv4x4(a, b, qP, flag != 0); break;
+    case KAT_FWD_DC_LUMA: fwd_dc_luma(a, b, qP); break;
+    case KAT_INV_DC_LUMA: inv_dc_luma(a, b, qP); break;
+    case KAT_FWD_DC_CHROMA: fwd_dc_chroma(a, b, qP); break;   // 2x2 raster in slots 0..3
+    case KAT_INV_DC_CHROMA: inv_dc_chroma(a, b, qP); break;
+    case KAT_SCAN:  // transformScan: flag = Intra16x16AC (15 entries from index 1)
+        for (int k = flag ? 1 : 0; k < 16; k++) b[k - (flag ? 1 : 0)] = a[c_zz[k]];
+        break;
+    default:  // transformInverseScan
+        for (int k = 0; k < 16; k++) b[c_zz[k]] = a[k];
+        break;
+    }
+    for (int k = 0; k < 16; k++) out[i * 16 + k] = b[k];
+}
+
+static int block_kat(int op, int qP, const int32_t *in, int32_t *out, int flag, size_t n)
+{
+    if (!in || !out || qP < 0 || qP > 51) return FERHIP_E_ARG;
+    if (n == 0) return 0;
+    int32_t *di = nullptr, *dout = nullptr;
+    CK(hipMalloc((void **)&di, n * 64));
+    if (hipMalloc((void **)&dout, n * 64) != hipSuccess) {
+        hipFree(di);
+        return FERHIP_E_HIP;
+    }
+    int rc = 0;
+    if (hipMemcpy(di, in, n * 64, hipMemcpyHostToDevice) != hipSuccess) rc = FERHIP_E_HIP;
+    if (!rc) {
+        hipLaunchKernelGGL(k_block_kat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, qP, di, dout, flag, n);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, n * 64, hipMemcpyDeviceToHost) != hipSuccess) rc = FERHIP_E_HIP;
+    }
+    hipFree(di);
+    hipFree(dout);
+    return rc;
+}
+
+extern "C" int ferhip_forward_residual(int qP, const int32_t *in, int32_t *out, int keep_dc, size_t n)
+{
+    return block_kat(KAT_FWD_RESIDUAL, qP, in, out, keep_dc, n);
+}
+extern "C" int ferhip_inverse_residual(int qP, const int32_t *in, int32_t *out, int keep_dc, size_t n)
+{
+    return block_kat(KAT_INV_RESIDUAL, qP, in, out, keep_dc, n);
+}
+extern "C" int ferhip_forward_dc_luma_intra(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_FWD_DC_LUMA, qP, in, out, 0, n); }
+extern "C" int ferhip_inverse_dc_luma_intra(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_INV_DC_LUMA, qP, in, out, 0, n); }
+extern "C" int ferhip_forward_dc_chroma(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_FWD_DC_CHROMA, qP, in, out, 0, n); }
+extern "C" int ferhip_inverse_dc_chroma(int qP, const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_INV_DC_CHROMA, qP, in, out, 0, n); }
+extern "C" int ferhip_transform_scan(const int32_t *in, int32_t *out, int intra16x16_ac, size_t n) { return block_kat(KAT_SCAN, 0, in, out, intra16x16_ac, n); }
+extern "C" int ferhip_transform_inverse_scan(const int32_t *in, int32_t *out, size_t n) { return block_kat(KAT_INV_SCAN, 0, in, out, 0, n); }

@@ -20,8 +20,31 @@
 //                neighbouring chunk and are stored byte-wise.  Chunk 0 also places the parameter sets (where asked for),
 //                the start code and the header byte.  An entry is written only if its 16-byte slots end within `cap`.
 // No workgroup waits for another one: the phases are separate launches on one stream.
-#include "../../include/ferhip.h"
-#include "fer_internal.h"
+// The host side follows the kernels: the context's buffers and parameter set table, and the three entry points.
+#include "fer_ctx.h"
+#include <string.h>
+#include <algorithm>
+
+// One framing job: n payloads, payload s = lens[s] bytes at src + s * src_stride (16-byte
+// aligned, every slot readable up to its length rounded up to 16).  hdr != null: an encoder context's slice headers say
+// which payloads are there and give the NAL unit type; else types[n] does and every payload is there.  ps (optional):
+// [n][FER_NAL_PS_ROW] framed SPS + PPS of every payload, the row's last byte = their length; they go in front of IDR units.
+#define FER_NAL_PS_ROW 64
+struct FerNalJob {
+    const uint8_t *src;
+    size_t src_stride;
+    const uint32_t *lens;
+    const uint32_t *hdr;
+    const int32_t *types;
+    const uint8_t *ps;
+    int n, nchmax;       // payloads; 4096-byte chunks a payload can have (the pitch of summ and cin)
+    uint4 *summ;         // [n][nchmax] what each chunk does to writeNAL's counter (k_nal_count)
+    uint2 *cin;          // [n][nchmax] each chunk's incoming counter and the 03 bytes in front of it (k_nal_plan)
+    uint2 *ent;          // [n] entry size, NAL unit type
+    ferhip_au *index;    // [n + 1] device
+    uint8_t *dst;
+    unsigned long long cap;
+};
 
 #define NAL_THREADS 256
 #define NAL_CHUNK (NAL_THREADS * 16)
@@ -279,7 +302,7 @@ static unsigned nal_grid_x(const FerNalJob &j)
 }
 
 // count + plan: fills j.index (device) for the payloads of j; nothing of dst is touched
-void fer_launch_nal_plan(const FerNalJob &j, hipStream_t st)
+static void fer_launch_nal_plan(const FerNalJob &j, hipStream_t st)
 {
     hipLaunchKernelGGL(k_nal_count, dim3(nal_grid_x(j), j.n), dim3(NAL_THREADS), 0, st, j);
     hipLaunchKernelGGL(k_nal_plan, dim3(j.n), dim3(64), 0, st, j);
@@ -287,7 +310,208 @@ void fer_launch_nal_plan(const FerNalJob &j, hipStream_t st)
 }
 
 // writes every entry of j.index whose 16-byte slots end within j.cap
-void fer_launch_nal_emit(const FerNalJob &j, hipStream_t st)
+static void fer_launch_nal_emit(const FerNalJob &j, hipStream_t st)
 {
     hipLaunchKernelGGL(k_nal_emit, dim3(nal_grid_x(j), j.n), dim3(NAL_THREADS), 0, st, j);
+}
+
+// ---- host side: an encoder context's buffers, allocated on first use
+static int nal_alloc(ferhip_ctx *c)
+{
+    if (c->nal_nchmax) return 0;
+    FerDev &d = c->d;
+    const int nchmax = (int)((d.bits_cap_words * 4 + 4095) / 4096);
+    // the allocators keep what exists: a call after a failed one allocates only what is still missing
+    if (dalloc(c, &c->nal_summ, (size_t)d.S * nchmax) || dalloc(c, &c->nal_cin, (size_t)d.S * nchmax) || dalloc(c, &c->nal_ent, (size_t)d.S) ||
+        dalloc(c, &c->nal_index, (size_t)d.S + 1) || halloc(c, &c->h_nal_index, (size_t)d.S + 1) ||
+        hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
+        (void)hipGetLastError();
+        fprintf(stderr, "ferhip: could not allocate the NAL framing buffers\n");
+        return FERHIP_E_HIP;
+    }
+    c->nal_nchmax = nchmax;
+    return 0;
+}
+
+// FERHIP_AU_PARAM_SETS: the framed SPS + PPS of every stream in the device table.  Rows that can have changed are built
+// into the next slot of a pinned ring and sent from there on the context's stream.
+static int ps_refresh(ferhip_ctx *c)
+{
+    const int S = c->d.S;
+    if (c->ps_dirty.empty()) {
+        if (dalloc(c, &c->d_ps, (size_t)S * FER_NAL_PS_ROW) || hipDeviceSynchronize() != hipSuccess ||  // as in nal_alloc
+            c->ps_ring.create((size_t)S * FER_NAL_PS_ROW)) {
+            (void)hipGetLastError();
+            return FERHIP_E_HIP;
+        }
+        c->ps_dirty.assign(S, 1);
+    }
+    bool any = false;
+    for (int s = 0; s < S; s++) any |= c->ps_dirty[s] != 0;
+    if (!any) return 0;
+    uint8_t *slot = (uint8_t *)c->ps_ring.next();
+    if (!slot) return FERHIP_E_HIP;
+    for (int s = 0; s < S; s++) {
+        if (!c->ps_dirty[s]) continue;
+        uint8_t rbsp[64], nal[2 * (5 + 96)];
+        size_t n = ferhip_write_sps(c, rbsp, sizeof rbsp);
+        size_t m = ferhip_write_nal(1, 7, rbsp, n, nal);
+        n = ferhip_write_pps_stream(c, s, rbsp, sizeof rbsp);
+        m += ferhip_write_nal(1, 8, rbsp, n, nal + m);
+        if (m > FER_NAL_PS_ROW - 1) return FERHIP_E_UNSUP;
+        uint8_t *row = slot + (size_t)s * FER_NAL_PS_ROW;
+        memset(row, 0, FER_NAL_PS_ROW);
+        memcpy(row, nal, m);
+        row[FER_NAL_PS_ROW - 1] = (uint8_t)m;
+    }
+    for (int s = 0; s < S;) {  // one copy per run of rows
+        if (!c->ps_dirty[s]) {
+            s++;
+            continue;
+        }
+        int e = s;
+        while (e < S && c->ps_dirty[e]) c->ps_dirty[e++] = 0;
+        CK(hipMemcpyAsync(c->d_ps + (size_t)s * FER_NAL_PS_ROW, slot + (size_t)s * FER_NAL_PS_ROW, (size_t)(e - s) * FER_NAL_PS_ROW,
+                          hipMemcpyHostToDevice, c->st));
+        s = e;
+    }
+    return c->ps_ring.sent(c->st);
+}
+
+static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
+{
+    if (!c->nal_ready) return FERHIP_E_STATE;
+    (void)hipSetDevice(c->device);
+    if (nal_alloc(c)) return FERHIP_E_HIP;
+    if (flags & FERHIP_AU_PARAM_SETS) {
+        int rc = ps_refresh(c);
+        if (rc) return rc;
+    }
+    FerDev &d = c->d;
+    j.src = (const uint8_t *)d.bits;
+    j.src_stride = d.bits_cap_words * 4;
+    j.lens = d.out_bytes;
+    j.hdr = d.hdr;
+    j.types = nullptr;
+    j.ps = (flags & FERHIP_AU_PARAM_SETS) ? c->d_ps : nullptr;
+    j.n = d.S;
+    j.nchmax = c->nal_nchmax;
+    j.summ = c->nal_summ;
+    j.cin = c->nal_cin;
+    j.ent = c->nal_ent;
+    j.index = c->nal_index;
+    j.dst = nullptr;
+    j.cap = 0;
+    return 0;
+}
+
+extern "C" int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap, ferhip_au *d_index)
+{
+    if (!c || !d_index || (flags & ~FERHIP_AU_PARAM_SETS) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_index & 7) || (!d_dst && cap))
+        return FERHIP_E_ARG;
+    FerNalJob j;
+    int rc = nal_prepare(c, flags, j);
+    if (rc) return rc;
+    j.index = d_index;
+    j.dst = (uint8_t *)d_dst;
+    j.cap = cap;
+    fer_launch_nal_plan(j, c->st);
+    fer_launch_nal_emit(j, c->st);
+    CK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_au *h_index)
+{
+    if (!c || !h_index || (flags & ~FERHIP_AU_PARAM_SETS) || (!h_dst && cap)) return FERHIP_E_ARG;
+    FerNalJob j;
+    int rc = nal_prepare(c, flags, j);
+    if (rc) return rc;
+    const int S = c->d.S;
+    j.cap = cap;
+    fer_launch_nal_plan(j, c->st);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(c->h_nal_index, c->nal_index, sizeof(ferhip_au) * (S + 1), hipMemcpyDeviceToHost, c->st));
+    CK(hipStreamSynchronize(c->st));
+    memcpy(h_index, c->h_nal_index, sizeof(ferhip_au) * (S + 1));
+    const size_t total = (size_t)c->h_nal_index[S].offset;
+    if (total > cap) return FERHIP_E_ARG;
+    if (total == 0) return 0;
+    if (c->nal_buf_cap < total) {
+        if (c->nal_buf) CK(hipFree(c->nal_buf));
+        c->nal_buf = nullptr;
+        c->nal_buf_cap = 0;
+        const size_t want = (total + total / 4 + 65535) & ~(size_t)65535;
+        CK(hipMalloc((void **)&c->nal_buf, want));
+        CK(hipMemsetAsync(c->nal_buf, 0, want, c->st));  // the bytes between entries are copied out too
+        c->nal_buf_cap = want;
+    }
+    j.dst = c->nal_buf;
+    j.cap = total;
+    fer_launch_nal_emit(j, c->st);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(h_dst, c->nal_buf, total, hipMemcpyDeviceToHost, c->st));
+    CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// known-answer surface: host payloads through the same kernels, on the null stream with buffers of its own
+extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
+                                       size_t n, uint8_t *out, size_t cap, ferhip_au *index)
+{
+    if (!lens || !nal_type || !index || n == 0 || n > 65535 || (!out && cap)) return FERHIP_E_ARG;
+    uint32_t maxlen = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (lens[i] > stride || (lens[i] && !payloads)) return FERHIP_E_ARG;
+        maxlen = std::max(maxlen, lens[i]);
+    }
+    const size_t pitch = std::max<size_t>(((size_t)maxlen + 15) & ~(size_t)15, 16);
+    const int nchmax = (int)std::max<size_t>(((size_t)maxlen + 4095) / 4096, 1);
+    uint8_t *src = nullptr, *dst = nullptr;
+    uint32_t *dl = nullptr;
+    int32_t *dt = nullptr;
+    uint4 *summ = nullptr;
+    uint2 *cin = nullptr, *ent = nullptr;
+    ferhip_au *idx = nullptr;
+    auto body = [&]() -> int {
+        CK(hipMalloc((void **)&src, pitch * n));
+        CK(hipMalloc((void **)&dst, std::max<size_t>(cap, 16)));
+        CK(hipMalloc((void **)&dl, sizeof(uint32_t) * n));
+        CK(hipMalloc((void **)&dt, sizeof(int32_t) * n));
+        CK(hipMalloc((void **)&summ, sizeof(uint4) * n * nchmax));
+        CK(hipMalloc((void **)&cin, sizeof(uint2) * n * nchmax));
+        CK(hipMalloc((void **)&ent, sizeof(uint2) * n));
+        CK(hipMalloc((void **)&idx, sizeof(ferhip_au) * (n + 1)));
+        CK(hipMemset(src, 0, pitch * n));
+        if (maxlen) CK(hipMemcpy2D(src, pitch, payloads, stride, maxlen, n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dl, lens, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dt, nal_type, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+        if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
+        FerNalJob j;
+        j.src = src;
+        j.src_stride = pitch;
+        j.lens = dl;
+        j.hdr = nullptr;
+        j.types = dt;
+        j.ps = nullptr;
+        j.n = (int)n;
+        j.nchmax = nchmax;
+        j.summ = summ;
+        j.cin = cin;
+        j.ent = ent;
+        j.index = idx;
+        j.dst = dst;
+        j.cap = cap;
+        fer_launch_nal_plan(j, nullptr);
+        fer_launch_nal_emit(j, nullptr);
+        CK(hipGetLastError());
+        CK(hipDeviceSynchronize());
+        if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(index, idx, sizeof(ferhip_au) * (n + 1), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = body();
+    for (void *p : {(void *)src, (void *)dst, (void *)dl, (void *)dt, (void *)summ, (void *)cin, (void *)ent, (void *)idx})
+        if (p) hipFree(p);
+    return rc;
 }
