@@ -3,7 +3,7 @@
 // header (F/headers_and_parameter_sets.cpp:245-298,398-537) -- a few dozen bits per NAL -- then windows of pictures through
 // the device's macroblock loop (fer_decode.hip).  ferhip_decode_streams, the streaming decoder (ferhip_dec_*) and the
 // live decoder with per-stream fault isolation (ferhip_decs_*) share one session type over a decode-only context.
-#include "fer_ctx.h"
+#include "fer_nalsplit.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -172,6 +172,10 @@ struct ByteView {  // bytes owned elsewhere: a stream's RBSP store (split_stream
 struct NalRef {
     int type, ref_idc;
     ByteView rbsp;
+    // a unit the device splitter left in the decoder's store (ferhip_decs_decode_dev): its RBSP is dev_n bytes at `dev`, and
+    // rbsp holds the first min(dev_n, FER_SPLIT_PREFIX) of them (all of them once the unit was fetched whole)
+    const uint8_t *dev = nullptr;
+    size_t dev_n = 0;
 };
 // next position i in [from, n - 2) with s[i] == 0, s[i+1] == 0 and s[i+2] in `third` (two allowed values), or npos;
 // zero bytes are rare in entropy-coded data, so the scan is driven by memchr
@@ -340,6 +344,8 @@ struct DecSession {
     uint8_t *hold = nullptr;
     std::vector<char> held;
     double t_pack = 0, t_parse = 0, t_recon = 0;
+    const uint8_t *dev_rbsp = nullptr;  // the device splitter's store: where the `dev` units of a window lie
+    std::vector<uint8_t> whole;         // a device unit whose slice header runs past its prefix, fetched to be parsed again
 };
 
 static double dec_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -552,6 +558,7 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
     ss.pres.assign(TW * S, 0);
     // slice headers and the offsets of the slices in the window's RBSP buffer
     size_t total = 0;
+    bool on_dev = false;  // the window's slices lie in the device splitter's store (a call's units are all of one kind)
     for (size_t t = 0; t < TW; t++)
         for (int s = 0; s < S; s++) {
             uint32_t *in = &ss.info[(t * S + s) * 6];
@@ -559,10 +566,24 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             hd[3] = 2;
             if (t0 + t >= slices[s].size() || !slices[s][t0 + t] || (iso && iso->stop[s])) continue;
             const NalRef &n = *slices[s][t0 + t];
+            const size_t full = n.dev ? n.dev_n : n.rbsp.size();
             int ov = 0;
+            const DecHdr before = ss.hs[s];
             int rc = dec_parse_slice_header(ss.hs[s], n.rbsp.data(), n.rbsp.size(), n.type, n.ref_idc, in, ov);
+            if (full > n.rbsp.size() && (rc || in[1] > n.rbsp.size() * 8)) {
+                // the header is longer than the prefix that came back with the table: this unit is fetched whole and
+                // parsed again from the state in front of it
+                ss.whole.resize(full);
+                if (hipMemcpyAsync(ss.whole.data(), n.dev, full, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
+                    hipStreamSynchronize(c->st) != hipSuccess)
+                    return FERHIP_E_HIP;
+                ss.hs[s] = before;
+                ov = 0;
+                rc = dec_parse_slice_header(ss.hs[s], ss.whole.data(), full, n.type, n.ref_idc, in, ov);
+            }
+            in[0] = rc ? in[0] : (uint32_t)full;
             // a header that runs past the end of its NAL unit, or a SliceQPY outside 0..51: damaged
-            if (!rc && iso && (in[1] > n.rbsp.size() * 8 || in[3] > 51)) rc = FERHIP_E_ARG;
+            if (!rc && iso && (in[1] > full * 8 || in[3] > 51)) rc = FERHIP_E_ARG;
             if (rc) {
                 if (!iso) return rc;
                 iso->status[s] = rc;
@@ -571,9 +592,16 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
                 continue;
             }
             ss.pres[t * S + s] = 1;
-            in[4] = (uint32_t)total;
-            in[5] = (uint32_t)(total >> 32);
-            total += (n.rbsp.size() + 15) & ~(size_t)15;
+            if (n.dev) {  // parsed where the splitter left it
+                const size_t at = (size_t)(n.dev - ss.dev_rbsp);
+                in[4] = (uint32_t)at;
+                in[5] = (uint32_t)((unsigned long long)at >> 32);
+                on_dev = true;
+            } else {
+                in[4] = (uint32_t)total;
+                in[5] = (uint32_t)(total >> 32);
+                total += (n.rbsp.size() + 15) & ~(size_t)15;
+            }
             // what the kernels need of this stream's PPS travels with the picture
             hd[0] = (uint32_t)ss.hs[s].chroma_qp_offset;
             hd[1] = (uint32_t)ss.hs[s].constrained_intra;
@@ -582,7 +610,7 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             ss.anyAny[t] = 1;
             ss.keep[t * S + s] = !ss.hs[s].mod_flag || ss.hs[s].mod_copies > 0;
         }
-    if (total + 64 > ar->rbsp_cap) {
+    if (!on_dev && total + 64 > ar->rbsp_cap) {
         if (ar->d_rbsp) hipFree(ar->d_rbsp);
         if (ar->h_rbsp) hipHostFree(ar->h_rbsp);
         ar->d_rbsp = ar->h_rbsp = nullptr;
@@ -592,7 +620,7 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             return FERHIP_E_HIP;
         }
     }
-    {  // gather the slices into the pinned staging buffer with a few threads, then one H2D copy
+    if (!on_dev) {  // gather the slices into the pinned staging buffer with a few threads, then one H2D copy
         const int nth = std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
         auto gather = [&](int k) {
             for (int s = k; s < S; s += nth)
@@ -611,12 +639,12 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             for (auto &x : th) x.join();
         }
     }
-    if (hipMemcpyAsync(ar->d_rbsp, ar->h_rbsp, total, hipMemcpyHostToDevice, c->st) != hipSuccess ||
+    if ((!on_dev && hipMemcpyAsync(ar->d_rbsp, ar->h_rbsp, total, hipMemcpyHostToDevice, c->st) != hipSuccess) ||
         hipMemcpyAsync(ss.d_info, ss.info.data(), ss.info.size() * 4, hipMemcpyHostToDevice, c->st) != hipSuccess ||
         hipMemcpyAsync(B.hdr, ss.hdr.data(), ss.hdr.size() * 4, hipMemcpyHostToDevice, c->st) != hipSuccess)
         return FERHIP_E_HIP;
     B.TW = (int)TW;
-    B.rbsp = ar->d_rbsp;
+    B.rbsp = on_dev ? ss.dev_rbsp : ar->d_rbsp;
     B.info = ss.d_info;
     ss.t_pack += dec_now() - ta;
     ta = dec_now();
@@ -879,6 +907,9 @@ struct ferhip_decs {
     std::vector<int> queued;                  // slice NAL units taken from each stream's chunk in this call
     std::vector<char> need_idr;               // after a fault: P slices are refused until an IDR slice
     DecIsolate iso;
+    FerSplit split;                           // ferhip_decs_decode_dev: the splitter's buffers and the store of the units' RBSP
+    std::vector<std::vector<uint8_t>> whole;  // ... parameter sets longer than the prefix, fetched whole
+    double t_split = 0;                       // seconds in the host splitter
 };
 
 // Stream s back to the state of a new decoder; forget_ps = also forget its parameter sets, else keep them and refuse
@@ -951,6 +982,7 @@ extern "C" void ferhip_decs_destroy(ferhip_decs *d)
     if (d->iso.d_map) hipFree(d->iso.d_map);
     if (d->iso.d_stage) hipFree(d->iso.d_stage);
     if (d->iso.h_stage) hipHostFree(d->iso.h_stage);
+    fer_split_free(d->split);
     dec_session_close(d->ss);
     delete d;
 }
@@ -994,6 +1026,8 @@ static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices
     }
 }
 
+static int decs_run(ferhip_decs *d, uint8_t *out, int out_on_device, int *pictures, int *status);
+
 extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
                                   int *pictures, int *status)
 {
@@ -1008,6 +1042,7 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
         d->queued[s] = 0;
         if (chunks[s] && lens[s]) bytes += lens[s];
     }
+    const double ts = dec_now();
     {  // NAL splitting: a few threads when there is much of it
         const int nth = bytes < ((size_t)1 << 20) ? 1 : std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
         auto split = [&](int k) {
@@ -1022,6 +1057,82 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
             for (auto &x : th) x.join();
         }
     }
+    d->t_split += dec_now() - ts;
+    return decs_run(d, out, out_on_device, pictures, status);
+}
+
+extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out,
+                                      int out_on_device, int *pictures, int *status)
+{
+    if (!d || !d_chunks || !lens || !pictures || !status) return FERHIP_E_ARG;
+    const int S = d->S;
+    ferhip_ctx *c = d->ss.c;
+    if (hipSetDevice(c->device) != hipSuccess) return FERHIP_E_HIP;
+    bool any = false;
+    for (int s = 0; s < S; s++) {
+        pictures[s] = status[s] = 0;
+        d->nals[s].clear();
+        d->cursor[s] = 0;
+        d->queued[s] = 0;
+        any |= d_chunks[s] && lens[s];
+    }
+    if (!any) return 0;
+    // range s = the chunk of stream s: one set of launches splits them all into the decoder's store
+    int rc = fer_split_run(d->split, c->st, d_chunks, lens, S, nullptr, 0);
+    if (rc) return rc;
+    const FerSplit &sp = d->split;
+    const ferhip_nal_unit *tab = sp.table();
+    const size_t nu = sp.head()->units;
+    d->whole.clear();
+    uint32_t cut = ~0u;
+    for (size_t k = 0; k < nu; k++) {
+        const ferhip_nal_unit &u = tab[k];
+        if (u.range == cut) continue;
+        if (u.bytes == 0) {  // a unit without payload ends its stream's chunk (split_stream)
+            cut = u.range;
+            continue;
+        }
+        NalRef n;
+        n.type = u.nal_type;
+        n.ref_idc = u.ref_idc;
+        n.dev = sp.d_store + u.offset;
+        n.dev_n = u.bytes;
+        n.rbsp.p = sp.prefix(k);
+        n.rbsp.n = std::min<size_t>(u.bytes, FER_SPLIT_PREFIX);
+        if ((n.type == 7 || n.type == 8) && n.dev_n > n.rbsp.n) {  // a parameter set longer than the prefix
+            d->whole.emplace_back(n.dev_n);
+            if (hipMemcpyAsync(d->whole.back().data(), n.dev, n.dev_n, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
+                hipStreamSynchronize(c->st) != hipSuccess)
+                return FERHIP_E_HIP;
+            n.rbsp.p = d->whole.back().data();  // (the vector's buffer stays where it is when `whole` grows)
+            n.rbsp.n = n.dev_n;
+        }
+        d->nals[u.range].push_back(n);
+    }
+    d->ss.dev_rbsp = sp.d_store;
+    return decs_run(d, out, out_on_device, pictures, status);
+}
+
+extern "C" int ferhip_decs_timing(ferhip_decs *d, double *t, int reset)
+{
+    if (!d || !t) return FERHIP_E_ARG;
+    t[0] = d->t_split;
+    t[1] = d->ss.t_pack;
+    t[2] = d->ss.t_parse;
+    t[3] = d->ss.t_recon;
+    t[4] = d->split.ms * 1e-3;
+    t[5] = (double)d->split.in_bytes;
+    if (reset) {
+        d->t_split = d->ss.t_pack = d->ss.t_parse = d->ss.t_recon = d->split.ms = 0;
+        d->split.in_bytes = 0;
+    }
+    return 0;
+}
+
+// the chunks of a call are split into d->nals: take them window by window
+static int decs_run(ferhip_decs *d, uint8_t *out, int out_on_device, int *pictures, int *status)
+{
+    const int S = d->S;
     d->iso.status = status;
     d->iso.stop.assign(S, 0);
     d->iso.out = out;

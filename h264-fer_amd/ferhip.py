@@ -49,6 +49,9 @@ assert _QREC.itemsize == C.sizeof(QualityRec)
 
 # ferhip_au of include/ferhip.h: one entry of the index of ferhip_pack_nal / ferhip_fetch_nal / ferhip_frame_nal_blocks
 AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.int32)])
+# ferhip_nal_unit: one entry of the table of ferhip_split_nal_blocks
+NAL_UNIT = np.dtype([("range", np.uint32), ("nal_type", np.int32), ("ref_idc", np.int32), ("bytes", np.uint32), ("offset", np.uint64)])
+SPLIT_PREFIX = 64  # FERHIP_SPLIT_PREFIX: bytes of every unit's RBSP that decode_dev parses headers from
 assert AU.itemsize == 16
 
 
@@ -143,6 +146,9 @@ def load_library():
     lib.ferhip_decs_create.argtypes = [C.POINTER(vp), i, i, i, i]
     lib.ferhip_decs_decode.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_decs_reset_stream.argtypes = [vp, i]
+    lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
+    lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
     lib.ferhip_decs_destroy.argtypes = [vp]
     lib.ferhip_decs_destroy.restype = None
     lib.ferhip_y4m_open.argtypes = [C.POINTER(vp), C.c_char_p, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]
@@ -573,6 +579,38 @@ def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5):
     return rc, out, idx
 
 
+def split_nal_blocks_raw(ranges, misalign=0, cap=None, units_cap=None, fill=0xA5):
+    """ferhip_split_nal_blocks on a list of byte ranges (bytes or uint8 arrays) -> (return code, out [cap] pre-filled with
+    `fill`, units [min(count, units_cap)] of dtype NAL_UNIT, true count).  cap None = room for every range with every unit
+    rounded up to 16; units_cap None = one unit per five bytes."""
+    lib = load_library()
+    n = len(ranges)
+    lens = np.array([len(r) for r in ranges], np.uint32)
+    stride = max(int(lens.max()) if n else 0, 1)
+    src = np.zeros((n, stride), np.uint8)
+    for k, r in enumerate(ranges):
+        src[k, : len(r)] = np.frombuffer(bytes(r), np.uint8) if not isinstance(r, np.ndarray) else r
+    if cap is None:
+        cap = int(sum((int(m) // 5 + 1) * 16 + int(m) for m in lens))
+    if units_cap is None:
+        units_cap = int(sum(int(m) // 5 + 1 for m in lens))
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    units = np.zeros(max(int(units_cap), 1), NAL_UNIT)
+    count = C.c_size_t(0)
+    rc = lib.ferhip_split_nal_blocks(src.ctypes.data, stride, lens.ctypes.data, n, int(misalign), out.ctypes.data, int(cap),
+                                     units.ctypes.data, int(units_cap), C.byref(count))
+    return rc, out, units[: min(count.value, int(units_cap))], count.value
+
+
+def split_nal_blocks(ranges, misalign=0):
+    """The NAL units of every range, split by the kernels of ferhip_decs_decode_dev -> list of (range, nal_unit_type,
+    nal_ref_idc, rbsp bytes)"""
+    rc, out, units, _ = split_nal_blocks_raw(ranges, misalign)
+    _chk(rc, "ferhip_split_nal_blocks")
+    return [(int(u["range"]), int(u["nal_type"]), int(u["ref_idc"]), bytes(out[int(u["offset"]): int(u["offset"]) + int(u["bytes"])]))
+            for u in units]
+
+
 def frame_nal_blocks(payloads, nal_types):
     """Annex-B framing (start code, header byte 1 << 5 | type, emulation prevention) of every payload by the kernels of
     ferhip_pack_nal -> list of bytes"""
@@ -655,7 +693,7 @@ class LiveDecoder:
         self.h = C.c_void_p()
         _chk(self.lib.ferhip_decs_create(C.byref(self.h), nstreams, width, height, max_pictures), "ferhip_decs_create")
 
-    def decode(self, chunks, out=None):
+    def decode(self, chunks, out=None, dev_lens=None):
         """chunks: one bytes or None per stream.  out: [max_pictures][S][W*H*3/2] uint8 -- a NumPy array, a DeviceBuffer,
         a torch tensor on the CPU or on the decoder's device -- or None for a new zeroed NumPy array.  -> (out, pictures,
         status): picture k of stream s in out[k, s] for k < pictures[s]; every other slot is left as it was."""
@@ -681,11 +719,28 @@ class LiveDecoder:
                 on_dev = 1
                 torch.cuda.current_stream(out.device).synchronize()  # the decoder writes from a stream of its own
             ptr = out.data_ptr()
-        arr = (C.c_char_p * self.S)(*[c if c else None for c in chunks])
-        lens = (C.c_size_t * self.S)(*[len(c) if c else 0 for c in chunks])
         pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
-        _chk(self.lib.ferhip_decs_decode(self.h, arr, lens, C.c_void_p(ptr), on_dev, pics, status), "ferhip_decs_decode")
+        if dev_lens is None:
+            arr = (C.c_char_p * self.S)(*[c if c else None for c in chunks])
+            lens = (C.c_size_t * self.S)(*[len(c) if c else 0 for c in chunks])
+            _chk(self.lib.ferhip_decs_decode(self.h, arr, lens, C.c_void_p(ptr), on_dev, pics, status), "ferhip_decs_decode")
+        else:
+            arr = (C.c_void_p * self.S)(*[int(c) if c else None for c in chunks])
+            lens = (C.c_size_t * self.S)(*[int(n) if c else 0 for c, n in zip(chunks, dev_lens)])
+            _chk(self.lib.ferhip_decs_decode_dev(self.h, arr, lens, C.c_void_p(ptr), on_dev, pics, status), "ferhip_decs_decode_dev")
         return out, list(pics), list(status)
+
+    def decode_dev(self, ptrs, lens, out=None):
+        """decode() for chunks that lie in device memory on the decoder's device (ferhip_decs_decode_dev): ptrs[s] = device
+        address of stream s's chunk (any alignment) or None / 0, lens[s] = its bytes."""
+        return self.decode(ptrs, out, dev_lens=lens)
+
+    def timing(self, reset=False):
+        """ferhip_decs_timing -> dict of seconds (host split, pack + H2D, parse, reconstruction, device split launches) and
+        the bytes the device splitter took"""
+        t = (C.c_double * 6)()
+        _chk(self.lib.ferhip_decs_timing(self.h, t, int(reset)), "ferhip_decs_timing")
+        return dict(zip(("host_split", "pack_h2d", "parse", "recon", "dev_split", "dev_split_bytes"), t))
 
     def reset_stream(self, s):
         _chk(self.lib.ferhip_decs_reset_stream(self.h, s), "ferhip_decs_reset_stream")

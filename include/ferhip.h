@@ -405,6 +405,42 @@ int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_
 int ferhip_decs_reset_stream(ferhip_decs *d, int s);
 void ferhip_decs_destroy(ferhip_decs *d);
 
+/* ---- Annex-B input in device memory: the splitter on the device ----
+ * What the decoder's host splitter computes, by kernels.  For a range s[0..n): a unit begins at st = z + 4 for every z with
+ * s[z..z+3] = 00 00 00 01 (z + 3 < n); it ends at en = the smallest i >= st with s[i] = s[i+1] = 0, s[i+2] in {0, 1} and
+ * i + 2 < n, or at n (a three-byte start code ends a unit and begins none); en <= st is no unit.  The header byte is s[st]
+ * (nal_ref_idc = (s[st] & 0x7f) >> 5, nal_unit_type = s[st] & 0x1f), the RBSP is s[st+1..en) without every byte s[p] = 03
+ * with p - 2 >= st + 1 and s[p-2] = s[p-1] = 0.  A unit whose RBSP is empty ends its range: it and what follows are dropped.
+ * The RBSP of the units goes to one buffer, every unit at the next multiple of 16 (the units behind an empty one included:
+ * they are cut from the table, not from the buffer); bytes between units are not written.
+ *
+ * ferhip_split_nal_blocks: known-answer surface, context-free like ferhip_frame_nal_blocks.  n host byte ranges
+ * ([n][stride], lens[n] <= 2^30, n <= 65535) are copied to the device, each to `misalign` (0..15) bytes past a 16-byte
+ * boundary and ending at the end of its allocation, split and read back.  out (host, cap bytes: bytes the kernels do not
+ * write keep the caller's values); units[k] = (range, nal_unit_type, nal_ref_idc, RBSP bytes, offset in out) in range order,
+ * then stream order, after the cut; *nunits receives the true count even when it exceeds units_cap.  FERHIP_E_ARG when
+ * units_cap or cap is too small (no byte at or behind cap is written), or for arguments out of range.
+ *
+ * ferhip_decs_decode_dev: ferhip_decs_decode for chunks that lie in device memory on the decoder's device.  d_chunks[s] is a
+ * device pointer of any alignment (the array itself and lens are host memory; NULL / 0 = nothing new for stream s), for
+ * example d_dst + index[s].offset with index[s].bytes of ferhip_pack_nal once the producing context was synchronised
+ * (ferhip_sync); lens[s] <= 2^30.  The chunks are split on the device into a store the decoder owns, the table and the
+ * first FERHIP_SPLIT_PREFIX bytes of every unit's RBSP come back in one copy, parameter sets and slice headers are parsed
+ * from those on the host (a unit whose header is longer is fetched whole, that unit alone), and the slice data is parsed
+ * where the splitter left it: no chunk byte crosses the bus and nothing is staged.  One host synchronisation for the
+ * split, unless its table or store has to grow.  Results, pictures[], status[] and the isolation rules are those of
+ * ferhip_decs_decode given the same bytes; the two calls may be mixed on one decoder.
+ * ferhip_decs_timing: seconds this decoder has spent so far in t[0] the host splitter, t[1] gathering and copying slices to
+ * the device, t[2] the slice data parse, t[3] reconstruction and output, t[4] the launches of the device splitter (HIP
+ * events); t[5] = the bytes those launches split.  reset != 0 clears the sums. */
+#define FERHIP_SPLIT_PREFIX 64
+typedef struct { uint32_t range; int32_t nal_type, ref_idc; uint32_t bytes; uint64_t offset; } ferhip_nal_unit; /* 24 bytes */
+int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, uint8_t *out,
+                            size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits);
+int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out, int out_on_device,
+                           int *pictures, int *status);
+int ferhip_decs_timing(ferhip_decs *d, double *t /* [6] */, int reset);
+
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
  * centre.  ferhip_y4m_read fills one coded-size I420 picture (use pinned memory when it feeds ferhip_set_frames);
