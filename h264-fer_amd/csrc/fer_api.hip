@@ -238,6 +238,8 @@ int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p, bo
         }
     }
     c->types.assign(S, 2);
+    c->disp_w = W;
+    c->disp_h = H;
     bind_planes(c);
     // the buffers were cleared on the null stream, which the context's non-blocking streams do not wait for: without
     // this the clearing of a large buffer can land after the first picture's kernels have written into it
@@ -293,6 +295,22 @@ __global__ __launch_bounds__(256) void k_repack(uint8_t *set, uint8_t *frames, s
     }
 }
 
+// A presence mask (host [S]) rides a pinned ring to the device, ordered before the kernel that reads it on the context's
+// stream; null stays null (= every stream)
+static int send_mask(ferhip_ctx *c, const uint8_t *present, const uint8_t **d_mask)
+{
+    *d_mask = nullptr;
+    if (!present) return 0;
+    const int S = c->d.S;
+    uint8_t *h = (uint8_t *)c->pres_ring.next();
+    if (!h) return FERHIP_E_HIP;
+    for (int s = 0; s < S; s++) h[s] = present[s] ? 1 : 0;
+    CK(hipMemcpyAsync(c->d_present, h, (size_t)S, hipMemcpyHostToDevice, c->st));
+    if (c->pres_ring.sent(c->st)) return FERHIP_E_HIP;
+    *d_mask = c->d_present;
+    return 0;
+}
+
 // present (host [S], or null = every stream): only the pictures of streams with a non-zero byte are read from src
 static int copy_frames(ferhip_ctx *c, uint8_t *set, const uint8_t *src, uint8_t *dst, hipMemcpyKind kind,
                        const uint8_t *present = nullptr)
@@ -301,14 +319,7 @@ static int copy_frames(ferhip_ctx *c, uint8_t *set, const uint8_t *src, uint8_t 
     size_t fsz = d.ysz * 3 / 2;
     if (kind == hipMemcpyDeviceToDevice && (((uintptr_t)(src ? src : dst)) & 15) == 0) {
         const uint8_t *d_mask = nullptr;
-        if (present) {  // the mask rides a pinned ring to the device, ordered before the repack on the context's stream
-            uint8_t *h = (uint8_t *)c->pres_ring.next();
-            if (!h) return FERHIP_E_HIP;
-            for (int s = 0; s < d.S; s++) h[s] = present[s] ? 1 : 0;
-            CK(hipMemcpyAsync(c->d_present, h, (size_t)d.S, hipMemcpyHostToDevice, c->st));
-            if (c->pres_ring.sent(c->st)) return FERHIP_E_HIP;
-            d_mask = c->d_present;
-        }
+        if (send_mask(c, present, &d_mask)) return FERHIP_E_HIP;
         hipLaunchKernelGGL(k_repack, dim3(256, d.S), dim3(256), 0, c->st, set, (uint8_t *)(src ? src : dst), d.ysz, d.csz, d.S,
                            src ? 1 : 0, d_mask);
         return 0;
@@ -356,24 +367,105 @@ extern "C" int ferhip_set_frames_live(ferhip_ctx *c, const void *src, int host, 
     return 0;
 }
 
+// ---- display size: pictures coded at W x H that the SPS crops to dw x dh (fer_pad.hip, fer_headers.hip) ----
+extern "C" int ferhip_set_display_size(ferhip_ctx *c, int dw, int dh)
+{
+    if (!c) return FERHIP_E_ARG;
+    const FerDev &d = c->d;
+    if (dw <= 0 || dh <= 0 || (dw & 1) || (dh & 1) || dw <= d.W - 16 || dw > d.W || dh <= d.H - 16 || dh > d.H) return FERHIP_E_ARG;
+    if (c->coded) return FERHIP_E_STATE;
+    c->disp_w = dw;
+    c->disp_h = dh;
+    for (uint8_t &x : c->ps_dirty) x = 1;  // the SPS in the device table changes
+    return 0;
+}
+
+// display-size pictures in device memory ([S][dw*dh*3/2], any alignment) -> the current picture set, padded
+static int pad_frames(ferhip_ctx *c, const uint8_t *d_src, const uint8_t *present)
+{
+    const uint8_t *d_mask = nullptr;
+    if (send_mask(c, present, &d_mask)) return FERHIP_E_HIP;
+    fer_launch_pad_ingest(c->d, c->planes[c->cur_set], d_src, c->disp_w, c->disp_h, d_mask, c->st);
+    CK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ferhip_set_frames_display(ferhip_ctx *c, const void *src, int host, const uint8_t *present)
+{
+    if (!c || !src) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    const FerDev &d = c->d;
+    if (!host) return pad_frames(c, (const uint8_t *)src, present);
+    // host pictures: the present ones cross the bus into a device buffer of the display size (one copy per run of
+    // neighbouring present streams), the pad kernel takes them from there
+    const size_t fsz = (size_t)c->disp_w * c->disp_h * 3 / 2;
+    if (!c->disp_stage) {
+        if (dalloc(c, &c->disp_stage, d.ysz * 3 / 2 * d.S) || hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
+            (void)hipGetLastError();
+            return FERHIP_E_HIP;
+        }
+    }
+    for (int s = 0; s < d.S;) {
+        if (present && !present[s]) {
+            s++;
+            continue;
+        }
+        int e = s;
+        while (e < d.S && (!present || present[e])) e++;
+        CK(hipMemcpyAsync(c->disp_stage + (size_t)s * fsz, (const uint8_t *)src + (size_t)s * fsz, (size_t)(e - s) * fsz, hipMemcpyHostToDevice,
+                          c->st));
+        s = e;
+    }
+    int rc = pad_frames(c, c->disp_stage, present);
+    if (rc) return rc;
+    CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// the top-left dw x dh window of the last reconstruction, [S][dw*dh*3/2]: one strided copy per plane and stream
+extern "C" int ferhip_get_recon_display(ferhip_ctx *c, void *dst, int host)
+{
+    if (!c || !dst) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    const FerDev &d = c->d;
+    const size_t dw = (size_t)c->disp_w, dh = (size_t)c->disp_h, dys = dw * dh, fsz = dys * 3 / 2;
+    const uint8_t *set = c->planes[c->cur_set ^ 1];  // after encode_picture the reconstruction is the reference set
+    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    for (int s = 0; s < d.S; s++) {
+        uint8_t *o = (uint8_t *)dst + (size_t)s * fsz;
+        CK(hipMemcpy2DAsync(o, dw, set + (size_t)s * d.ysz, (size_t)d.W, dw, dh, kind, c->st));
+        for (int k = 0; k < 2; k++)
+            CK(hipMemcpy2DAsync(o + dys + (size_t)k * (dys / 4), dw / 2, set + (size_t)d.S * (d.ysz + k * d.csz) + (size_t)s * d.csz,
+                                (size_t)d.Wc, dw / 2, dh / 2, kind, c->st));
+    }
+    CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
 // ---- asynchronous ingest: ReadFromY4M's successor for many streams (row f3) ----
 // ferhip_upload_frames starts the H2D copy of the NEXT pictures ([S][W*H*3/2], pinned host memory) on a copy stream
 // of its own and returns; up to two uploads may be in flight.  ferhip_set_frames_uploaded makes the oldest one the
 // current picture (the repack runs on the encode stream behind the copy).  So the upload of picture t + 1 overlaps
 // the encode of picture t.
-static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *present);
-extern "C" int ferhip_upload_frames(ferhip_ctx *c, const void *pinned_src) { return upload_frames(c, pinned_src, nullptr); }
+// display: the pictures are [S][dw*dh*3/2] at the display size; the staging slot (sized for coded pictures) remembers it
+static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *present, bool display);
+extern "C" int ferhip_upload_frames(ferhip_ctx *c, const void *pinned_src) { return upload_frames(c, pinned_src, nullptr, false); }
 extern "C" int ferhip_upload_frames_live(ferhip_ctx *c, const void *pinned_src, const uint8_t *present)
 {
     if (!present) return FERHIP_E_ARG;
-    return upload_frames(c, pinned_src, present);
+    return upload_frames(c, pinned_src, present, false);
 }
-static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *present)
+extern "C" int ferhip_upload_frames_display(ferhip_ctx *c, const void *pinned_src, const uint8_t *present)
+{
+    return upload_frames(c, pinned_src, present, true);
+}
+static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *present, bool display)
 {
     if (!c || !pinned_src) return FERHIP_E_ARG;
     (void)hipSetDevice(c->device);
     FerDev &d = c->d;
     const size_t bytes = d.ysz * 3 / 2 * d.S;
+    const size_t fsz = display ? (size_t)c->disp_w * c->disp_h * 3 / 2 : d.ysz * 3 / 2;  // one picture of the source
     if (!c->st_copy) {
         // first call: the copy stream, two staging sets, their events.  A failure on the way leaves the context as it
         // was before the call (st_copy null), so that a later call tries again instead of meeting half a setup.
@@ -394,14 +486,14 @@ static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *p
     if (c->up_ready >= 2) return FERHIP_E_STATE;
     const int k = c->up_next;
     CK(hipStreamWaitEvent(c->st_copy, c->up_used[k], 0));  // the repack that last read this slot
+    c->up_disp[k] = display;
     if (!present) {
         c->up_mask[k].clear();
-        CK(hipMemcpyAsync(c->stage[k], pinned_src, bytes, hipMemcpyHostToDevice, c->st_copy));
+        CK(hipMemcpyAsync(c->stage[k], pinned_src, fsz * d.S, hipMemcpyHostToDevice, c->st_copy));
     } else {
         // only the pictures of present streams cross the bus, one copy per run of neighbouring present streams; the mask
         // stays with the staging slot until ferhip_set_frames_uploaded repacks it
         c->up_mask[k].assign(present, present + d.S);
-        const size_t fsz = d.ysz * 3 / 2;
         for (int s = 0; s < d.S;) {
             if (!present[s]) {
                 s++;
@@ -427,8 +519,8 @@ extern "C" int ferhip_set_frames_uploaded(ferhip_ctx *c)
     (void)hipSetDevice(c->device);
     const int k = (c->up_next + 2 - c->up_ready) & 1;  // oldest upload in flight
     CK(hipStreamWaitEvent(c->st, c->up_done[k], 0));
-    int rc = copy_frames(c, c->planes[c->cur_set], c->stage[k], nullptr, hipMemcpyDeviceToDevice,
-                         c->up_mask[k].empty() ? nullptr : c->up_mask[k].data());
+    const uint8_t *mask = c->up_mask[k].empty() ? nullptr : c->up_mask[k].data();
+    int rc = c->up_disp[k] ? pad_frames(c, c->stage[k], mask) : copy_frames(c, c->planes[c->cur_set], c->stage[k], nullptr, hipMemcpyDeviceToDevice, mask);
     if (rc) return rc;
     CK(hipEventRecord(c->up_used[k], c->st));
     c->up_ready--;
@@ -600,6 +692,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
         CK(hipGetLastError());
         return 0;
     }
+    c->coded = true;  // from here on the display size is fixed (ferhip_set_display_size)
     if (anyNone) fer_launch_carry_ref(d, c->st);  // absent streams keep their reference picture across the swap below
     // quality measurement: the source is reconstructed in place, so it is kept before the first launch that reconstructs
     const int qflags = quality_flags(c);

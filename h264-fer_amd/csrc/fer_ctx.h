@@ -71,6 +71,11 @@ struct ferhip_ctx {
     int up_next = 0, up_ready = 0;  // slot the next upload fills; uploads waiting to be made current
     int cur_set = 0;
     bool refprep_valid = false;
+    // display size (ferhip_set_display_size): the pictures are coded at W x H, the SPS crops them to disp_w x disp_h
+    int disp_w = 0, disp_h = 0;
+    bool coded = false;              // a picture has been coded: the display size is frozen
+    bool up_disp[2] = {};            // the staging slot holds display-size pictures (ferhip_upload_frames_display)
+    uint8_t *disp_stage = nullptr;   // ferhip_set_frames_display(host = 1): the pictures on their way to the pad kernel
     // live contexts: presence masks.  An ingest mask goes to the device through a pinned ring of its own; the mask of
     // k_frame_sad needs one slot only, because the read-back of the SADs waits for the stream
     uint8_t *d_present = nullptr, *d_sadskip = nullptr;  // device [S]

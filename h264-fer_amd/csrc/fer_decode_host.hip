@@ -47,6 +47,7 @@ struct DecHdr {
     // slice-header state the reference keeps in globals between slices: the active reference count is only ever set
     // by an override (never reset to the PPS default), the list-modification flag and its entry count only by P slices
     int nref_active_minus1, mod_flag, mod_copies;
+    int crop[4];  // frame cropping of the SPS in luma samples: left, right, top, bottom (zeros = none)
 };
 
 // seq_parameter_set_rbsp, F/headers_and_parameter_sets.cpp:398-470.  Returns 0, or FERHIP_E_UNSUP for syntax the
@@ -76,6 +77,18 @@ static int dec_parse_sps(DecHdr &h, HostBR &r)
     h.W = wmb * 16;
     h.H = hmu * 16;
     h.have_sps = 1;
+    // The reference stops here.  direct_8x8_inference_flag, then the frame cropping: offsets in units of two luma samples
+    // (4:2:0, frame_mbs_only).  Cropping is information for the caller (ferhip_decs_get_crop) and never a reason to refuse a
+    // stream: an SPS that ends before the offsets do, or whose offsets leave no picture, counts as uncropped.
+    h.crop[0] = h.crop[1] = h.crop[2] = h.crop[3] = 0;
+    r.bits(1);
+    if (r.bits(1)) {
+        unsigned o[4];
+        for (int k = 0; k < 4; k++) o[k] = r.ue();
+        const bool whole = r.pos < r.n * 8;  // vui_parameters_present_flag and the stop bit still follow
+        if (whole && (unsigned long long)o[0] + o[1] < (unsigned)h.W / 2u && (unsigned long long)o[2] + o[3] < (unsigned)h.H / 2u)
+            for (int k = 0; k < 4; k++) h.crop[k] = (int)(o[k] * 2u);
+    }
     return 0;
 }
 
@@ -461,6 +474,10 @@ struct DecIsolate {
     std::vector<size_t> fin;     // host output: slot (k * S + s) of the caller's buffer of every staged picture, in order
     uint8_t *d_stage = nullptr, *h_stage = nullptr;  // host output: the window's pictures, packed, on the device and pinned
     size_t stage_cap = 0;        // pictures
+    // ferhip_decs_set_display: the window (x0, y0, dw, dh) of every picture that goes to `out`; ofsz = bytes of one slot
+    bool windowed = false;
+    int win[4] = {};
+    size_t ofsz = 0;
 };
 
 // After the parse of an isolated window: find each faulted stream's first faulted picture (B.state[pic * 4 + 3]), drop it
@@ -529,7 +546,7 @@ static int dec_isolate_faults(DecSession &ss, size_t TW, DecIsolate &iso, const 
         iso.d_stage = iso.h_stage = nullptr;
         iso.stage_cap = 0;
         const size_t cap = std::min(std::max(iso.fin.size(), (size_t)S), ss.TWmax * S);
-        if (hipMalloc((void **)&iso.d_stage, cap * ss.fsz) != hipSuccess || hipHostMalloc((void **)&iso.h_stage, cap * ss.fsz) != hipSuccess)
+        if (hipMalloc((void **)&iso.d_stage, cap * iso.ofsz) != hipSuccess || hipHostMalloc((void **)&iso.h_stage, cap * iso.ofsz) != hipSuccess)
             return FERHIP_E_HIP;
         iso.stage_cap = cap;
     }
@@ -690,9 +707,11 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         c->cur_set ^= 1;  // the decoded picture becomes the reference (modificationProcess -> frameDeepCopy)
         bind_planes(c);
         if (iso) {
-            if (iso->out)
-                fer_launch_decode_out(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], iso->out_dev ? iso->out : iso->d_stage,
-                                      c->st);
+            uint8_t *to = iso->out_dev ? iso->out : iso->d_stage;
+            if (iso->out && iso->windowed)
+                fer_launch_decode_out_win(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, iso->win, c->st);
+            else if (iso->out)
+                fer_launch_decode_out(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, c->st);
         } else if (out) {
             int rc = ferhip_get_recon(c, out + (t0 + t) * S * ss.fsz, 1);
             if (rc) return rc;
@@ -720,12 +739,12 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
     size_t staged = 0;
     if (iso && iso->out && !iso->out_dev) {
         for (size_t t = 0; t < TW; t++) staged += (size_t)iso->nmap[t];
-        if (staged && hipMemcpyAsync(iso->h_stage, iso->d_stage, staged * ss.fsz, hipMemcpyDeviceToHost, c->st) != hipSuccess)
+        if (staged && hipMemcpyAsync(iso->h_stage, iso->d_stage, staged * iso->ofsz, hipMemcpyDeviceToHost, c->st) != hipSuccess)
             return FERHIP_E_HIP;
     }
     if (hipStreamSynchronize(c->st) != hipSuccess || hipGetLastError() != hipSuccess) return FERHIP_E_HIP;
     if (staged) {  // the staged pictures to their slots of the caller's buffer (nothing else of it is written)
-        const size_t fsz = ss.fsz;
+        const size_t fsz = iso->ofsz;
         auto scatter = [&](size_t j0, size_t j1) {
             for (size_t j = j0; j < j1; j++) memcpy(iso->out + iso->fin[j] * fsz, iso->h_stage + j * fsz, fsz);
         };
@@ -964,6 +983,9 @@ extern "C" int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, in
     d->cursor.assign(nstreams, 0);
     d->queued.assign(nstreams, 0);
     d->need_idr.assign(nstreams, 0);
+    d->iso.win[2] = width;
+    d->iso.win[3] = height;
+    d->iso.ofsz = d->ss.fsz;
     if (hipMalloc((void **)&d->iso.d_map, d->ss.TWmax * nstreams * sizeof(int2)) != hipSuccess) {
         ferhip_decs_destroy(d);
         return FERHIP_E_HIP;
@@ -992,6 +1014,38 @@ extern "C" int ferhip_decs_reset_stream(ferhip_decs *d, int s)
     if (!d || s < 0 || s >= d->S) return FERHIP_E_ARG;
     (void)hipSetDevice(d->ss.c->device);
     return decs_reset(d, s, true);
+}
+
+// frame cropping of stream s's current SPS, in luma samples: left, right, top, bottom
+extern "C" int ferhip_decs_get_crop(ferhip_decs *d, int s, int crop[4])
+{
+    if (!d || !crop || s < 0 || s >= d->S) return FERHIP_E_ARG;
+    const DecHdr &h = d->ss.hs[s];
+    if (!h.have_sps) return FERHIP_E_STATE;
+    for (int k = 0; k < 4; k++) crop[k] = h.crop[k];
+    return 0;
+}
+
+// From the next decode call on `out` holds the window (x0, y0, dw, dh) of every picture; (0, 0, W, H) is today's path
+extern "C" int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, int dh)
+{
+    if (!d || x0 < 0 || y0 < 0 || dw < 2 || dh < 2 || ((x0 | y0 | dw | dh) & 1) || x0 > d->W - dw || y0 > d->H - dh) return FERHIP_E_ARG;
+    DecIsolate &iso = d->iso;
+    const size_t ofsz = (size_t)dw * dh * 3 / 2;
+    if (ofsz != iso.ofsz) {  // the staging buffers of host output are sized in slots: they are made again at the next call
+        (void)hipSetDevice(d->ss.c->device);
+        if (iso.d_stage) hipFree(iso.d_stage);
+        if (iso.h_stage) hipHostFree(iso.h_stage);
+        iso.d_stage = iso.h_stage = nullptr;
+        iso.stage_cap = 0;
+    }
+    iso.win[0] = x0;
+    iso.win[1] = y0;
+    iso.win[2] = dw;
+    iso.win[3] = dh;
+    iso.ofsz = ofsz;
+    iso.windowed = !(x0 == 0 && y0 == 0 && dw == d->W && dh == d->H);
+    return 0;
 }
 
 // Take stream s's next NAL units up to the first parameter set that follows a slice (that one belongs to the next

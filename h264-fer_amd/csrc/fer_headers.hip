@@ -55,7 +55,17 @@ extern "C" size_t ferhip_write_sps(ferhip_ctx *c, uint8_t *rbsp, size_t cap)
     w.ue((unsigned)(c->d.mbh - 1));
     w.put(1, 1);
     w.put(1, 1);
-    w.put(1, 0);
+    if (c->disp_w < c->d.W || c->disp_h < c->d.H) {
+        // frame_cropping_flag and the offsets left, right, top, bottom in units of two luma samples (4:2:0, frame_mbs_only);
+        // the reference never crops, so this branch has no line of its own there
+        w.put(1, 1);
+        w.ue(0);
+        w.ue((unsigned)(c->d.W - c->disp_w) / 2u);
+        w.ue(0);
+        w.ue((unsigned)(c->d.H - c->disp_h) / 2u);
+    } else {
+        w.put(1, 0);
+    }
     w.put(1, 0);
     return w.trailing();
 }

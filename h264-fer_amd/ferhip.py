@@ -106,6 +106,10 @@ def load_library():
     lib.ferhip_set_frames_live.argtypes = [vp, vp, i, vp]
     lib.ferhip_upload_frames_live.argtypes = [vp, vp, vp]
     lib.ferhip_reset_stream.argtypes = [vp, i]
+    lib.ferhip_set_display_size.argtypes = [vp, i, i]
+    lib.ferhip_set_frames_display.argtypes = [vp, vp, i, vp]
+    lib.ferhip_upload_frames_display.argtypes = [vp, vp, vp]
+    lib.ferhip_get_recon_display.argtypes = [vp, vp, i]
     lib.ferhip_encode_picture.argtypes = [vp, C.POINTER(i), vp, sz, C.POINTER(C.c_uint32)]
     lib.ferhip_encode_picture_dev.argtypes = [vp, C.POINTER(i), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
     lib.ferhip_select_nal_type.argtypes = [vp, C.POINTER(i)]
@@ -146,6 +150,8 @@ def load_library():
     lib.ferhip_decs_create.argtypes = [C.POINTER(vp), i, i, i, i]
     lib.ferhip_decs_decode.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_decs_reset_stream.argtypes = [vp, i]
+    lib.ferhip_decs_get_crop.argtypes = [vp, i, C.POINTER(i)]
+    lib.ferhip_decs_set_display.argtypes = [vp, i, i, i, i]
     lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
     lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
@@ -214,6 +220,7 @@ class FerHip:
         self.W, self.H, self.S = width, height, nstreams
         self.nmb = (width // 16) * (height // 16)
         self.fsz = width * height * 3 // 2
+        self.dw, self.dh, self.dfsz = width, height, self.fsz  # display size (set_display_size)
         self.params = Params(qp, basic, window, maxdiff, intra_every)
         self.ctx = C.c_void_p()
         _chk(self.lib.ferhip_create(C.byref(self.ctx), width, height, nstreams, C.byref(self.params)), "ferhip_create")
@@ -286,6 +293,37 @@ class FerHip:
             self.set_frames_live(buf, present)
         nt = [NAL_NONE if not present[s] else (NAL_AUTO if nal_types is None else nal_types[s]) for s in range(self.S)]
         return self.encode_picture(nt)
+
+    # --- display size: pictures of any even size, padded to the coded size on the device and cropped by the SPS
+    def set_display_size(self, dw, dh):
+        """ferhip_set_display_size: W - 16 < dw <= W, H - 16 < dh <= H, both even; before the first picture"""
+        _chk(self.lib.ferhip_set_display_size(self.ctx, int(dw), int(dh)), "ferhip_set_display_size")
+        self.dw, self.dh, self.dfsz = int(dw), int(dh), int(dw) * int(dh) * 3 // 2
+
+    def set_frames_display(self, frames, present=None):
+        """ferhip_set_frames_display: [S][dw*dh*3/2] display-size pictures, padded by edge replication on the device.
+        frames: a uint8 array (host), or an integer = a device pointer of any alignment.  present (optional): as in
+        set_frames_live."""
+        m = None if present is None else self._mask(present)
+        mp = None if m is None else m.ctypes.data
+        if isinstance(frames, (int, np.integer)):
+            rc = self.lib.ferhip_set_frames_display(self.ctx, C.c_void_p(int(frames)), 0, mp)
+        else:
+            a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(self.S, self.dfsz)
+            rc = self.lib.ferhip_set_frames_display(self.ctx, a.ctypes.data, 1, mp)
+        _chk(rc, "ferhip_set_frames_display")
+
+    def upload_frames_display(self, host_ptr, present=None):
+        """upload_frames for display-size pictures (pinned host memory, [S][dw*dh*3/2]); set_frames_uploaded() pads them"""
+        m = None if present is None else self._mask(present)
+        _chk(self.lib.ferhip_upload_frames_display(self.ctx, C.c_void_p(int(host_ptr)), None if m is None else m.ctypes.data),
+             "ferhip_upload_frames_display")
+
+    def get_recon_display(self):
+        """the top-left dw x dh window of the last reconstruction, [S][dw*dh*3/2]"""
+        out = np.empty((self.S, self.dfsz), np.uint8)
+        _chk(self.lib.ferhip_get_recon_display(self.ctx, out.ctypes.data, 1), "ferhip_get_recon_display")
+        return out
 
     def set_reference(self, frames):
         a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(self.S, self.fsz)
@@ -690,11 +728,24 @@ class LiveDecoder:
         self.lib = load_library()
         self.S, self.W, self.H, self.P = nstreams, width, height, max_pictures
         self.fsz = width * height * 3 // 2
+        self.cfsz = self.fsz  # a full coded picture; fsz is one slot of `out` (set_display)
         self.h = C.c_void_p()
         _chk(self.lib.ferhip_decs_create(C.byref(self.h), nstreams, width, height, max_pictures), "ferhip_decs_create")
 
+    def get_crop(self, s):
+        """ferhip_decs_get_crop: (left, right, top, bottom) of stream s's current SPS in luma samples"""
+        c = (C.c_int * 4)()
+        _chk(self.lib.ferhip_decs_get_crop(self.h, int(s), c), "ferhip_decs_get_crop")
+        return tuple(c)
+
+    def set_display(self, x0, y0, dw, dh):
+        """ferhip_decs_set_display: from the next decode() on, every slot of `out` holds the window (x0, y0, dw, dh) of its
+        picture, dw*dh*3/2 bytes (self.fsz follows); (0, 0, W, H) restores the full pictures"""
+        _chk(self.lib.ferhip_decs_set_display(self.h, int(x0), int(y0), int(dw), int(dh)), "ferhip_decs_set_display")
+        self.fsz = int(dw) * int(dh) * 3 // 2
+
     def decode(self, chunks, out=None, dev_lens=None):
-        """chunks: one bytes or None per stream.  out: [max_pictures][S][W*H*3/2] uint8 -- a NumPy array, a DeviceBuffer,
+        """chunks: one bytes or None per stream.  out: [max_pictures][S][W*H*3/2] uint8 (after set_display: [..][dw*dh*3/2]) -- a NumPy array, a DeviceBuffer,
         a torch tensor on the CPU or on the decoder's device -- or None for a new zeroed NumPy array.  -> (out, pictures,
         status): picture k of stream s in out[k, s] for k < pictures[s]; every other slot is left as it was."""
         if len(chunks) != self.S:
@@ -711,6 +762,8 @@ class LiveDecoder:
             if out.kind != 0 or out.nbytes < need:
                 raise FerHipError("LiveDecoder.decode: out must be a device DeviceBuffer of [max_pictures][S][W*H*3/2] bytes")
             ptr, on_dev = out.ptr, 1
+        elif isinstance(out, (int, np.integer)):  # a device address of any alignment, max_pictures * S * fsz bytes
+            ptr, on_dev = int(out), 1
         else:  # torch tensor
             import torch
             if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < need:

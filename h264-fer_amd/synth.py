@@ -76,6 +76,20 @@ def crop_to_mb(frame, W, H):
     return np.concatenate([Y.ravel(), U.ravel(), V.ravel()]), Wc, Hc
 
 
+def pad_to_mb(frame, dw, dh):
+    """The padding rule of ferhip_set_frames_display: an I420 picture of dw x dh (both even) -> (coded picture, W, H) with
+    W, H the next multiples of 16 and, per plane of size (pw, ph), coded sample (x, y) = source sample (min(x, pw - 1),
+    min(y, ph - 1))."""
+    W, H = (dw + 15) & ~15, (dh + 15) & ~15
+    f = np.asarray(frame, np.uint8).reshape(-1)
+    planes, o = [], 0
+    for pw, ph, PW, PH in ((dw, dh, W, H), (dw // 2, dh // 2, W // 2, H // 2), (dw // 2, dh // 2, W // 2, H // 2)):
+        p = f[o:o + pw * ph].reshape(ph, pw)
+        o += pw * ph
+        planes.append(p[np.minimum(np.arange(PH), ph - 1)][:, np.minimum(np.arange(PW), pw - 1)].ravel())
+    return np.concatenate(planes), W, H
+
+
 def gen_frames_torch(W, H, n, S, device, seed=1234, noise=2, seeds=None, t0s=None):
     """Same pictures as gen_frame(), built with torch integer ops on `device`: [n][S][W*H*3/2] uint8.
 

@@ -100,6 +100,37 @@ int ferhip_set_frames_live(ferhip_ctx *c, const void *src, int host, const uint8
 int ferhip_upload_frames_live(ferhip_ctx *c, const void *pinned_src, const uint8_t *present);
 int ferhip_reset_stream(ferhip_ctx *c, int s);
 
+/* ---- display size: pictures of any even size ----
+ * The reference answers a picture size that is no multiple of 16 by cropping the source (F/fileIO.cpp:242-243); this section
+ * is what every other H.264 encoder does instead: the picture is padded to the macroblock grid and the SPS crops it back.
+ * The context is still created at the coded size W x H.  ferhip_set_display_size(dw, dh): dw, dh even, W - 16 < dw <= W,
+ * H - 16 < dh <= H, else FERHIP_E_ARG; FERHIP_E_STATE once the context has coded a picture.  The default is (W, H), and
+ * calling it with (W, H) is the default again: a context on which none of the calls below is made behaves as before, byte
+ * for byte.
+ * With dw < W or dh < H, ferhip_write_sps -- and so ferhip_encode_streams and FERHIP_AU_PARAM_SETS -- writes
+ * frame_cropping_flag = 1 and the offsets left ue(0), right ue((W - dw) / 2), top ue(0), bottom ue((H - dh) / 2), in units of
+ * two luma samples (4:2:0, frame_mbs_only), then vui_parameters_present_flag = 0; every bit in front of the flag is as before.
+ *
+ * ferhip_set_frames_display: src = [nstreams][dw*dh*3/2] I420 at the display size, host (host = 1) or device memory of any
+ * alignment (dw*dh*3/2 is in general no multiple of 16).  Each plane of size (pw, ph) = (dw, dh) for luma, (dw/2, dh/2) for
+ * chroma is padded by edge replication, on the device, in one launch:
+ *     coded sample (x, y) = source sample (min(x, pw - 1), min(y, ph - 1)).
+ * present (NULL = every stream) has the meaning it has in ferhip_set_frames_live: the slots of absent streams are not
+ * read (of a device source at most the rest of the aligned 4-byte word that holds a neighbouring picture's first or last
+ * byte is fetched, and dropped), none of their bytes cross the bus and their pictures in the context are untouched.
+ * ferhip_upload_frames_display: the same for the double-buffered pinned ingest (present may be NULL); the staging slot
+ * remembers that it holds display-size pictures and ferhip_set_frames_uploaded pads them.  Display-size and coded-size
+ * uploads may alternate.
+ * ferhip_get_recon_display: the top-left dw x dh window of the last reconstruction, [nstreams][dw*dh*3/2].
+ * ferhip_set_frames, ferhip_upload_frames and ferhip_get_recon keep working at the coded size on such a context (a caller
+ * may pad for itself), and ferhip_encode_streams keeps taking coded-size pictures.  Quality measurement (ferhip_quality),
+ * FERHIP_RC_QUALITY and the AUTO IDR decision (ferhip_select_nal_type) run over the whole coded picture, the padding
+ * included: the padding is part of what is coded. */
+int ferhip_set_display_size(ferhip_ctx *c, int dw, int dh);
+int ferhip_set_frames_display(ferhip_ctx *c, const void *src, int host, const uint8_t *present /* NULL = every stream */);
+int ferhip_upload_frames_display(ferhip_ctx *c, const void *pinned_src, const uint8_t *present /* NULL = every stream */);
+int ferhip_get_recon_display(ferhip_ctx *c, void *dst, int host);
+
 /* ---- RBSP_encode for slice NAL units (F/rbsp_encoding.cpp:139-323) ----
  * nal_type[s]: FERHIP_NAL_IDR / FERHIP_NAL_SLICE / FERHIP_NAL_AUTO / FERHIP_NAL_NONE per stream on input, the
  * type actually used on output (NULL = AUTO for all).  After the call the picture buffers
@@ -397,12 +428,26 @@ void ferhip_dec_destroy(ferhip_dec *d);
  * stream had been absent.
  * Returns 0 when the call ran, even if some streams failed; FERHIP_E_ARG / _HIP for the call as a whole.
  *
- * ferhip_decs_reset_stream: stream s forgets everything, its parameter sets included (a new feed on that slot). */
+ * ferhip_decs_reset_stream: stream s forgets everything, its parameter sets included (a new feed on that slot).
+ *
+ * Cropping.  The live decoder reads an SPS on past frame_mbs_only_flag, where the reference stops: direct_8x8_inference_flag,
+ * frame_cropping_flag and the four offsets.  ferhip_decs_get_crop returns left, right, top, bottom of stream s's current SPS
+ * in luma samples (offset * 2); FERHIP_E_STATE before the stream has an SPS, FERHIP_E_ARG for s outside 0..S-1.  An SPS
+ * without cropping, one that ends before its offsets do and one whose offsets leave no picture (left + right >= W or
+ * top + bottom >= H) report zeros; cropping never changes a status or a decoded sample.
+ * ferhip_decs_set_display(x0, y0, dw, dh): all four even, x0 + dw <= W, y0 + dh <= H, dw, dh >= 2, else FERHIP_E_ARG.  From
+ * the next ferhip_decs_decode / ferhip_decs_decode_dev call on, out is [max_pictures][nstreams][dw*dh*3/2] and slot (k, s)
+ * holds that window of picture k of stream s (host or device out, of any alignment; slots from pictures[s] on are still not
+ * written).  (0, 0, W, H) is the default and restores the full pictures.  The decoder does not apply a stream's cropping by
+ * itself: a caller reads it with ferhip_decs_get_crop and asks for the window it wants.
+ * ferhip_decode_streams and the single-stream ferhip_dec_* always deliver the full coded pictures. */
 typedef struct ferhip_decs ferhip_decs;
 int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, int height, int max_pictures);
 int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
                        int *pictures, int *status);
 int ferhip_decs_reset_stream(ferhip_decs *d, int s);
+int ferhip_decs_get_crop(ferhip_decs *d, int s, int crop[4] /* left, right, top, bottom */);
+int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, int dh);
 void ferhip_decs_destroy(ferhip_decs *d);
 
 /* ---- Annex-B input in device memory: the splitter on the device ----
@@ -443,7 +488,7 @@ int ferhip_decs_timing(ferhip_decs *d, double *t /* [6] */, int reset);
 
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
- * centre.  ferhip_y4m_read fills one coded-size I420 picture (use pinned memory when it feeds ferhip_set_frames);
+ * centre, as the reference does (a caller that wants every sample coded reads the file itself and uses "display size" above).  ferhip_y4m_read fills one coded-size I420 picture (use pinned memory when it feeds ferhip_set_frames);
  * returns 0, or 1 at the end of the stream. */
 typedef struct ferhip_y4m ferhip_y4m;
 int ferhip_y4m_open(ferhip_y4m **out, const char *path, int *in_width, int *in_height, int *coded_width, int *coded_height);
