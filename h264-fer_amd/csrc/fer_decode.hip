@@ -14,7 +14,9 @@
 //                 reconstructed neighbours): intraPrediction (F/intra.cpp:770) + residual.
 //
 // Supported syntax: what the reference encoder emits plus intra macroblocks inside P slices and
-// non-zero mb_qp_delta.  Sub-macroblock types other than P_L0_8x8 set FER_ERR_DEC_UNSUPPORTED.
+// non-zero mb_qp_delta.  All four P sub-macroblock types are parsed (like the reference's DeriveMVs, the first vector
+// difference of a sub-macroblock stands for all of it); a sub_mb_type above 3 is a syntax error, and I_PCM (mb_type 25 in
+// an I slice, 30 in a P slice) sets FER_ERR_DEC_UNSUPPORTED.
 // Decoder quirks of the reference that its output depends on are kept: mb_qp_delta persists when
 // absent (F/rbsp_decoding.cpp:298,322), chroma AC levels persist into cbp == 0 macroblocks
 // (F/residual.cpp:28-49), the more_rbsp_data heuristic (F/rbsp_IO.cpp:193).
@@ -604,7 +606,7 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
             int16_t *lv = mblv;
             for (int i = lane; i < FER_LEVELS / 2; i += 64) ((uint32_t *)mblv)[i] = 0;
             int t = (int)db_ue(b);
-            if (t > 31 || (stype == 2 && t > 24)) {
+            if (t > 30 || (stype == 2 && t > 25)) {  // (25 / 30 is I_PCM, below)
                 atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
                 perr = FER_ERR_DEC_SYNTAX;
                 break;

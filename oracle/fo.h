@@ -15,6 +15,9 @@
  *     MV prediction, motion compensation): pinned by decoding the reference's
  *     own fixture F/drugi.264 and comparing with the md5 of the reference's
  *     output recorded in SURVEY.md section 4.
+ *     On the synthesized streams of tests/slice_synth.py it is pinned to the
+ *     reference's own decoder units linked as oracle/_ref/ref_decode
+ *     (tests/golden/synth_decode_md5.json, tests/test_slice_synth_host.py).
  *   - encoder mode decisions (intra mode choice, motion search): PARITY UNPINNED.
  *     The reference's full translation-unit set cannot be built in this image
  *     (F/stdafx.h:9 needs <tchar.h>, a Windows SDK header the image lacks), so

@@ -278,6 +278,24 @@ def decode_stream_md5(stream):
     return n, frames, state
 
 
+def decode_stream_trace(stream):
+    """Decode an Annex-B stream -> (pictures, list of I420 pictures, list of mb_type_array as it stood after each picture)."""
+    L = lib()
+    frames, types = [], []
+    CB = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)
+
+    def cb(cptr, user):
+        W, H = (int(v) for v in _arr(cptr, 2, np.int32))
+        ys = W * H
+        c = C.c_void_p(cptr)
+        frames.append(np.concatenate([_arr(L.fo_dbg_plane(c, k), ys if k == 0 else ys // 4, np.uint8).copy() for k in range(3)]))
+        types.append(_arr(L.fo_dbg_mb_type(c), (W // 16) * (H // 16), np.int32).copy())
+
+    a = np.frombuffer(stream, np.uint8)
+    n = L.fo_decode_stream(a.ctypes.data, a.size, CB(cb), None, None)
+    return n, frames, types
+
+
 def block_op(name, blocks, qp=0, flag=None):
     """oracle twin of h264_fer_amd.ferhip.block_op (16-int32 records; chroma DC uses slots 0..3)"""
     L = lib()

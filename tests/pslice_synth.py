@@ -63,14 +63,18 @@ def te_bits(w, rng):
 
 
 def p_slice(rng, nmb, frame_num, poc_lsb, override, active_minus1, modification, early_end=False, intra_every=0,
-            mvd_range=3, p_skip=0.25, p_resid=0.3):
-    """-> (rbsp bytes, ref_idx_coded_in_mb_pred).  modification: None | [] | [(idc, value), ...]"""
+            mvd_range=3, p_skip=0.25, p_resid=0.3, log2_max_frame_num=9, log2_max_poc_lsb=10, slice_qp_delta=None,
+            deblocking=None):
+    """The P slice header -> (writer, override, active_minus1).  modification: None | [] | [(idc, value), ...].  The
+    defaults are the field widths of the encoder's parameter sets; slice_synth.py passes those of its own SPS / PPS, a
+    slice_qp_delta of its choice (None: drawn here) and, when the PPS has deblocking_filter_control_present_flag,
+    deblocking = (disable_deblocking_filter_idc, alpha_c0_offset_div2, beta_offset_div2)."""
     w = Bits()
     w.ue(0)
     w.ue(5 if rng.random() < 0.5 else 0)  # slice_type 0 or 5: both P
     w.ue(0)
-    w.put(9, frame_num & 511)
-    w.put(10, poc_lsb & 1023)
+    w.put(log2_max_frame_num, frame_num & ((1 << log2_max_frame_num) - 1))
+    w.put(log2_max_poc_lsb, poc_lsb & ((1 << log2_max_poc_lsb) - 1))
     w.put(1, 1 if override else 0)
     if override:
         w.ue(active_minus1)
@@ -83,7 +87,12 @@ def p_slice(rng, nmb, frame_num, poc_lsb, override, active_minus1, modification,
             w.ue(val)
         w.ue(3)
     w.put(1, 0)  # adaptive_ref_pic_marking_mode_flag
-    w.se(int(rng.integers(-3, 4)))  # slice_qp_delta
+    w.se(int(rng.integers(-3, 4)) if slice_qp_delta is None else slice_qp_delta)
+    if deblocking is not None:
+        w.ue(deblocking[0])
+        if deblocking[0] != 1:
+            w.se(deblocking[1])
+            w.se(deblocking[2])
     return w, override, active_minus1
 
 
