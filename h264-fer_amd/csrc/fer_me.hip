@@ -848,15 +848,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
 // so one batch per slice left them 72 % full); each lane finds its slice through a bitmap of slice starts in LDS
 // (mbcnt over the batch's 64 bits), so the slice fields and the stop tests are per lane.  Four batches in flight.
 // Groups of steps with more than 62 x 64 records (flat content: thousands of positions per sum) go slice by slice.
-// sink(ok, rank, rel, D, info) is called for every batch by all lanes: ok = the lane holds a candidate, rank = its
-// arrival index, rel = (tx - sx) << 16 | (ty - sy) & 0xffff, D = its feature distance, info = the lane's slice
-// descriptor (step j bits 8-15, bucket bits 16-30, side bit 31; a batch may span slices); it returns true (in any
+// sink(ok, rank, rel, D, info, below_lim) is called for every batch by all lanes: ok = the lane holds a candidate,
+// rank = its arrival index, rel = (tx - sx) << 16 | (ty - sy) & 0xffff, D = its feature distance, info = the lane's
+// slice descriptor (step j bits 8-15, bucket bits 16-30, side bit 31; a batch may span slices), below_lim (wave-uniform)
+// = the walk knows that every rank of the batch is below min(128, halt_cnt); it returns true (in any
 // lane) to end the walk after the batch.  Returns the count; jend = the step j the walk ended in.
 // tbl = 192 dwords of 8-byte aligned LDS private to the calling wavefront.
 // max_slice: slices with more records than this are not read (the caller bounds them otherwise) -- those of the steps
 // j > 0, and those of step 0 as well when skip0 is set.
 // probe(bucket) may return a number of candidates the slice of that bucket is KNOWN to hold (0 = unknown): when that
 // alone takes the count past halt_cnt the slice is not read (only walks that ask "is this partition crowded" pass one).
+// the lane's bit of a wave-uniform mask as a predicate: the mask itself serves as the condition, where a shift and a
+// test per lane would take it through a vector register and back
+__device__ __forceinline__ bool wave_mask_bit(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// ... and the other way round: the compare's result is the mask (__ballot takes an int: the predicate goes through a 0 / 1 value)
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 struct NoProbe {
     __device__ __forceinline__ int operator()(int) const { return 0; }
 };
@@ -886,7 +892,7 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
         return kol2[(size_t)a * kt] - (uint32_t)n0;
     };
     const uint32_t sxy = ((uint32_t)sx << 16) | (uint32_t)sy;  // the records' (tx << 16) | ty pairing
-    // Descriptor of a batch, one per lane: first record; count (bits 0-6) | last batch of its step (bit 7) | step j
+    // Descriptor of a batch, one per lane: first record; count (bits 0-6, slice-by-slice route only) | last batch of its step (bit 7) | step j
     // (bits 8-15) | bucket (bits 16-30) | side (bit 31: 0 = su[0] - j, 1 = su[0] + j).  Lanes beyond the last batch hold an empty batch at a readable address, so
     // the loop can fetch two batches ahead without tests.
     const char *srec_s = (const char *)(srec + (size_t)g0 * 3);  // the stream's records: a uniform base + 32-bit byte offsets
@@ -902,6 +908,13 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
         uint32_t dist = __builtin_amdgcn_sad_u16(r0, sxy, 0);
         uint32_t e12 = pk_abs16(pk_sub16(r1, sp.s12));
         return dist < 280u && (pk_sub16(e12, 0x00640064u) & 0x80008000u) == 0x80008000u;
+    };
+    // the same as a wave mask: one ballot per compare, so that each compare's result is used as it is (the ballot of
+    // a conjunction is made from a 0 / 1 value per lane)
+    auto passes_mask = [&](uint32_t r0, uint32_t r1) -> unsigned long long {
+        uint32_t dist = __builtin_amdgcn_sad_u16(r0, sxy, 0);
+        uint32_t e12 = pk_abs16(pk_sub16(r1, sp.s12));
+        return wave_ballot(dist < 280u) & wave_ballot((pk_sub16(e12, 0x00640064u) & 0x80008000u) == 0x80008000u);
     };
     auto feat_d = [&](uint32_t info, uint32_t r0, uint32_t r1, uint32_t r2) -> uint32_t {
         uint32_t D;
@@ -925,7 +938,7 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
         unsigned long long mk = __ballot(ok);
         int rank = tren + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
         const uint32_t D = feat_d(info, r0, r1, r2);
-        const bool halt = sink(ok, rank, (int)pk_sub16(r0, sxy), (int)D, info);
+        const bool halt = sink(ok, rank, (int)pk_sub16(r0, sxy), (int)D, info, false);
         tren += __popcll(mk);
         return halt || tren > halt_cnt;  // the sink has what it wanted, or the caller only asked whether the count passes halt_cnt
     };
@@ -1029,20 +1042,19 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
             WAVE_LDS_SYNC();
             const int nbd = (T + 63) >> 6;
             int dbase = 0;  // slice starts in front of the next batch to describe (described in order)
-            // batch b: the lane's record (stream-relative index) and its descriptor = the slice's | bit 0: last record of
-            // its slice.  b >= nbd: the stream's first record (fetched ahead, never used).
+            // batch b: the lane's record (stream-relative index) and its slice's descriptor.  b >= nbd: the stream's first
+            // record (fetched ahead, never used).
             auto ddesc = [&](int b, uint32_t &li, uint32_t &inf) {
                 const int bb = min(b, nbd - 1);
-                const uint32_t w0 = tbl[2 * bb], w1 = tbl[2 * bb + 1], w2 = tbl[2 * bb + 2];
+                const uint32_t w0 = tbl[2 * bb], w1 = tbl[2 * bb + 1];
                 const unsigned long long M = ((unsigned long long)w1 << 32) | w0;
                 const int inc = (int)__builtin_amdgcn_mbcnt_hi(w1, __builtin_amdgcn_mbcnt_lo(w0, 0u)) + (int)((M >> lane) & 1ull);
                 const int r = min(dbase + inc - 1, nne - 1);  // (lanes past T: the last slice)
                 dbase += __popcll(M);
-                const uint32_t last = lane < 63 ? (uint32_t)((M >> (lane + 1)) & 1ull) : (w2 & 1u);
                 const uint32_t g = min(64u * (uint32_t)bb + (uint32_t)lane, (uint32_t)T - 1u);
                 const uint2 e = *(const uint2 *)&tbl[128 + 2 * r];
                 li = b < nbd ? e.x + g : 0u;
-                inf = e.y | last;
+                inf = e.y;
             };
             auto fetchl = [&](uint32_t li, uint32_t &r0, uint32_t &r1, uint32_t &r2) {
                 const uint32_t *e = (const uint32_t *)(srec_s + __umul24(li, 12u));
@@ -1053,25 +1065,51 @@ __device__ __forceinline__ int walk_buckets_q(const FerDev &d, int s, const int 
             // the stop tests of the walk fall on lanes: the first lane that closes a step with the count past 128 ends
             // the walk there; the first lane that takes the count past halt_cnt ends it with the last record of its step
             // in the batch.  Lanes behind the end are handed to the sink as not ok.  true = the walk is over.
+            // Both ends need a lane whose inclusive count is past min(128, halt_cnt), and no lane's count is above the
+            // count behind the batch: a batch that leaves the count at or below that limit cannot end the walk, and it
+            // is most of them (a partition reads ~20 batches before its count passes 128).  Such a batch takes the short
+            // form -- rank, sink, count --; the stop tests are evaluated only in the others.  Predicates stay wave masks
+            // in scalar registers (ballot in, inverse ballot out), and the records in reach of the batch (64 b + lane <
+            // T: all of them, except in the group's last batch) are a mask made on the scalar side.
+            const int stop_lim = min(128, halt_cnt);
             auto dstep = [&](int b, uint32_t inf, uint32_t r0, uint32_t r1, uint32_t r2) -> bool {
-                const bool valid = 64 * b + lane < T;
-                const bool ok0 = valid && passes(r0, r1);
-                const unsigned long long mk = __ballot(ok0);
+                const int rem = T - 64 * b;  // >= 1: only batches b < nbd are stepped
+                unsigned long long vm = ~0ull, mk = passes_mask(r0, r1);
+                if (rem < 64) {
+                    vm = (1ull << rem) - 1ull;
+                    mk &= vm;
+                }
+                const int nmk = __popcll(mk);
                 const int rank = tren + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                const int incl = rank + (int)ok0;
+                const int rel = (int)pk_sub16(r0, sxy), D = (int)feat_d(inf, r0, r1, r2);
+                if (tren + nmk <= stop_lim) {
+                    // (every rank handed out here is below stop_lim <= 128, which the sink is told)
+                    const bool halt = sink(wave_mask_bit(mk), rank, rel, D, inf, true);
+                    tren += nmk;
+                    const unsigned long long hm = wave_ballot(halt);
+                    if (hm) {  // the sink has what it wanted
+                        jend = __builtin_amdgcn_readlane((int)((inf >> 8) & 255u), __ffsll((long long)hm) - 1);
+                        return true;
+                    }
+                    return false;
+                }
+                const int incl = rank + (int)wave_mask_bit(mk);
                 const int jl = (int)((inf >> 8) & 255u);
-                const unsigned long long s1 = __ballot(valid && (inf & 129u) == 129u && incl > 128);
-                const unsigned long long s2 = __ballot(valid && incl > halt_cnt);
-                unsigned long long live = __ballot(valid);
+                // the last record of each slice: the place in front of a slice start (the bitmap has a bit at T as well)
+                const unsigned long long M = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)tbl[2 * b + 1]) << 32) |
+                                             (uint32_t)__builtin_amdgcn_readfirstlane((int)tbl[2 * b]);
+                const unsigned long long lastm = (M >> 1) | ((unsigned long long)(__builtin_amdgcn_readfirstlane((int)tbl[2 * b + 2]) & 1) << 63);
+                const unsigned long long s1 = wave_ballot((inf & 128u) != 0u) & wave_ballot(incl > 128) & lastm & vm;
+                const unsigned long long s2 = wave_ballot(incl > halt_cnt) & vm;
+                unsigned long long live = vm;
                 if (s1) live &= (2ull << (__ffsll((long long)s1) - 1)) - 1ull;
                 if (s2) {
                     const int j2 = __builtin_amdgcn_readlane(jl, __ffsll((long long)s2) - 1);
-                    live &= __ballot(jl <= j2);
+                    live &= wave_ballot(jl <= j2);
                 }
-                const bool ok = ok0 && ((live >> lane) & 1ull);
-                const bool halt = sink(ok, rank, (int)pk_sub16(r0, sxy), (int)feat_d(inf, r0, r1, r2), inf);
+                const bool halt = sink(wave_mask_bit(mk & live), rank, rel, D, inf, false);
                 tren += __popcll(mk & live);
-                const unsigned long long hm = __ballot(halt);
+                const unsigned long long hm = wave_ballot(halt);
                 if (hm) {  // the sink has what it wanted
                     jend = __builtin_amdgcn_readlane(jl, __ffsll((long long)hm) - 1);
                     return true;
@@ -1202,8 +1240,9 @@ __global__ __launch_bounds__(64, 8) void k_me_walk(FerDev d)
         }
         return n;
     };
-    const int tren = walk_buckets(d, s, su, sp, sx, sy, lane, tbl, FER_ST2_CAP, jend, [&](bool ok, int rank, int rel, int D, uint32_t) {
-        if (ok && rank < FER_ST2_CAP) out[rank] = make_int2(rel, D);
+    static_assert(FER_ST2_CAP >= 128, "a rank the walk reports as below its limit must be inside the list");
+    const int tren = walk_buckets(d, s, su, sp, sx, sy, lane, tbl, FER_ST2_CAP, jend, [&](bool ok, int rank, int rel, int D, uint32_t, bool below_lim) {
+        if (ok && (below_lim || rank < FER_ST2_CAP)) out[rank] = make_int2(rel, D);
         return false;
     }, flat_probe);
     if (tren > FER_ST2_CAP && d.zero_cnt[s] == 0) {
@@ -1347,7 +1386,7 @@ __global__ __launch_bounds__(64, 8) void k_me_walk(FerDev d)
             // smallest positive distance of those (the general bound)
             int j2, dpos = 0x7fffffff;
             // (a batch may span several slices: the sink works per lane and keeps its counters wave-uniform)
-            walk_buckets_q<false>(d, s, su, sp, sx, sy, lane, tbl, 0x7fffffff, j2, [&](bool ok, int rank, int rel, int D, uint32_t info) {
+            walk_buckets_q<false>(d, s, su, sp, sx, sy, lane, tbl, 0x7fffffff, j2, [&](bool ok, int rank, int rel, int D, uint32_t info, bool) {
                 (void)rank;
                 const int j = (int)((info >> 8) & 255u);
                 const bool in = j <= jend && !(j == 0 && (info >> 31));  // (the second visit of bucket su[0]: the same records)
@@ -1799,7 +1838,7 @@ __device__ __forceinline__ int stage2_list(const FerDev &d, int s, int gx, int g
         // now that the predictor is known, through an exact running top-33 (ordered insertion = the reference's own list update)
         const SuPk sp = su_pack(P.su);
         int jx;
-        walk_buckets(d, s, P.su, sp, sx, sy, lane, (uint32_t *)sel_lds, 0x7fffffff, jx, [&](bool ok, int rank, int rel, int D, uint32_t) {
+        walk_buckets(d, s, P.su, sp, sx, sy, lane, (uint32_t *)sel_lds, 0x7fffffff, jx, [&](bool ok, int rank, int rel, int D, uint32_t, bool) {
             (void)rank;
             int tx = rel >> 16, ty = (int)(short)(rel & 0xffff);
             wl_insert(L2, 33, lane, ok, (iabs(tx - genx) + iabs(ty - geny) + 4) * D, pack_xy(tx * 4, ty * 4));
