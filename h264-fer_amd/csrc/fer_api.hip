@@ -3,6 +3,7 @@
 // setters.  Headers are in fer_headers.hip, NAL framing in fer_nalpack.hip, the decoder's host side in fer_decode_host.hip.
 // Host code is C-style C++; nothing here runs the hot path on the CPU.
 #include "fer_ctx.h"
+#include "fer_pic_host.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -263,7 +264,7 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
     if (c->nal_buf) hipFree(c->nal_buf);
     for (void *p : c->pinned) hipHostFree(p);
     for (hipEvent_t e : c->events) hipEventDestroy(e);
-    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring}) r->destroy();
+    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring, &c->pic_ring}) r->destroy();
     for (hipStream_t st : {c->st, c->st_hi, c->st_aux, c->st_copy})
         if (st) hipStreamDestroy(st);
     delete c;
@@ -438,6 +439,52 @@ extern "C" int ferhip_get_recon_display(ferhip_ctx *c, void *dst, int host)
             CK(hipMemcpy2DAsync(o + dys + (size_t)k * (dys / 4), dw / 2, set + (size_t)d.S * (d.ysz + k * d.csz) + (size_t)s * d.csz,
                                 (size_t)d.Wc, dw / 2, dh / 2, kind, c->st));
     }
+    CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// ---- pictures by descriptor (fer_pic.hip): a pointer and a pitch per stream and plane, I420 or NV12 ----
+// The checked descriptors (host [S]) ride a pinned ring to the device table, ordered before the kernel that reads it on the
+// context's stream.  Table and ring are made on first use.  Of an absent stream only the NULL plane[0] is passed on.
+static int send_pics(ferhip_ctx *c, const ferhip_pic *pics, int format)
+{
+    const int S = c->d.S;
+    int rc = fer_pic_check(pics, S, format, (uint32_t)c->disp_w);
+    if (rc) return rc;
+    if (!c->d_pics) {
+        if (c->pic_ring.create(sizeof(ferhip_pic) * S)) return FERHIP_E_HIP;
+        if (dalloc(c, &c->d_pics, (size_t)S) || hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
+            (void)hipGetLastError();
+            return FERHIP_E_HIP;
+        }
+    }
+    ferhip_pic *h = (ferhip_pic *)c->pic_ring.next();
+    if (!h) return FERHIP_E_HIP;
+    for (int s = 0; s < S; s++) h[s] = pics[s].plane[0] ? pics[s] : ferhip_pic{};
+    CK(hipMemcpyAsync(c->d_pics, h, sizeof(ferhip_pic) * S, hipMemcpyHostToDevice, c->st));
+    return c->pic_ring.sent(c->st);
+}
+
+extern "C" int ferhip_set_pictures(ferhip_ctx *c, const ferhip_pic *pics, int format)
+{
+    if (!c || !pics) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = send_pics(c, pics, format);
+    if (rc) return rc;
+    fer_launch_pic_ingest(c->d, c->planes[c->cur_set], c->d_pics, format, c->disp_w, c->disp_h, c->st);
+    CK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ferhip_get_recon_pictures(ferhip_ctx *c, const ferhip_pic *pics, int format)
+{
+    if (!c || !pics) return FERHIP_E_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = send_pics(c, pics, format);
+    if (rc) return rc;
+    const int win[4] = {0, 0, c->disp_w, c->disp_h};
+    fer_launch_pic_emit(c->d, c->planes[c->cur_set ^ 1], c->d_pics, format, win, c->st);  // the reconstruction is the reference set
+    CK(hipGetLastError());
     CK(hipStreamSynchronize(c->st));
     return 0;
 }

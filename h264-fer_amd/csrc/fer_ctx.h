@@ -82,6 +82,9 @@ struct ferhip_ctx {
     PinnedRing pres_ring;                                // [S]
     uint8_t *h_sadskip = nullptr;                        // pinned [S]
     std::vector<uint8_t> up_mask[2];  // ferhip_upload_frames_live: the mask of each staging slot (empty = every stream)
+    // pictures by descriptor (ferhip_set_pictures, ferhip_get_recon_pictures): the [S] table and its pinned ring, on first use
+    ferhip_pic *d_pics = nullptr;  // device [S]
+    PinnedRing pic_ring;           // [S] ferhip_pic
     // NAL framing on the device (fer_nalpack.hip): everything is allocated on first use, the parameter set table and its
     // pinned ring only once FERHIP_AU_PARAM_SETS was asked for
     bool nal_ready = false;            // a picture call has been made: hdr and out_bytes describe a picture

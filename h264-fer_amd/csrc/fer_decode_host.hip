@@ -4,6 +4,7 @@
 // the device's macroblock loop (fer_decode.hip).  ferhip_decode_streams, the streaming decoder (ferhip_dec_*) and the
 // live decoder with per-stream fault isolation (ferhip_decs_*) share one session type over a decode-only context.
 #include "fer_nalsplit.h"
+#include "fer_pic_host.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -478,6 +479,12 @@ struct DecIsolate {
     bool windowed = false;
     int win[4] = {};
     size_t ofsz = 0;
+    // ferhip_decs_set_layout: the slots of device output are pitched I420 or NV12 (k_pic_emit); layout_set stays false on
+    // a decoder that never makes the call, and the pitches then follow the window
+    bool layout_set = false;
+    int fmt = FERHIP_FMT_I420;
+    uint32_t pitch_y = 0, pitch_c = 0;
+    bool pitched() const { return layout_set && !(fmt == FERHIP_FMT_I420 && pitch_y == (uint32_t)win[2] && pitch_c == (uint32_t)win[2] / 2u); }
 };
 
 // After the parse of an isolated window: find each faulted stream's first faulted picture (B.state[pic * 4 + 3]), drop it
@@ -708,7 +715,10 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         bind_planes(c);
         if (iso) {
             uint8_t *to = iso->out_dev ? iso->out : iso->d_stage;
-            if (iso->out && iso->windowed)
+            if (iso->out && iso->pitched())
+                fer_launch_pic_emit_slots(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, iso->fmt, iso->pitch_y, iso->pitch_c,
+                                          fer_pic_slot_bytes(iso->fmt, iso->pitch_y, iso->pitch_c, (uint32_t)iso->win[3]), iso->win, c->st);
+            else if (iso->out && iso->windowed)
                 fer_launch_decode_out_win(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, iso->win, c->st);
             else if (iso->out)
                 fer_launch_decode_out(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, c->st);
@@ -1048,6 +1058,27 @@ extern "C" int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, i
     return 0;
 }
 
+// From the next decode call on the slots of `out` are pitched I420 or NV12; the pitches are checked against the window
+// when a decode call is made (decs_layout_check), since ferhip_decs_set_display may change it in between
+extern "C" int ferhip_decs_set_layout(ferhip_decs *d, int format, uint32_t pitch_y, uint32_t pitch_c)
+{
+    if (!d || (format != FERHIP_FMT_I420 && format != FERHIP_FMT_NV12)) return FERHIP_E_ARG;
+    d->iso.layout_set = true;
+    d->iso.fmt = format;
+    d->iso.pitch_y = pitch_y;
+    d->iso.pitch_c = pitch_c;
+    return 0;
+}
+
+// a layout other than the default: device output only, and pitches that hold a row of the current window
+static int decs_layout_check(const ferhip_decs *d, int out_on_device)
+{
+    const DecIsolate &iso = d->iso;
+    if (!iso.pitched()) return 0;
+    if (!out_on_device) return FERHIP_E_ARG;
+    return fer_pic_layout_check(iso.fmt, iso.pitch_y, iso.pitch_c, (uint32_t)iso.win[2]);
+}
+
 // Take stream s's next NAL units up to the first parameter set that follows a slice (that one belongs to the next
 // window: a slice is parsed with the parameter sets that precede it), appending its slices to `slices`.
 static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices, int *status)
@@ -1085,7 +1116,7 @@ static int decs_run(ferhip_decs *d, uint8_t *out, int out_on_device, int *pictur
 extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
                                   int *pictures, int *status)
 {
-    if (!d || !chunks || !lens || !pictures || !status) return FERHIP_E_ARG;
+    if (!d || !chunks || !lens || !pictures || !status || decs_layout_check(d, out_on_device)) return FERHIP_E_ARG;
     const int S = d->S;
     if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
     size_t bytes = 0;
@@ -1118,7 +1149,7 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
 extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out,
                                       int out_on_device, int *pictures, int *status)
 {
-    if (!d || !d_chunks || !lens || !pictures || !status) return FERHIP_E_ARG;
+    if (!d || !d_chunks || !lens || !pictures || !status || decs_layout_check(d, out_on_device)) return FERHIP_E_ARG;
     const int S = d->S;
     ferhip_ctx *c = d->ss.c;
     if (hipSetDevice(c->device) != hipSuccess) return FERHIP_E_HIP;

@@ -45,3 +45,11 @@ void fer_launch_decode_out_win(const FerDev &d, const uint8_t *set, const int2 *
 // display-size ingest (fer_pad.hip): src = [S][dw*dh*3/2] I420 in device memory, any alignment -> `set`, padded by edge
 // replication to the coded size; present: device [S], 0 = the stream is left out (null = every stream)
 void fer_launch_pad_ingest(const FerDev &d, uint8_t *set, const uint8_t *src, int dw, int dh, const uint8_t *present, hipStream_t st);
+// pictures by descriptor (fer_pic.hip).  d_pics: device [S], a stream with plane[0] == NULL is left out.
+// ingest: pitched I420 / NV12 pictures of dw x dh -> `set`, padded by edge replication to the coded size
+void fer_launch_pic_ingest(const FerDev &d, uint8_t *set, const ferhip_pic *d_pics, int format, int dw, int dh, hipStream_t st);
+// emit: the window win = (x0, y0, dw, dh) of every stream's picture in `set` -> through its descriptor ...
+void fer_launch_pic_emit(const FerDev &d, const uint8_t *set, const ferhip_pic *d_pics, int format, const int *win, hipStream_t st);
+// ... or, for the pictures map[j] = (stream, slot), j < n, -> the pitched slot at dst + slot * slot_bytes (Y, then Cb, Cr or CbCr)
+void fer_launch_pic_emit_slots(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, int format, uint32_t pitch_y,
+                               uint32_t pitch_c, size_t slot_bytes, const int *win, hipStream_t st);

@@ -13,6 +13,7 @@
 //                 taken from the registers; the replicated bottom rows read the last source row again (cache hits).
 // No LDS, no scratch; the kernel moves (dw*dh + W*H) * 3/2 bytes per stream and is bound by HBM like k_repack.
 #include "fer_internal.h"
+#include "fer_pad_run.h"
 
 struct FerPadJob {
     uint8_t *set;            // the picture set, coded size, plane-major
@@ -21,40 +22,6 @@ struct FerPadJob {
     uint32_t W, H, dw, dh;
     int S;
 };
-
-// 4 * N coded samples of one row from column col on: source bytes min(col + i, pw - 1) of the row that starts at `row`
-template <int N>
-__device__ __forceinline__ void pad_run(const uint8_t *row, uint32_t col, uint32_t pw, uint32_t (&out)[N])
-{
-    const uint32_t c0 = min(col, pw - 1u), c1 = min(col + 4u * N - 1u, pw - 1u);
-    const uintptr_t a = (uintptr_t)(row + c0), last = (uintptr_t)(row + c1) & ~(uintptr_t)3;
-    const uint32_t *p = (const uint32_t *)(a & ~(uintptr_t)3);
-    const uint32_t sh = (uint32_t)a & 3u;
-    uint32_t w[N + 1];
-#pragma unroll
-    for (int i = 0; i <= N; i++) w[i] = (uintptr_t)(p + i) <= last ? p[i] : 0u;  // a dword past the run's last byte is not read
-#pragma unroll
-    for (int i = 0; i < N; i++) out[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], sh);
-    const uint32_t nvalid = c1 - c0 + 1u;  // 1 .. 4N bytes of the run come from the source, the rest repeat the last of them
-    if (nvalid < 4u * N) {
-        const uint32_t k = nvalid - 1u;
-        uint32_t e = 0u;
-#pragma unroll
-        for (int i = 0; i < N; i++)
-            if ((k >> 2) == (uint32_t)i) e = out[i];
-        e = ((e >> (8u * (k & 3u))) & 0xffu) * 0x01010101u;
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            const int keep = (int)nvalid - 4 * i;  // bytes of dword i that stay
-            if (keep <= 0) {
-                out[i] = e;
-            } else if (keep < 4) {
-                const uint32_t m = (1u << (8 * keep)) - 1u;
-                out[i] = (out[i] & m) | (e & ~m);
-            }
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void k_pad_ingest(FerPadJob j)
 {

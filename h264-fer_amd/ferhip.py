@@ -110,6 +110,8 @@ def load_library():
     lib.ferhip_set_frames_display.argtypes = [vp, vp, i, vp]
     lib.ferhip_upload_frames_display.argtypes = [vp, vp, vp]
     lib.ferhip_get_recon_display.argtypes = [vp, vp, i]
+    lib.ferhip_set_pictures.argtypes = [vp, vp, i]
+    lib.ferhip_get_recon_pictures.argtypes = [vp, vp, i]
     lib.ferhip_encode_picture.argtypes = [vp, C.POINTER(i), vp, sz, C.POINTER(C.c_uint32)]
     lib.ferhip_encode_picture_dev.argtypes = [vp, C.POINTER(i), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
     lib.ferhip_select_nal_type.argtypes = [vp, C.POINTER(i)]
@@ -152,6 +154,7 @@ def load_library():
     lib.ferhip_decs_reset_stream.argtypes = [vp, i]
     lib.ferhip_decs_get_crop.argtypes = [vp, i, C.POINTER(i)]
     lib.ferhip_decs_set_display.argtypes = [vp, i, i, i, i]
+    lib.ferhip_decs_set_layout.argtypes = [vp, i, C.c_uint32, C.c_uint32]
     lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
     lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
@@ -171,6 +174,30 @@ def load_library():
     lib.ferhip_transform_inverse_scan.argtypes = [vp, vp, sz]
     _lib = lib
     return lib
+
+
+FMT_I420, FMT_NV12 = 0, 1
+
+
+class Pic(C.Structure):
+    """ferhip_pic: one picture where it lies in device memory -- a pointer and a row pitch per plane"""
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+def pic_table(pics):
+    """a list of Pic, None (an absent stream) or (planes, pitches) tuples of up to three entries each -> a ferhip_pic array"""
+    t = (Pic * len(pics))()
+    for k, p in enumerate(pics):
+        if p is None:
+            continue
+        if isinstance(p, Pic):
+            t[k] = p
+            continue
+        planes, pitches = p
+        for n, (a, b) in enumerate(zip(planes, pitches)):
+            t[k].plane[n] = int(a) if a else None
+            t[k].pitch[n] = int(b)
+    return t
 
 
 def _chk(rc, what):
@@ -324,6 +351,20 @@ class FerHip:
         out = np.empty((self.S, self.dfsz), np.uint8)
         _chk(self.lib.ferhip_get_recon_display(self.ctx, out.ctypes.data, 1), "ferhip_get_recon_display")
         return out
+
+    # --- pictures by descriptor: one pointer and row pitch per stream and plane, I420 or NV12, in device memory
+    def set_pictures(self, pics, fmt=FMT_I420):
+        """ferhip_set_pictures: pics[s] = Pic, (planes, pitches) or None for an absent stream (see pic_table); pictures of the
+        display size, padded by edge replication on the device"""
+        if len(pics) != self.S:
+            raise ValueError(f"{len(pics)} descriptors for {self.S} streams")
+        _chk(self.lib.ferhip_set_pictures(self.ctx, pic_table(pics), int(fmt)), "ferhip_set_pictures")
+
+    def get_recon_pictures(self, pics, fmt=FMT_I420):
+        """ferhip_get_recon_pictures: the dw x dh window of the last reconstruction, written through the descriptors"""
+        if len(pics) != self.S:
+            raise ValueError(f"{len(pics)} descriptors for {self.S} streams")
+        _chk(self.lib.ferhip_get_recon_pictures(self.ctx, pic_table(pics), int(fmt)), "ferhip_get_recon_pictures")
 
     def set_reference(self, frames):
         a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(self.S, self.fsz)
@@ -728,7 +769,8 @@ class LiveDecoder:
         self.lib = load_library()
         self.S, self.W, self.H, self.P = nstreams, width, height, max_pictures
         self.fsz = width * height * 3 // 2
-        self.cfsz = self.fsz  # a full coded picture; fsz is one slot of `out` (set_display)
+        self.cfsz = self.fsz  # a full coded picture; fsz is one slot of `out` (set_display, set_layout)
+        self.win, self.layout = (0, 0, width, height), None
         self.h = C.c_void_p()
         _chk(self.lib.ferhip_decs_create(C.byref(self.h), nstreams, width, height, max_pictures), "ferhip_decs_create")
 
@@ -742,7 +784,23 @@ class LiveDecoder:
         """ferhip_decs_set_display: from the next decode() on, every slot of `out` holds the window (x0, y0, dw, dh) of its
         picture, dw*dh*3/2 bytes (self.fsz follows); (0, 0, W, H) restores the full pictures"""
         _chk(self.lib.ferhip_decs_set_display(self.h, int(x0), int(y0), int(dw), int(dh)), "ferhip_decs_set_display")
-        self.fsz = int(dw) * int(dh) * 3 // 2
+        self.win = (int(x0), int(y0), int(dw), int(dh))
+        self._slot()
+
+    def set_layout(self, fmt, pitch_y, pitch_c):
+        """ferhip_decs_set_layout: from the next decode() on (device output only), every slot of `out` holds its picture as
+        pitched I420 (Y, Cb, Cr) or NV12 (Y, CbCr): pitch_y * dh + (2 or 1) * pitch_c * dh/2 bytes (self.fsz follows)"""
+        _chk(self.lib.ferhip_decs_set_layout(self.h, int(fmt), int(pitch_y), int(pitch_c)), "ferhip_decs_set_layout")
+        self.layout = (int(fmt), int(pitch_y), int(pitch_c))
+        self._slot()
+
+    def _slot(self):
+        dw, dh = self.win[2:]
+        if self.layout is None:
+            self.fsz = dw * dh * 3 // 2
+        else:
+            fmt, py, pc = self.layout
+            self.fsz = py * dh + (1 if fmt == FMT_NV12 else 2) * pc * (dh // 2)
 
     def decode(self, chunks, out=None, dev_lens=None):
         """chunks: one bytes or None per stream.  out: [max_pictures][S][W*H*3/2] uint8 (after set_display: [..][dw*dh*3/2]) -- a NumPy array, a DeviceBuffer,

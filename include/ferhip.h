@@ -131,6 +131,41 @@ int ferhip_set_frames_display(ferhip_ctx *c, const void *src, int host, const ui
 int ferhip_upload_frames_display(ferhip_ctx *c, const void *pinned_src, const uint8_t *present /* NULL = every stream */);
 int ferhip_get_recon_display(ferhip_ctx *c, void *dst, int host);
 
+/* ---- pictures by descriptor: a pointer and a row pitch per stream and plane, I420 or NV12 ----
+ * A feed seldom owns one packed [nstreams][w*h*3/2] array: a capture card, a hardware decoder, a compositor or another
+ * library's frame pool hands over one allocation per stream or per plane, rows at a pitch larger than the width (256-byte
+ * aligned on most producers), NV12 more often than I420.  A ferhip_pic names one such picture where it lies, in device
+ * memory on the context's device; pics is a host array of nstreams of them, read before the call returns.
+ * Pictures have the context's display size (dw, dh): (W, H) unless ferhip_set_display_size was called.  A luma row is dw
+ * bytes; a chroma row is dw/2 bytes (I420), or dw bytes of CbCr pairs (NV12, dh/2 rows of them).  Row r of plane k starts
+ * at plane[k] + r * pitch[k]; bases and pitches may have any value, odd ones included, as long as pitch[k] >= the row's bytes.
+ *
+ * ferhip_set_pictures fills the current picture set exactly as ferhip_set_frames_display would fill it from the same
+ * samples packed tight, the edge-replication padding to W x H included, in one launch for all streams and planes.  A
+ * stream with plane[0] == NULL is absent in the sense of ferhip_set_frames_live: nothing of it is read -- the rest of its
+ * descriptor is not looked at either -- and its pictures in the context are untouched.  FERHIP_E_ARG for an unknown
+ * format, and in a present stream for a pitch below the row's bytes, a NULL chroma plane or reserved != 0.  The pictures
+ * must be complete when the call is made, as for ferhip_set_frames(host = 0): the kernel is ordered on the context's
+ * stream, not behind the producer's.
+ * What is read: of a source row only the aligned 4-byte words that hold at least one byte of the row are fetched, so
+ * nothing outside a row is touched except the rest of the word that holds the row's first or last byte (fetched, and
+ * dropped).  The bytes between a row's end and the next row are otherwise never read; a row of NV12 chroma is read once.
+ *
+ * ferhip_get_recon_pictures is the way back: the top-left dw x dh window of each present stream's last reconstruction is
+ * written through the descriptor (ferhip_get_recon_display in the caller's own layout).  Only bytes that belong to a row
+ * are written: the bytes between a row's end and the next row, and every byte around the planes, are left as they were.
+ * It waits for the copy, like ferhip_get_recon_display, and like it delivers whatever the reference picture set holds
+ * (zeros in a new context) when the context has not coded a picture yet. */
+#define FERHIP_FMT_I420 0 /* plane[0] = Y, plane[1] = Cb, plane[2] = Cr */
+#define FERHIP_FMT_NV12 1 /* plane[0] = Y, plane[1] = CbCr interleaved, plane[2] ignored */
+typedef struct ferhip_pic {
+    const void *plane[3]; /* device pointers, any byte alignment; plane[0] == NULL: the stream is absent */
+    uint32_t pitch[3];    /* bytes from one row to the next, >= the row's bytes, otherwise any value (odd included) */
+    uint32_t reserved;    /* 0 */
+} ferhip_pic;
+int ferhip_set_pictures(ferhip_ctx *c, const ferhip_pic *pics /* host, [nstreams] */, int format);
+int ferhip_get_recon_pictures(ferhip_ctx *c, const ferhip_pic *pics /* host, [nstreams]; planes are written */, int format);
+
 /* ---- RBSP_encode for slice NAL units (F/rbsp_encoding.cpp:139-323) ----
  * nal_type[s]: FERHIP_NAL_IDR / FERHIP_NAL_SLICE / FERHIP_NAL_AUTO / FERHIP_NAL_NONE per stream on input, the
  * type actually used on output (NULL = AUTO for all).  After the call the picture buffers
@@ -440,6 +475,17 @@ void ferhip_dec_destroy(ferhip_dec *d);
  * holds that window of picture k of stream s (host or device out, of any alignment; slots from pictures[s] on are still not
  * written).  (0, 0, W, H) is the default and restores the full pictures.  The decoder does not apply a stream's cropping by
  * itself: a caller reads it with ferhip_decs_get_crop and asks for the window it wants.
+ * ferhip_decs_set_layout(format, pitch_y, pitch_c): from the next decode call on every output slot holds its picture -- the
+ * current window of ferhip_decs_set_display, or the full coded picture -- in a pitched layout, as a consumer's frame pool
+ * wants it: Y rows at pitch_y, then for FERHIP_FMT_I420 the Cb rows and the Cr rows at pitch_c, for FERHIP_FMT_NV12 the
+ * dh/2 rows of CbCr pairs at pitch_c.  The Y plane takes pitch_y * dh bytes and each chroma plane pitch_c * dh/2, so a
+ * slot is pitch_y*dh + 2*pitch_c*(dh/2) bytes (I420) or pitch_y*dh + pitch_c*(dh/2) bytes (NV12), and out is
+ * [max_pictures][nstreams][slot] at any alignment.  Only bytes that belong to a row are written: the pitch gaps keep what
+ * they held.  FERHIP_E_ARG for an unknown format.  The pitches must hold a row of the window that is current when a decode
+ * call is made (pitch_y >= dw; pitch_c >= dw/2 for I420, >= dw for NV12), and a layout other than the default needs
+ * out_on_device = 1: else that decode call returns FERHIP_E_ARG before it takes anything.  The default is I420 with pitches
+ * equal to the row bytes; (FERHIP_FMT_I420, dw, dw/2) is the default again, and a decoder on which the call is never made
+ * behaves as before, byte for byte.
  * ferhip_decode_streams and the single-stream ferhip_dec_* always deliver the full coded pictures. */
 typedef struct ferhip_decs ferhip_decs;
 int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, int height, int max_pictures);
@@ -448,6 +494,7 @@ int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_
 int ferhip_decs_reset_stream(ferhip_decs *d, int s);
 int ferhip_decs_get_crop(ferhip_decs *d, int s, int crop[4] /* left, right, top, bottom */);
 int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, int dh);
+int ferhip_decs_set_layout(ferhip_decs *d, int format, uint32_t pitch_y, uint32_t pitch_c);
 void ferhip_decs_destroy(ferhip_decs *d);
 
 /* ---- Annex-B input in device memory: the splitter on the device ----
