@@ -97,6 +97,7 @@ struct ferhip_ctx {
     uint8_t *d_ps = nullptr;           // device [S][FER_NAL_PS_ROW]
     PinnedRing ps_ring;                // [S][FER_NAL_PS_ROW]
     std::vector<uint8_t> ps_dirty;     // [S] the stream's row must be sent (empty until the table exists)
+    bool ps_wide = false;              // a row was too long to record where its PPS begins: no length-prefixed form
     // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof = false;
     struct Span { int phase; hipEvent_t a, b; long launches; };

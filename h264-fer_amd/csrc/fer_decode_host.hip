@@ -249,6 +249,51 @@ static void split_stream(const uint8_t *s, size_t n, std::vector<NalRef> &out, s
     }
 }
 
+// s[from..en) without every s[p] = 03 with s[p-2] = s[p-1] = 0 and p - 2 >= from, appended at w; returns the new end
+static uint8_t *unescape_rbsp(const uint8_t *s, size_t from, size_t en, uint8_t *w)
+{
+    for (;;) {
+        size_t z = find_zz(s, from, en, 3, 3);
+        if (z == (size_t)-1) break;
+        memcpy(w, s + from, z + 2 - from);
+        w += z + 2 - from;
+        from = z + 3;
+    }
+    if (from < en) {
+        memcpy(w, s + from, en - from);
+        w += en - from;
+    }
+    return w;
+}
+
+// split a length-prefixed range (every unit behind its length of L = 1, 2 or 4 bytes, big-endian; the definition: ferhip.h)
+// like split_stream; an empty unit, one without payload and one that overruns the range end it.  Returns 1 if it overran.
+static int split_avcc(const uint8_t *s, size_t n, int L, std::vector<NalRef> &out, std::vector<uint8_t> &store)
+{
+    if (store.size() < n) store.resize(n);
+    uint8_t *w = store.data();
+    size_t pos = 0;
+    while (n - pos >= (size_t)L) {
+        size_t len = 0;
+        for (int k = 0; k < L; k++) len = len << 8 | s[pos + k];
+        const size_t st = pos + L;
+        if (len == 0) return 0;
+        if (len > n - st) return 1;
+        if (len == 1) return 0;
+        const size_t en = st + len;
+        NalRef nal;
+        nal.ref_idc = (s[st] & 0x7f) >> 5;
+        nal.type = s[st] & 0x1f;
+        uint8_t *w0 = w;
+        w = unescape_rbsp(s, st + 1, en, w);
+        nal.rbsp.p = w0;
+        nal.rbsp.n = (size_t)(w - w0);
+        out.push_back(std::move(nal));
+        pos = en;
+    }
+    return pos < n;  // fewer than L bytes are left: a unit that cannot state its length
+}
+
 // Window buffers of the decode twin.  ferhip_decode_streams keeps one arena per process between calls (releasing
 // tens of GB costs more than a window's reconstruction); it is tied to the HIP device it was allocated on and
 // can be dropped with ferhip_decode_release().  A streaming decoder (ferhip_dec_*) owns a small one of its own.
@@ -938,6 +983,8 @@ struct ferhip_decs {
     DecIsolate iso;
     FerSplit split;                           // ferhip_decs_decode_dev: the splitter's buffers and the store of the units' RBSP
     std::vector<std::vector<uint8_t>> whole;  // ... parameter sets longer than the prefix, fetched whole
+    int in_format = FERHIP_IN_ANNEXB, length_size = 4;  // ferhip_decs_set_input
+    std::vector<int> overrun;                 // [S] AVCC input: the stream's chunk of this call overran
     double t_split = 0;                       // seconds in the host splitter
 };
 
@@ -993,6 +1040,7 @@ extern "C" int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, in
     d->cursor.assign(nstreams, 0);
     d->queued.assign(nstreams, 0);
     d->need_idr.assign(nstreams, 0);
+    d->overrun.assign(nstreams, 0);
     d->iso.win[2] = width;
     d->iso.win[3] = height;
     d->iso.ofsz = d->ss.fsz;
@@ -1079,6 +1127,67 @@ static int decs_layout_check(const ferhip_decs *d, int out_on_device)
     return fer_pic_layout_check(iso.fmt, iso.pitch_y, iso.pitch_c, (uint32_t)iso.win[2]);
 }
 
+extern "C" int ferhip_decs_set_input(ferhip_decs *d, int format, int length_size)
+{
+    if (!d || (format != FERHIP_IN_ANNEXB && format != FERHIP_IN_AVCC)) return FERHIP_E_ARG;
+    if (format == FERHIP_IN_AVCC) {
+        if (length_size != 1 && length_size != 2 && length_size != 4) return FERHIP_E_ARG;
+        d->length_size = length_size;
+    }
+    d->in_format = format;
+    return 0;
+}
+
+// one parameter set of stream s: it replaces the stream's current one only if it parses and keeps the decoder's picture size
+static int decs_param_set(ferhip_decs *d, int s, int type, const uint8_t *rbsp, size_t n)
+{
+    DecHdr hn = d->ss.hs[s];
+    HostBR r{rbsp, n, 0};
+    int rc = type == 7 ? dec_parse_sps(hn, r) : dec_parse_pps(hn, r);
+    if (!rc && type == 7 && (hn.W != d->W || hn.H != d->H)) rc = FERHIP_E_UNSUP;  // one picture size per decoder
+    if (!rc) d->ss.hs[s] = hn;
+    return rc;
+}
+
+// AVCDecoderConfigurationRecord -> the SPS units, then the PPS units, to stream s as if they had come in a chunk
+extern "C" int ferhip_decs_set_config(ferhip_decs *d, int s, const uint8_t *avcc, size_t n)
+{
+    if (!d || !avcc || s < 0 || s >= d->S || n < 7 || avcc[0] != 1) return FERHIP_E_ARG;
+    if (d->in_format == FERHIP_IN_AVCC && (avcc[4] & 3) + 1 != d->length_size) return FERHIP_E_ARG;
+    struct Span { size_t at, len; };
+    std::vector<Span> units;
+    size_t pos = 5, longest = 0;
+    for (int pass = 0; pass < 2; pass++) {  // numOfSequenceParameterSets (5 bits), numOfPictureParameterSets
+        if (pos >= n) return FERHIP_E_ARG;
+        const int count = pass ? avcc[pos] : avcc[pos] & 31;
+        pos++;
+        if (count == 0) return FERHIP_E_ARG;
+        for (int k = 0; k < count; k++) {
+            if (n - pos < 2) return FERHIP_E_ARG;
+            const size_t len = (size_t)avcc[pos] << 8 | avcc[pos + 1];
+            pos += 2;
+            if (len == 0 || len > n - pos) return FERHIP_E_ARG;
+            units.push_back({pos, len});
+            longest = std::max(longest, len);
+            pos += len;
+        }
+    }
+    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
+    std::vector<uint8_t> rbsp(longest);
+    for (const Span &u : units) {
+        const int type = avcc[u.at] & 0x1f;
+        if (type != 7 && type != 8) continue;  // ignored, as in a chunk
+        const size_t m = (size_t)(unescape_rbsp(avcc, u.at + 1, u.at + u.len, rbsp.data()) - rbsp.data());
+        if (m == 0) break;  // a unit without payload ends a chunk
+        if (int rc = decs_param_set(d, s, type, rbsp.data(), m)) {
+            // the stream's fault, as in a chunk: it restarts at its next IDR slice
+            if (int rr = decs_reset(d, s, false)) return rr;
+            return rc;
+        }
+    }
+    return 0;
+}
+
 // Take stream s's next NAL units up to the first parameter set that follows a slice (that one belongs to the next
 // window: a slice is parsed with the parameter sets that precede it), appending its slices to `slices`.
 static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices, int *status)
@@ -1087,16 +1196,9 @@ static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices
     std::vector<NalRef> &nals = d->nals[s];
     for (size_t &i = d->cursor[s]; i < nals.size() && !status[s]; i++) {
         const NalRef &n = nals[i];
-        HostBR r{n.rbsp.data(), n.rbsp.size(), 0};
         if (n.type == 7 || n.type == 8) {
             if (!slices.empty()) return;
-            DecHdr hn = h;
-            int rc = n.type == 7 ? dec_parse_sps(hn, r) : dec_parse_pps(hn, r);
-            if (!rc && n.type == 7 && (hn.W != d->W || hn.H != d->H)) rc = FERHIP_E_UNSUP;  // one picture size per decoder
-            if (rc)
-                status[s] = rc;
-            else
-                h = hn;
+            if (int rc = decs_param_set(d, s, n.type, n.rbsp.data(), n.rbsp.size())) status[s] = rc;
         } else if (n.type == 1 || n.type == 5) {
             if (!h.have_sps || !h.have_pps || (n.type == 1 && d->need_idr[s]))
                 status[s] = FERHIP_E_STATE;
@@ -1125,14 +1227,20 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
         d->nals[s].clear();
         d->cursor[s] = 0;
         d->queued[s] = 0;
+        d->overrun[s] = 0;
         if (chunks[s] && lens[s]) bytes += lens[s];
     }
     const double ts = dec_now();
     {  // NAL splitting: a few threads when there is much of it
         const int nth = bytes < ((size_t)1 << 20) ? 1 : std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
         auto split = [&](int k) {
-            for (int s = k; s < S; s += nth)
-                if (chunks[s] && lens[s]) split_stream(chunks[s], lens[s], d->nals[s], d->store[s]);
+            for (int s = k; s < S; s += nth) {
+                if (!chunks[s] || !lens[s]) continue;
+                if (d->in_format == FERHIP_IN_AVCC)
+                    d->overrun[s] = split_avcc(chunks[s], lens[s], d->length_size, d->nals[s], d->store[s]);
+                else
+                    split_stream(chunks[s], lens[s], d->nals[s], d->store[s]);
+            }
         };
         if (nth == 1) {
             split(0);
@@ -1159,13 +1267,16 @@ extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_ch
         d->nals[s].clear();
         d->cursor[s] = 0;
         d->queued[s] = 0;
+        d->overrun[s] = 0;
         any |= d_chunks[s] && lens[s];
     }
     if (!any) return 0;
     // range s = the chunk of stream s: one set of launches splits them all into the decoder's store
-    int rc = fer_split_run(d->split, c->st, d_chunks, lens, S, nullptr, 0);
+    const bool avcc = d->in_format == FERHIP_IN_AVCC;
+    int rc = fer_split_run(d->split, c->st, d_chunks, lens, S, nullptr, 0, avcc ? d->length_size : 0);
     if (rc) return rc;
     const FerSplit &sp = d->split;
+    for (int s = 0; avcc && s < S; s++) d->overrun[s] = sp.h_fault[s];
     const ferhip_nal_unit *tab = sp.table();
     const size_t nu = sp.head()->units;
     d->whole.clear();
@@ -1235,7 +1346,10 @@ static int decs_run(ferhip_decs *d, uint8_t *out, int out_on_device, int *pictur
         for (size_t t0 = 0; t0 < T && !rc; t0 += d->ss.TWmax) rc = dec_session_window(d->ss, slices, t0, std::min(d->ss.TWmax, T - t0), nullptr, pictures, &d->iso);
         if (rc) break;
     }
-    for (int s = 0; s < S && !rc; s++)
+    for (int s = 0; s < S && !rc; s++) {
+        // a chunk that overran (AVCC input): its units in front of the overrun were taken, then the stream faults
+        if (d->overrun[s] && !status[s]) status[s] = FERHIP_E_ARG;
         if (status[s]) rc = decs_reset(d, s, false);
+    }
     return rc;
 }

@@ -1,6 +1,8 @@
 // fer_nalpack.hip -- Annex-B framing of the coded pictures on the device (ferhip_pack_nal, ferhip_fetch_nal,
 // ferhip_frame_nal_blocks): start code, header byte and emulation prevention of writeNAL (F/nal.cpp:261-299) for many
 // payloads at once, written 16-byte aligned into one buffer with an index of (offset, bytes, NAL type).
+// FERHIP_AU_AVCC: the four bytes in front of every unit are its length (big-endian) instead of 00 00 00 01, nothing else
+// changes; the host-side AVCDecoderConfigurationRecord (ferhip_write_avcc_config) stands at the end of the file.
 //
 // writeNAL's counter takes the values 0, 1 and 2 only and an insertion resets it, so a run of payload bytes is a function
 // on three states: for each incoming counter value, how many 03 bytes it inserts and which value it leaves.  These
@@ -18,7 +20,7 @@
 //                output position, the bytes and the inserted 03s are placed in output order in LDS, and the chunk's
 //                output span is stored with 16-byte stores; the ragged bytes at its two ends share a 16-byte word with the
 //                neighbouring chunk and are stored byte-wise.  Chunk 0 also places the parameter sets (where asked for),
-//                the start code and the header byte.  An entry is written only if its 16-byte slots end within `cap`.
+//                the start code -- or the unit's length, which the index holds since k_nal_plan -- and the header byte.  An entry is written only if its 16-byte slots end within `cap`.
 // No workgroup waits for another one: the phases are separate launches on one stream.
 // The host side follows the kernels: the context's buffers and parameter set table, and the three entry points.
 #include "fer_ctx.h"
@@ -29,6 +31,8 @@
 // aligned, every slot readable up to its length rounded up to 16).  hdr != null: an encoder context's slice headers say
 // which payloads are there and give the NAL unit type; else types[n] does and every payload is there.  ps (optional):
 // [n][FER_NAL_PS_ROW] framed SPS + PPS of every payload, the row's last byte = their length; they go in front of IDR units.
+// A row of at most FER_NAL_PS_ROW - 2 bytes also records where its second prefix (the PPS's) sits, in the byte in front of
+// the last one: the length-prefixed form of the row is the row itself with its two prefixes rewritten as it is placed.
 #define FER_NAL_PS_ROW 64
 struct FerNalJob {
     const uint8_t *src;
@@ -37,6 +41,7 @@ struct FerNalJob {
     const uint32_t *hdr;
     const int32_t *types;
     const uint8_t *ps;
+    int avcc;            // the 4-byte prefix of every unit is its length (FERHIP_AU_AVCC), not the start code
     int n, nchmax;       // payloads; 4096-byte chunks a payload can have (the pitch of summ and cin)
     uint4 *summ;         // [n][nchmax] what each chunk does to writeNAL's counter (k_nal_count)
     uint2 *cin;          // [n][nchmax] each chunk's incoming counter and the 03 bytes in front of it (k_nal_plan)
@@ -256,10 +261,21 @@ __global__ __launch_bounds__(NAL_THREADS) void k_nal_emit(FerNalJob j)
         const uint32_t nin = len > chunk * NAL_CHUNK ? min((uint32_t)NAL_CHUNK, len - chunk * NAL_CHUNK) : 0u;
         const uint32_t n = head + nin + nal_cnt(tot, cin.x);
         if (!chunk) {
-            if ((uint32_t)tid < pslen) img[tid] = j.ps[(size_t)s * FER_NAL_PS_ROW + tid];
+            if ((uint32_t)tid < pslen) {
+                const uint8_t *row = j.ps + (size_t)s * FER_NAL_PS_ROW;
+                uint8_t b = row[tid];
+                if (j.avcc) {  // the row's two start codes become the lengths of the SPS and the PPS unit
+                    const uint32_t pps = row[FER_NAL_PS_ROW - 2];
+                    if ((uint32_t)tid < 4u) b = (uint8_t)((pps - 4u) >> (8u * (3u - (uint32_t)tid)));
+                    if ((uint32_t)tid >= pps && (uint32_t)tid < pps + 4u) b = (uint8_t)((pslen - pps - 4u) >> (8u * (3u - ((uint32_t)tid - pps))));
+                }
+                img[tid] = b;
+            }
             if ((uint32_t)tid >= pslen && (uint32_t)tid < pslen + 5u) {
                 const uint32_t k = (uint32_t)tid - pslen;
-                img[tid] = k < 3u ? 0u : (k == 3u ? 1u : (uint8_t)(1u << 5 | ((uint32_t)au.nal_type & 31u)));
+                const uint32_t ulen = au.bytes - pslen - 4u;  // header byte + escaped payload
+                const uint8_t pre = j.avcc ? (uint8_t)(ulen >> (8u * (3u - k))) : (uint8_t)(k == 3u);
+                img[tid] = k < 4u ? pre : (uint8_t)(1u << 5 | ((uint32_t)au.nal_type & 31u));
             }
         }
         {
@@ -335,7 +351,7 @@ static int nal_alloc(ferhip_ctx *c)
 
 // FERHIP_AU_PARAM_SETS: the framed SPS + PPS of every stream in the device table.  Rows that can have changed are built
 // into the next slot of a pinned ring and sent from there on the context's stream.
-static int ps_refresh(ferhip_ctx *c)
+static int ps_refresh(ferhip_ctx *c, bool avcc)
 {
     const int S = c->d.S;
     if (c->ps_dirty.empty()) {
@@ -348,7 +364,7 @@ static int ps_refresh(ferhip_ctx *c)
     }
     bool any = false;
     for (int s = 0; s < S; s++) any |= c->ps_dirty[s] != 0;
-    if (!any) return 0;
+    if (!any) return (avcc && c->ps_wide) ? FERHIP_E_UNSUP : 0;
     uint8_t *slot = (uint8_t *)c->ps_ring.next();
     if (!slot) return FERHIP_E_HIP;
     for (int s = 0; s < S; s++) {
@@ -356,6 +372,7 @@ static int ps_refresh(ferhip_ctx *c)
         uint8_t rbsp[64], nal[2 * (5 + 96)];
         size_t n = ferhip_write_sps(c, rbsp, sizeof rbsp);
         size_t m = ferhip_write_nal(1, 7, rbsp, n, nal);
+        const size_t pps_at = m;
         n = ferhip_write_pps_stream(c, s, rbsp, sizeof rbsp);
         m += ferhip_write_nal(1, 8, rbsp, n, nal + m);
         if (m > FER_NAL_PS_ROW - 1) return FERHIP_E_UNSUP;
@@ -363,6 +380,10 @@ static int ps_refresh(ferhip_ctx *c)
         memset(row, 0, FER_NAL_PS_ROW);
         memcpy(row, nal, m);
         row[FER_NAL_PS_ROW - 1] = (uint8_t)m;
+        if (m <= FER_NAL_PS_ROW - 2)
+            row[FER_NAL_PS_ROW - 2] = (uint8_t)pps_at;
+        else
+            c->ps_wide = true;  // a row without room for the record: such a context has no length-prefixed form
     }
     for (int s = 0; s < S;) {  // one copy per run of rows
         if (!c->ps_dirty[s]) {
@@ -375,7 +396,8 @@ static int ps_refresh(ferhip_ctx *c)
                           hipMemcpyHostToDevice, c->st));
         s = e;
     }
-    return c->ps_ring.sent(c->st);
+    if (int rc = c->ps_ring.sent(c->st)) return rc;
+    return (avcc && c->ps_wide) ? FERHIP_E_UNSUP : 0;
 }
 
 static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
@@ -384,7 +406,7 @@ static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
     (void)hipSetDevice(c->device);
     if (nal_alloc(c)) return FERHIP_E_HIP;
     if (flags & FERHIP_AU_PARAM_SETS) {
-        int rc = ps_refresh(c);
+        int rc = ps_refresh(c, (flags & FERHIP_AU_AVCC) != 0);
         if (rc) return rc;
     }
     FerDev &d = c->d;
@@ -394,6 +416,7 @@ static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
     j.hdr = d.hdr;
     j.types = nullptr;
     j.ps = (flags & FERHIP_AU_PARAM_SETS) ? c->d_ps : nullptr;
+    j.avcc = (flags & FERHIP_AU_AVCC) ? 1 : 0;
     j.n = d.S;
     j.nchmax = c->nal_nchmax;
     j.summ = c->nal_summ;
@@ -407,7 +430,7 @@ static int nal_prepare(ferhip_ctx *c, int flags, FerNalJob &j)
 
 extern "C" int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap, ferhip_au *d_index)
 {
-    if (!c || !d_index || (flags & ~FERHIP_AU_PARAM_SETS) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_index & 7) || (!d_dst && cap))
+    if (!c || !d_index || (flags & ~(FERHIP_AU_PARAM_SETS | FERHIP_AU_AVCC)) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_index & 7) || (!d_dst && cap))
         return FERHIP_E_ARG;
     FerNalJob j;
     int rc = nal_prepare(c, flags, j);
@@ -423,7 +446,7 @@ extern "C" int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap
 
 extern "C" int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_au *h_index)
 {
-    if (!c || !h_index || (flags & ~FERHIP_AU_PARAM_SETS) || (!h_dst && cap)) return FERHIP_E_ARG;
+    if (!c || !h_index || (flags & ~(FERHIP_AU_PARAM_SETS | FERHIP_AU_AVCC)) || (!h_dst && cap)) return FERHIP_E_ARG;
     FerNalJob j;
     int rc = nal_prepare(c, flags, j);
     if (rc) return rc;
@@ -456,10 +479,10 @@ extern "C" int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t ca
 }
 
 // known-answer surface: host payloads through the same kernels, on the null stream with buffers of its own
-extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
-                                       size_t n, uint8_t *out, size_t cap, ferhip_au *index)
+static int frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type, size_t n, int flags,
+                            uint8_t *out, size_t cap, ferhip_au *index)
 {
-    if (!lens || !nal_type || !index || n == 0 || n > 65535 || (!out && cap)) return FERHIP_E_ARG;
+    if ((flags & ~FERHIP_AU_AVCC) || !lens || !nal_type || !index || n == 0 || n > 65535 || (!out && cap)) return FERHIP_E_ARG;
     uint32_t maxlen = 0;
     for (size_t i = 0; i < n; i++) {
         if (lens[i] > stride || (lens[i] && !payloads)) return FERHIP_E_ARG;
@@ -494,6 +517,7 @@ extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, c
         j.hdr = nullptr;
         j.types = dt;
         j.ps = nullptr;
+        j.avcc = (flags & FERHIP_AU_AVCC) ? 1 : 0;
         j.n = (int)n;
         j.nchmax = nchmax;
         j.summ = summ;
@@ -514,4 +538,49 @@ extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, c
     for (void *p : {(void *)src, (void *)dst, (void *)dl, (void *)dt, (void *)summ, (void *)cin, (void *)ent, (void *)idx})
         if (p) hipFree(p);
     return rc;
+}
+
+extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
+                                       size_t n, uint8_t *out, size_t cap, ferhip_au *index)
+{
+    return frame_nal_blocks(payloads, stride, lens, nal_type, n, 0, out, cap, index);
+}
+
+extern "C" int ferhip_frame_nal_blocks_fmt(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
+                                           size_t n, int flags, uint8_t *out, size_t cap, ferhip_au *index)
+{
+    return frame_nal_blocks(payloads, stride, lens, nal_type, n, flags, out, cap, index);
+}
+
+// AVCDecoderConfigurationRecord (ISO/IEC 14496-15 5.2.4.1) of stream s: one SPS and the stream's own PPS, 4-byte lengths
+extern "C" size_t ferhip_write_avcc_config(ferhip_ctx *c, int s, uint8_t *out, size_t cap)
+{
+    if (!c || !out || s < 0 || s >= c->d.S) return 0;
+    uint8_t rbsp[64], sps[2 * (5 + 96)], pps[2 * (5 + 96)];
+    size_t n = ferhip_write_sps(c, rbsp, sizeof rbsp);
+    if (n < 3) return 0;
+    const uint8_t prof[3] = {rbsp[0], rbsp[1], rbsp[2]};
+    const size_t ns = ferhip_write_nal(1, 7, rbsp, n, sps) - 4;  // the unit behind its start code
+    n = ferhip_write_pps_stream(c, s, rbsp, sizeof rbsp);
+    if (n == 0) return 0;
+    const size_t np = ferhip_write_nal(1, 8, rbsp, n, pps) - 4;
+    const size_t total = 6 + 2 + ns + 1 + 2 + np;
+    if (total > cap || ns > 65535 || np > 65535) return 0;
+    uint8_t *w = out;
+    *w++ = 1;  // configurationVersion
+    *w++ = prof[0];
+    *w++ = prof[1];
+    *w++ = prof[2];
+    *w++ = 0xFC | 3;  // lengthSizeMinusOne
+    *w++ = 0xE0 | 1;  // numOfSequenceParameterSets
+    *w++ = (uint8_t)(ns >> 8);
+    *w++ = (uint8_t)ns;
+    memcpy(w, sps + 4, ns);
+    w += ns;
+    *w++ = 1;  // numOfPictureParameterSets
+    *w++ = (uint8_t)(np >> 8);
+    *w++ = (uint8_t)np;
+    memcpy(w, pps + 4, np);
+    w += np;
+    return (size_t)(w - out);
 }

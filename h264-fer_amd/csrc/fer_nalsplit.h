@@ -1,5 +1,6 @@
-// fer_nalsplit.h -- the Annex-B splitter on the device (fer_nalsplit.hip) as the live decoder drives it
-// (fer_decode_host.hip): byte ranges in device memory -> a table of NAL units and their RBSP in one device store.
+// fer_nalsplit.h -- the NAL splitters on the device (fer_nalsplit.hip: Annex-B and length-prefixed ranges) as the live
+// decoder drives them (fer_decode_host.hip): byte ranges in device memory -> a table of NAL units and their RBSP in one
+// device store.
 #pragma once
 #include "fer_ctx.h"
 
@@ -14,6 +15,9 @@ struct FerSplitRange {  // one input range: `len` bytes at `p` (any alignment); 
 struct FerSplitBase {  // what stands in front of a range: RBSP bytes (every unit rounded up to 16) and units
     unsigned long long bytes;
     uint32_t units, pad;
+};
+struct FerAvccUnit {  // one unit of a length-prefixed range: range | header byte << 16; the unit is s[st..en); its first chunk slot
+    uint32_t range, st, en, choff;
 };
 struct FerSplitHead {  // the totals of a job, in front of the table
     unsigned long long bytes;
@@ -32,6 +36,10 @@ struct FerSplit {
     size_t tab_cap = 0;
     uint8_t *d_store = nullptr;                        // the units' RBSP
     size_t store_cap = 0;
+    int32_t *d_fault = nullptr, *h_fault = nullptr;    // device / pinned [fault_cap]: a length-prefixed range overran
+    size_t fault_cap = 0;
+    FerAvccUnit *d_aunit = nullptr;                    // [aunit_cap >= tab_cap] the units of length-prefixed ranges
+    size_t aunit_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;           // around the launches of a job
     double ms = 0;                                     // ... their time, summed over the jobs
     unsigned long long in_bytes = 0;                   // input bytes of those jobs
@@ -45,7 +53,10 @@ struct FerSplit {
 // entries and prefix(k) the first FER_SPLIT_PREFIX bytes of unit k.  dst == NULL: the RBSP goes to sp.d_store, which is grown
 // as needed; else to dst[0, cap) as far as whole units fit (head()->bytes tells what all of them need) and no prefixes are
 // read back.  One host synchronisation unless the table or the store had to grow.
-int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, const size_t *lens, int n, uint8_t *dst, size_t cap);
+// length_size = 0: Annex-B ranges.  1, 2, 4: every unit is preceded by its length of that many bytes; h_fault[r] is then 1
+// for a range that overran, and the table holds the units in front of the range's first empty, header-only or overrunning one.
+int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, const size_t *lens, int n, uint8_t *dst, size_t cap,
+                  int length_size = 0);
 void fer_split_free(FerSplit &sp);
 
 #pragma GCC visibility pop

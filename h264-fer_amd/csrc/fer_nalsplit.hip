@@ -30,6 +30,25 @@
 //   k_split_prefix one wavefront per unit: the first FER_SPLIT_PREFIX bytes of its RBSP to a dense array behind the table.
 // No workgroup waits for another one: the phases are separate launches on one stream.  All loads are naturally aligned
 // and made only of pieces that hold a byte of the range, so nothing outside the pages of [p, p + len) is touched.
+//
+// Length-prefixed (AVCC) ranges, ferhip_split_avcc_blocks and ferhip_decs_decode_dev in AVCC input: the same table, store
+// and prefixes from ranges in which every unit is preceded by its length of L = 1, 2 or 4 bytes (the definition: ferhip.h).
+// Boundaries come from the lengths alone, so the units are found by following the chain, and what is left per unit is the
+// local predicate D(p): s[p] = 3, s[p-1] = s[p-2] = 0, p - 2 >= st + 1.  A unit's payload s[st+1..en) is taken in 4096-byte
+// chunks of its own 16-byte-aligned image; the walk ends a range at its first empty, header-only or overrunning unit, so
+// the table the device writes is already the one behind the cut.
+//   k_avcc_walk   one lane per range follows the length chain with byte loads, twice: first it counts the range's units and
+//                 their chunks and finds its fault, then (behind k_avcc_base) it writes one record per unit (range, header
+//                 byte, st, en, first chunk slot).
+//   k_avcc_base   one wavefront: exclusive sums of the units and chunks over the ranges, the total of the units.
+//   k_avcc_count  grid (chunk, unit): the dropped 03 bytes of every chunk.
+//   k_avcc_plan   one wavefront per unit: exclusive sum of its chunk counts = the 03 bytes in front of every chunk, and the
+//                 unit's RBSP size.
+//   k_avcc_index  one wavefront: exclusive sum of the 16-rounded RBSP sizes over the units = their offsets; the table
+//                 entries and the totals in front of the table.
+//   k_avcc_emit   grid (chunk, unit): the chunk's surviving bytes are compacted in LDS in output order and the span is
+//                 stored with 16-byte stores, its ragged ends byte-wise (k_nal_emit's way); nothing at or behind `cap`.
+//   k_split_prefix as above.
 #include "fer_nalsplit.h"
 #include <string.h>
 #include <algorithm>
@@ -39,6 +58,7 @@
 // LDS image of a chunk's output: its payload bytes, up to 15 bytes in front (the first word's misalignment) and up to 15
 // bytes of rounding for every unit that begins in it (a unit costs five input bytes: 820 units at the most)
 #define SPL_IMG (((15 + SPL_CHUNK + 15 * ((SPL_CHUNK + 4) / 5) + 15) & ~15) + 16)
+#define AVCC_IMG ((15 + SPL_CHUNK + 15) & ~15)  // a chunk's surviving bytes behind up to 15 bytes of misalignment
 #define SPL_MAX_LEN (1u << 30)  // bytes per range: positions, counts and 16-rounded sums stay within 32 bits
 
 struct FerSplitJob {
@@ -53,6 +73,11 @@ struct FerSplitJob {
     uint8_t *dst;
     unsigned long long cap;
     uint8_t *pref;
+    // length-prefixed ranges
+    int lsize;            // bytes of a length: 1, 2 or 4
+    FerAvccUnit *aunit;   // [tab_cap]
+    uint32_t *acnt, *acin;  // [chunk slots] dropped 03 bytes of a chunk / in front of it within its unit
+    int32_t *fault;       // [n] the range overran
 };
 
 // A run's function as a uint4: x = units begun | has an event << 30 | open at the end << 31, y = head bytes, z = bytes of
@@ -377,6 +402,275 @@ static void split_launch_emit(const FerSplitJob &j, unsigned gx, hipStream_t st)
     if (j.pref) hipLaunchKernelGGL(k_split_prefix, dim3((j.tab_cap + 3) / 4), dim3(SPL_THREADS), 0, st, j);
 }
 
+
+// ---- length-prefixed ranges
+
+// pass 0 (write == 0): rtot[r] = (units, chunk slots), fault[r]; pass 1: the units' records, from rbase[r] on
+__global__ __launch_bounds__(64) void k_avcc_walk(FerSplitJob j, int write)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= j.n) return;
+    const FerSplitRange r = j.rng[s];
+    const uint32_t n = r.len, L = (uint32_t)j.lsize;
+    uint32_t ubase = 0u, chbase = 0u;
+    if (write) {
+        const FerSplitBase b = j.rbase[s];
+        ubase = b.units;
+        chbase = (uint32_t)b.bytes;
+    }
+    uint32_t pos = 0u, units = 0u, chunks = 0u, fault = 0u;
+    bool cut = false;
+    while (!cut && n - pos >= L) {  // pos <= n throughout
+        uint32_t len = 0u;
+        for (uint32_t k = 0; k < L; k++) len = len << 8 | r.p[pos + k];
+        const uint32_t st = pos + L;
+        if (len == 0u) {
+            cut = true;
+        } else if (len > n - st) {
+            cut = true;
+            fault = 1u;
+        } else if (len == 1u) {
+            cut = true;
+        } else {
+            const uint32_t a = (uint32_t)((uintptr_t)(r.p + st + 1u) & 15u);
+            const uint32_t u = ubase + units;
+            if (write && u < j.tab_cap) {
+                FerAvccUnit rec;
+                rec.range = (uint32_t)s | (uint32_t)r.p[st] << 16;
+                rec.st = st;
+                rec.en = st + len;
+                rec.choff = chbase + chunks;
+                j.aunit[u] = rec;
+            }
+            units++;
+            chunks += (a + (len - 1u) + SPL_CHUNK - 1u) / SPL_CHUNK;
+            pos = st + len;
+        }
+    }
+    if (!cut && pos < n) fault = 1u;  // fewer than L bytes are left: a unit that cannot state its length
+    if (!write) {
+        j.rtot[s] = make_uint2(units, chunks);
+        j.fault[s] = (int32_t)fault;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_avcc_base(FerSplitJob j)
+{
+    const int lane = threadIdx.x;
+    uint32_t units = 0u, chunks = 0u;
+    for (int s0 = 0; s0 < j.n; s0 += 64) {
+        const int s = s0 + lane;
+        const uint2 e = s < j.n ? j.rtot[s] : make_uint2(0u, 0u);
+        uint32_t iu = e.x, ic = e.y;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t tu = __shfl_up(iu, m), tc = __shfl_up(ic, m);
+            if (lane >= m) {
+                iu += tu;
+                ic += tc;
+            }
+        }
+        if (s < j.n) {
+            FerSplitBase b;
+            b.bytes = chunks + ic - e.y;  // the range's first chunk slot
+            b.units = units + iu - e.x;
+            b.pad = 0;
+            j.rbase[s] = b;
+        }
+        units += __shfl(iu, 63);
+        chunks += __shfl(ic, 63);
+    }
+    if (lane == 0) {
+        FerSplitHead h;
+        h.bytes = 0;
+        h.units = units;
+        h.pad = 0;
+        *j.head = h;
+    }
+}
+
+// A unit's payload is s[st+1 .. en); its image starts a = (address of s[st+1]) & 15 bytes in front of it.  Lane tid of chunk
+// `chunk` takes image bytes [v0, v0 + 16): w = the word, V = one bit per byte inside the payload, D = per dropped 03.
+// The two bytes in front of the word come from the dword that ends at v0, read only when it holds a payload byte.
+__device__ __forceinline__ void avcc_lane(const uint8_t *pay, uint32_t a, uint32_t paylen, uint32_t chunk, int tid, uint4 &w, uint32_t &V, uint32_t &D)
+{
+    const uint8_t *base = pay - a;
+    const int end = (int)(a + paylen), ia = (int)a;
+    const int v0 = (int)(chunk * SPL_CHUNK) + tid * 16;
+    w = make_uint4(~0u, ~0u, ~0u, ~0u);
+    V = D = 0u;
+    if (v0 + 16 <= ia || v0 >= end) return;
+    w = *(const uint4 *)(base + v0);
+    uint32_t prev = ~0u;
+    if (v0 > ia) prev = *(const uint32_t *)(base + v0 - 4);
+    const int lo = max(ia - v0, 0), hi = min(end - v0, 16);
+    V = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+    const uint32_t x[4] = {w.x, w.y, w.z, w.w};
+    uint32_t Z = 0u, Th = 0u;  // bit k + 2: byte k of the word is 00 / 03 (and inside the payload); bits 0, 1: the two bytes in front
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t c = (x[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        Z |= (uint32_t)(c == 0u) << (k + 2);
+        Th |= (uint32_t)(c == 3u) << (k + 2);
+    }
+    Z &= V << 2;
+    Th &= V << 2;
+    if (v0 - 2 >= ia) Z |= (uint32_t)(((prev >> 16) & 0xffu) == 0u);
+    if (v0 - 1 >= ia) Z |= (uint32_t)((prev >> 24) == 0u) << 1;
+    D = (Th & (Z << 1) & (Z << 2)) >> 2;
+}
+
+__device__ __forceinline__ uint32_t avcc_nch(uint32_t a, uint32_t paylen) { return (a + paylen + SPL_CHUNK - 1u) / SPL_CHUNK; }
+
+__global__ __launch_bounds__(SPL_THREADS) void k_avcc_count(FerSplitJob j)
+{
+    const uint32_t nu = min(j.head->units, j.tab_cap);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __shared__ uint32_t wtot[SPL_THREADS / 64];
+    for (uint32_t u = blockIdx.y; u < nu; u += gridDim.y) {
+    const FerAvccUnit rec = j.aunit[u];
+    const uint8_t *pay = j.rng[rec.range & 0xffffu].p + rec.st + 1u;
+    const uint32_t paylen = rec.en - rec.st - 1u, a = (uint32_t)((uintptr_t)pay & 15u), nch = avcc_nch(a, paylen);
+    for (uint32_t chunk = blockIdx.x; chunk < nch; chunk += gridDim.x) {
+        uint4 w;
+        uint32_t V, D;
+        avcc_lane(pay, a, paylen, chunk, tid, w, V, D);
+        uint32_t c = (uint32_t)__popc(D);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+        if (lane == 0) wtot[wave] = c;
+        __syncthreads();
+        if (tid == 0) j.acnt[rec.choff + chunk] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        __syncthreads();
+    }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_avcc_plan(FerSplitJob j)
+{
+    const uint32_t u = blockIdx.x;
+    if (u >= min(j.head->units, j.tab_cap)) return;
+    const FerAvccUnit rec = j.aunit[u];
+    const uint8_t *pay = j.rng[rec.range & 0xffffu].p + rec.st + 1u;
+    const uint32_t paylen = rec.en - rec.st - 1u, nch = avcc_nch((uint32_t)((uintptr_t)pay & 15u), paylen);
+    const int lane = threadIdx.x;
+    uint32_t run = 0u;
+    for (uint32_t i0 = 0; i0 < nch; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        const uint32_t c = i < nch ? j.acnt[rec.choff + i] : 0u;
+        uint32_t incl = c;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t t = __shfl_up(incl, m);
+            if (lane >= m) incl += t;
+        }
+        if (i < nch) j.acin[rec.choff + i] = run + incl - c;
+        run += __shfl(incl, 63);
+    }
+    if (lane == 0) j.tab[u].bytes = paylen - run;
+}
+
+__global__ __launch_bounds__(64) void k_avcc_index(FerSplitJob j)
+{
+    const int lane = threadIdx.x;
+    const uint32_t nu = min(j.head->units, j.tab_cap);
+    unsigned long long run = 0;
+    for (uint32_t u0 = 0; u0 < nu; u0 += 64) {
+        const uint32_t u = u0 + lane;
+        const uint32_t b = u < nu ? j.tab[u].bytes : 0u;
+        const unsigned long long r = ((unsigned long long)b + 15ull) & ~15ull;
+        unsigned long long incl = r;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const unsigned long long t = __shfl_up(incl, m);
+            if (lane >= m) incl += t;
+        }
+        if (u < nu) {
+            const FerAvccUnit rec = j.aunit[u];
+            const uint32_t c = rec.range >> 16;
+            ferhip_nal_unit e;
+            e.range = rec.range & 0xffffu;
+            e.nal_type = (int32_t)(c & 0x1fu);
+            e.ref_idc = (int32_t)((c & 0x7fu) >> 5);
+            e.bytes = b;
+            e.offset = run + incl - r;
+            j.tab[u] = e;
+        }
+        run += __shfl(incl, 63);
+    }
+    if (lane == 0) j.head->bytes = run;  // of the units in the table: with more units than that the host repeats the job
+}
+
+__global__ __launch_bounds__(SPL_THREADS) void k_avcc_emit(FerSplitJob j)
+{
+    const uint32_t nu = min(j.head->units, j.tab_cap);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __shared__ uint32_t wtot[SPL_THREADS / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t img[AVCC_IMG];
+    for (uint32_t u = blockIdx.y; u < nu; u += gridDim.y) {
+    const FerAvccUnit rec = j.aunit[u];
+    const uint8_t *pay = j.rng[rec.range & 0xffffu].p + rec.st + 1u;
+    const uint32_t paylen = rec.en - rec.st - 1u, a = (uint32_t)((uintptr_t)pay & 15u), nch = avcc_nch(a, paylen);
+    const unsigned long long uoff = j.tab[u].offset;
+    for (uint32_t chunk = blockIdx.x; chunk < nch; chunk += gridDim.x) {
+        uint4 w;
+        uint32_t V, D;
+        avcc_lane(pay, a, paylen, chunk, tid, w, V, D);
+        const uint32_t K = V & ~D, c = (uint32_t)__popc(K);
+        uint32_t incl = c;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t t = __shfl_up(incl, m);
+            if (lane >= m) incl += t;
+        }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        uint32_t pre = 0u;
+        for (int k = 0; k < wave; k++) pre += wtot[k];
+        const uint32_t n = wtot[0] + wtot[1] + wtot[2] + wtot[3];  // the chunk's surviving bytes
+        // the chunk's span of the store: [o, o + n), staged in img at [sh, sh + n) so that 16-byte words line up
+        const uint32_t inb = chunk ? chunk * SPL_CHUNK - a : 0u;  // payload bytes in front of the chunk
+        const unsigned long long o = uoff + (inb - j.acin[rec.choff + chunk]);
+        const uint32_t sh = (uint32_t)o & 15u;
+        {
+            uint32_t p = sh + pre + incl - c;
+            const uint32_t x[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                if (K >> k & 1u) img[p++] = (uint8_t)(x[k >> 2] >> (8 * (k & 3)));
+        }
+        __syncthreads();
+        const unsigned long long g0 = o - sh;  // a multiple of 16
+        const uint32_t nwords = (sh + n + 15u) >> 4;
+        for (uint32_t q = tid; q < nwords; q += SPL_THREADS) {
+            const uint32_t lo = q << 4, hi = lo + 16u;
+            if (lo >= sh && hi <= sh + n && g0 + hi <= j.cap) {
+                *(uint4 *)(j.dst + g0 + lo) = *(const uint4 *)(img + lo);
+            } else {
+                for (uint32_t k = max(lo, sh); k < min(hi, sh + n); k++)
+                    if (g0 + k < j.cap) j.dst[g0 + k] = img[k];
+            }
+        }
+        __syncthreads();
+    }
+    }
+}
+
+// the launches of a length-prefixed job; gx = workgroups per unit (a unit of more chunks walks them with that stride)
+static void avcc_launch(const FerSplitJob &j, unsigned gx, hipStream_t st)
+{
+    const unsigned gr = (unsigned)((j.n + 63) / 64);
+    hipLaunchKernelGGL(k_avcc_walk, dim3(gr), dim3(64), 0, st, j, 0);
+    hipLaunchKernelGGL(k_avcc_base, dim3(1), dim3(64), 0, st, j);
+    hipLaunchKernelGGL(k_avcc_walk, dim3(gr), dim3(64), 0, st, j, 1);
+    const unsigned gy = (unsigned)std::min<uint32_t>(j.tab_cap, 32768u);  // more units than that: a workgroup takes several
+    hipLaunchKernelGGL(k_avcc_count, dim3(gx, gy), dim3(SPL_THREADS), 0, st, j);
+    hipLaunchKernelGGL(k_avcc_plan, dim3(j.tab_cap), dim3(64), 0, st, j);
+    hipLaunchKernelGGL(k_avcc_index, dim3(1), dim3(64), 0, st, j);
+    hipLaunchKernelGGL(k_avcc_emit, dim3(gx, gy), dim3(SPL_THREADS), 0, st, j);
+    if (j.pref) hipLaunchKernelGGL(k_split_prefix, dim3((j.tab_cap + 3) / 4), dim3(SPL_THREADS), 0, st, j);
+}
+
 // ---- host side
 template <typename T>
 static int split_grow(T **p, size_t *cap, size_t want, bool pinned = false)
@@ -396,9 +690,11 @@ static int split_grow(T **p, size_t *cap, size_t want, bool pinned = false)
 
 void fer_split_free(FerSplit &sp)
 {
-    for (void *p : {(void *)sp.d_rng, (void *)sp.d_rtot, (void *)sp.d_rbase, (void *)sp.d_summ, (void *)sp.d_cin, (void *)sp.d_res, (void *)sp.d_store})
+    for (void *p : {(void *)sp.d_rng, (void *)sp.d_rtot, (void *)sp.d_rbase, (void *)sp.d_summ, (void *)sp.d_cin, (void *)sp.d_res, (void *)sp.d_store, (void *)sp.d_fault,
+                    (void *)sp.d_aunit})
         if (p) hipFree(p);
     if (sp.h_rng) hipHostFree(sp.h_rng);
+    if (sp.h_fault) hipHostFree(sp.h_fault);
     if (sp.h_res) hipHostFree(sp.h_res);
     if (sp.ev0) hipEventDestroy(sp.ev0);
     if (sp.ev1) hipEventDestroy(sp.ev1);
@@ -422,9 +718,10 @@ static int split_grow_table(FerSplit &sp, size_t want)
     return 0;
 }
 
-int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, const size_t *lens, int n, uint8_t *dst, size_t cap)
+int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, const size_t *lens, int n, uint8_t *dst, size_t cap, int length_size)
 {
-    if (n <= 0 || n > 65535) return FERHIP_E_ARG;
+    if (n <= 0 || n > 65535 || (length_size != 0 && length_size != 1 && length_size != 2 && length_size != 4)) return FERHIP_E_ARG;
+    const bool avcc = length_size != 0;
     if (!sp.ev0) CK(hipEventCreate(&sp.ev0));
     if (!sp.ev1) CK(hipEventCreate(&sp.ev1));
     if (sp.rng_cap < (size_t)n) {
@@ -436,6 +733,14 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
             return FERHIP_E_HIP;
         }
         sp.rng_cap = want;
+    }
+    if (avcc && sp.fault_cap < (size_t)n) {
+        size_t c0 = sp.d_fault ? sp.fault_cap : 0, c1 = sp.h_fault ? sp.fault_cap : 0;
+        if (split_grow(&sp.d_fault, &c0, sp.rng_cap) || split_grow(&sp.h_fault, &c1, sp.rng_cap, true)) {
+            sp.fault_cap = 0;
+            return FERHIP_E_HIP;
+        }
+        sp.fault_cap = sp.rng_cap;
     }
     size_t nchunks = 0, nchmax = 1, in_bytes = 0, need = 0;
     for (int s = 0; s < n; s++) {
@@ -452,6 +757,11 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
         need += (len + 15) & ~(size_t)15;
     }
     if (nchunks >> 32) return FERHIP_E_ARG;
+    if (int rc = split_grow_table(sp, std::max<size_t>(sp.tab_cap, std::max<size_t>(64, 4 * (size_t)n)))) return rc;
+    // length-prefixed: a unit's payload is chunked on an image of its own, which costs a unit up to two chunk slots more than
+    // its bytes alone; the slots are 32-bit counts in the arrays of the chunk functions (four to an element)
+    auto avcc_slots = [&]() { return (in_bytes / SPL_CHUNK + 2 * sp.tab_cap + 4) / 4 + 1; };
+    if (avcc) nchunks = avcc_slots();
     if (sp.ch_cap < nchunks) {
         const size_t want = nchunks + nchunks / 4 + 64;
         size_t c0 = sp.d_summ ? sp.ch_cap : 0, c1 = sp.d_cin ? sp.ch_cap : 0;
@@ -472,7 +782,6 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
         }
         sp.store_cap = c;
     }
-    if (int rc = split_grow_table(sp, std::max<size_t>(sp.tab_cap, std::max<size_t>(64, 4 * (size_t)n)))) return rc;
     const unsigned gx = (unsigned)std::min<size_t>(nchmax, 64);  // a range of more chunks walks them with that stride
     FerSplitJob j;
     auto bind = [&]() {
@@ -488,18 +797,39 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
         j.dst = dst ? dst : sp.d_store;
         j.cap = dst ? cap : sp.store_cap - 64;
         j.pref = dst ? nullptr : sp.d_res + sizeof(FerSplitHead) + sp.tab_cap * sizeof(ferhip_nal_unit);
+        j.lsize = length_size;
+        j.aunit = sp.d_aunit;
+        j.acnt = (uint32_t *)sp.d_summ;
+        j.acin = (uint32_t *)sp.d_cin;
+        j.fault = sp.d_fault;
     };
+    auto grow_units = [&]() -> int {  // length-prefixed: one record per table entry
+        if (!avcc || (sp.aunit_cap >= sp.tab_cap && sp.d_aunit)) return 0;
+        size_t c = sp.d_aunit ? sp.aunit_cap : 0;
+        if (split_grow(&sp.d_aunit, &c, sp.tab_cap)) {
+            sp.aunit_cap = 0;
+            return FERHIP_E_HIP;
+        }
+        sp.aunit_cap = c;
+        return 0;
+    };
+    if (int rc = grow_units()) return rc;
     auto fetch = [&]() -> int {  // the totals, the table and (the decoder's jobs) the prefixes in one copy
         const size_t nb = dst ? sizeof(FerSplitHead) + sp.tab_cap * sizeof(ferhip_nal_unit) : split_res_bytes(sp.tab_cap);
         CK(hipMemcpyAsync(sp.h_res, sp.d_res, nb, hipMemcpyDeviceToHost, st));
+        if (avcc) CK(hipMemcpyAsync(sp.h_fault, sp.d_fault, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
         CK(hipStreamSynchronize(st));
         return 0;
     };
     bind();
     CK(hipMemcpyAsync(sp.d_rng, sp.h_rng, sizeof(FerSplitRange) * n, hipMemcpyHostToDevice, st));
     CK(hipEventRecord(sp.ev0, st));
-    split_launch_plan(j, gx, st);
-    split_launch_emit(j, gx, st);
+    if (avcc) {
+        avcc_launch(j, gx, st);
+    } else {
+        split_launch_plan(j, gx, st);
+        split_launch_emit(j, gx, st);
+    }
     CK(hipEventRecord(sp.ev1, st));
     CK(hipGetLastError());
     if (int rc = fetch()) return rc;
@@ -511,26 +841,53 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
     if (more_units || more_store) {  // the plan stands (chunk functions, range bases): only the emit is repeated
         if (more_units)
             if (int rc = split_grow_table(sp, units + units / 4 + 64)) return rc;
-        if (more_store) {
+        auto grow_store = [&](size_t bytes) -> int {
             size_t c = sp.store_cap;
-            if (split_grow(&sp.d_store, &c, total + total / 4 + 4096)) {
+            if (split_grow(&sp.d_store, &c, bytes + bytes / 4 + 4096)) {
                 sp.store_cap = 0;
                 return FERHIP_E_HIP;
             }
             sp.store_cap = c;
+            return 0;
+        };
+        if (more_store)
+            if (int rc = grow_store(total)) return rc;
+        if (avcc && more_units) {  // the records and the chunk slots follow the table
+            if (int rc = grow_units()) return rc;
+            if (sp.ch_cap < avcc_slots()) {
+                const size_t want = avcc_slots();
+                size_t c0 = sp.d_summ ? sp.ch_cap : 0, c1 = sp.d_cin ? sp.ch_cap : 0;
+                if (split_grow(&sp.d_summ, &c0, want) || split_grow(&sp.d_cin, &c1, want)) {
+                    sp.ch_cap = 0;
+                    return FERHIP_E_HIP;
+                }
+                sp.ch_cap = want;
+            }
         }
         bind();
-        hipLaunchKernelGGL(k_split_index, dim3(1), dim3(64), 0, st, j);  // a new table has no totals yet
-        split_launch_emit(j, gx, st);
+        if (avcc) {
+            avcc_launch(j, gx, st);  // the whole job: it is a handful of small launches
+        } else {
+            hipLaunchKernelGGL(k_split_index, dim3(1), dim3(64), 0, st, j);  // a new table has no totals yet
+            split_launch_emit(j, gx, st);
+        }
         CK(hipGetLastError());
         if (int rc = fetch()) return rc;
+        // length-prefixed: the first total covered the units of the old table only, so the store is looked at once more
+        if (avcc && more_units && !dst && (size_t)sp.head()->bytes > sp.store_cap - 64) {
+            if (int rc = grow_store((size_t)sp.head()->bytes)) return rc;
+            bind();
+            avcc_launch(j, gx, st);
+            CK(hipGetLastError());
+            if (int rc = fetch()) return rc;
+        }
     }
     return 0;
 }
 
 // known-answer surface: host ranges through the same kernels, on the null stream with buffers of its own
-extern "C" int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, uint8_t *out,
-                                       size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits)
+static int split_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, int length_size, uint8_t *out,
+                        size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits, int32_t *range_fault)
 {
     if (nunits) *nunits = 0;
     if (!lens || !nunits || n == 0 || n > 65535 || misalign < 0 || misalign > 15 || (!out && cap) || (!units && units_cap)) return FERHIP_E_ARG;
@@ -552,7 +909,7 @@ extern "C" int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, con
         }
         CK(hipMalloc((void **)&dst, std::max<size_t>(cap, 16)));
         if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
-        if (int rc = fer_split_run(sp, nullptr, ptrs.data(), ln.data(), (int)n, dst, cap)) return rc;
+        if (int rc = fer_split_run(sp, nullptr, ptrs.data(), ln.data(), (int)n, dst, cap, length_size)) return rc;
         if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
         return 0;
     };
@@ -573,6 +930,8 @@ extern "C" int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, con
             k++;
         }
         *nunits = k;
+        if (range_fault)
+            for (size_t i = 0; i < n; i++) range_fault[i] = length_size ? sp.h_fault[i] : 0;
         if (k > units_cap || (size_t)sp.head()->bytes > cap) rc = FERHIP_E_ARG;
     }
     for (uint8_t *p : alloc)
@@ -580,4 +939,21 @@ extern "C" int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, con
     if (dst) hipFree(dst);
     fer_split_free(sp);
     return rc;
+}
+
+extern "C" int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, uint8_t *out,
+                                       size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits)
+{
+    return split_blocks(ranges, stride, lens, n, misalign, 0, out, cap, units, units_cap, nunits, nullptr);
+}
+
+extern "C" int ferhip_split_avcc_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, int length_size,
+                                        uint8_t *out, size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits,
+                                        int32_t *range_fault)
+{
+    if (length_size != 1 && length_size != 2 && length_size != 4) {
+        if (nunits) *nunits = 0;
+        return FERHIP_E_ARG;
+    }
+    return split_blocks(ranges, stride, lens, n, misalign, length_size, out, cap, units, units_cap, nunits, range_fault);
 }

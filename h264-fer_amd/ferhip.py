@@ -16,6 +16,8 @@ TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT = 1, 2, 
 RC_CQP, RC_ABR, RC_QUALITY = 0, 1, 2
 QM_SSE, QM_SSIM, QUALITY_RING = 1, 2, 64
 AU_PARAM_SETS = 1  # pack_nal / fetch_nal: SPS and the stream's own PPS in front of every IDR slice
+AU_AVCC = 4        # ... every NAL unit behind its 4-byte big-endian length instead of the start code (FERHIP_AU_AVCC)
+IN_ANNEXB, IN_AVCC = 0, 1  # LiveDecoder.set_input
 _BUF_DTYPE = {1: np.uint8, 2: np.uint16, 3: np.uint32, 4: np.int32, 5: np.int32, 6: np.int16, 7: np.int16,
               8: np.int16, 9: np.uint8, 10: np.uint8, 11: np.uint8, 12: np.uint8, 13: np.uint8, 14: np.int64, 15: np.int32, 16: np.int32,
               17: np.uint64, 18: np.int32, 19: np.int32, 20: np.int32, 21: np.int32, 22: np.int32, 23: np.int32, 24: np.int32,
@@ -134,6 +136,9 @@ def load_library():
     lib.ferhip_pack_nal.argtypes = [vp, i, vp, sz, vp]
     lib.ferhip_fetch_nal.argtypes = [vp, i, vp, sz, vp]
     lib.ferhip_frame_nal_blocks.argtypes = [vp, sz, vp, vp, sz, vp, sz, vp]
+    lib.ferhip_frame_nal_blocks_fmt.argtypes = [vp, sz, vp, vp, sz, i, vp, sz, vp]
+    lib.ferhip_write_avcc_config.argtypes = [vp, i, vp, sz]
+    lib.ferhip_write_avcc_config.restype = sz
     lib.ferhip_get_stats.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_status.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_fill_interpolated.argtypes = [vp]
@@ -158,6 +163,9 @@ def load_library():
     lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
     lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
+    lib.ferhip_split_avcc_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, sz, vp, sz, C.POINTER(sz), vp]
+    lib.ferhip_decs_set_input.argtypes = [vp, i, i]
+    lib.ferhip_decs_set_config.argtypes = [vp, i, vp, sz]
     lib.ferhip_decs_destroy.argtypes = [vp]
     lib.ferhip_decs_destroy.restype = None
     lib.ferhip_y4m_open.argtypes = [C.POINTER(vp), C.c_char_p, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]
@@ -451,6 +459,15 @@ class FerHip:
         m = self.lib.ferhip_write_nal(1, 8, b.ctypes.data, n, o.ctypes.data)
         return sps, bytes(o[:m])
 
+    def avcc_config(self, stream):
+        """ferhip_write_avcc_config: the AVCDecoderConfigurationRecord of a stream (the payload of an avcC box): its SPS and
+        its own PPS, 4-byte NAL lengths"""
+        o = np.empty(256, np.uint8)
+        n = self.lib.ferhip_write_avcc_config(self.ctx, int(stream), o.ctypes.data, o.size)
+        if n == 0:
+            raise FerHipError(f"ferhip_write_avcc_config({stream}) failed")
+        return bytes(o[:n])
+
     def write_nal(self, nal_type, rbsp):
         r = np.frombuffer(rbsp, np.uint8)
         o = np.empty(len(rbsp) * 3 // 2 + 16, np.uint8)
@@ -473,7 +490,8 @@ class FerHip:
 
     def fetch_nal(self, flags=0, cap=None):
         """The last picture of every stream as Annex-B NAL units (waits) -> (list of bytes per stream, b"" for the streams
-        without a picture; NAL unit types, 0 for them).  With AU_PARAM_SETS an IDR entry is SPS + PPS + slice.
+        without a picture; NAL unit types, 0 for them).  With AU_PARAM_SETS an IDR entry is SPS + PPS + slice; with AU_AVCC
+        every unit stands behind its 4-byte length instead of a start code (an MP4 / FLV sample).
         cap: size of the host buffer; None = one that grows to what the pictures need."""
         grow = cap is None
         if grow:
@@ -638,9 +656,10 @@ def cavlc_blocks(coef, nC, max_num_coeff):
     return bits, nb, tc
 
 
-def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5):
+def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5, flags=None):
     """ferhip_frame_nal_blocks on a list of payloads (bytes or uint8 arrays) -> (return code, out [cap] pre-filled with
-    `fill`, index [n + 1] of dtype AU).  cap None = room for every payload with every second byte escaped."""
+    `fill`, index [n + 1] of dtype AU).  cap None = room for every payload with every second byte escaped.
+    flags not None: through ferhip_frame_nal_blocks_fmt (AU_AVCC: lengths instead of start codes)."""
     lib = load_library()
     n = len(payloads)
     lens = np.array([len(p) for p in payloads], np.uint32)
@@ -653,8 +672,12 @@ def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5):
     out = np.full(max(int(cap), 1), fill, np.uint8)
     idx = np.zeros(n + 1, AU)
     nt = np.ascontiguousarray(nal_types, np.int32)
-    rc = lib.ferhip_frame_nal_blocks(src.ctypes.data, stride, lens.ctypes.data, nt.ctypes.data, n, out.ctypes.data, int(cap),
-                                     idx.ctypes.data)
+    if flags is None:
+        rc = lib.ferhip_frame_nal_blocks(src.ctypes.data, stride, lens.ctypes.data, nt.ctypes.data, n, out.ctypes.data, int(cap),
+                                         idx.ctypes.data)
+    else:
+        rc = lib.ferhip_frame_nal_blocks_fmt(src.ctypes.data, stride, lens.ctypes.data, nt.ctypes.data, n, int(flags), out.ctypes.data,
+                                             int(cap), idx.ctypes.data)
     return rc, out, idx
 
 
@@ -679,6 +702,30 @@ def split_nal_blocks_raw(ranges, misalign=0, cap=None, units_cap=None, fill=0xA5
     rc = lib.ferhip_split_nal_blocks(src.ctypes.data, stride, lens.ctypes.data, n, int(misalign), out.ctypes.data, int(cap),
                                      units.ctypes.data, int(units_cap), C.byref(count))
     return rc, out, units[: min(count.value, int(units_cap))], count.value
+
+
+def split_avcc_blocks_raw(ranges, length_size, misalign=0, cap=None, units_cap=None, fill=0xA5):
+    """ferhip_split_avcc_blocks on a list of length-prefixed byte ranges -> (return code, out [cap] pre-filled with `fill`,
+    units [min(count, units_cap)] of dtype NAL_UNIT, true count, range_fault [n] int32).  cap None = room for every range
+    with every unit rounded up to 16; units_cap None = one unit per two bytes."""
+    lib = load_library()
+    n = len(ranges)
+    lens = np.array([len(r) for r in ranges], np.uint32)
+    stride = max(int(lens.max()) if n else 0, 1)
+    src = np.zeros((n, stride), np.uint8)
+    for k, r in enumerate(ranges):
+        src[k, : len(r)] = np.frombuffer(bytes(r), np.uint8) if not isinstance(r, np.ndarray) else r
+    if cap is None:
+        cap = int(sum((int(m) // 3 + 1) * 16 + int(m) for m in lens))
+    if units_cap is None:
+        units_cap = int(sum(int(m) // 2 + 1 for m in lens))
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    units = np.zeros(max(int(units_cap), 1), NAL_UNIT)
+    fault = np.full(max(n, 1), -1, np.int32)
+    count = C.c_size_t(0)
+    rc = lib.ferhip_split_avcc_blocks(src.ctypes.data, stride, lens.ctypes.data, n, int(misalign), int(length_size), out.ctypes.data,
+                                      int(cap), units.ctypes.data, int(units_cap), C.byref(count), fault.ctypes.data)
+    return rc, out, units[: min(count.value, int(units_cap))], count.value, fault[:n]
 
 
 def split_nal_blocks(ranges, misalign=0):
@@ -793,6 +840,17 @@ class LiveDecoder:
         _chk(self.lib.ferhip_decs_set_layout(self.h, int(fmt), int(pitch_y), int(pitch_c)), "ferhip_decs_set_layout")
         self.layout = (int(fmt), int(pitch_y), int(pitch_c))
         self._slot()
+
+    def set_input(self, fmt, length_size=4):
+        """ferhip_decs_set_input: from the next decode() / decode_dev() on the chunks are Annex-B (IN_ANNEXB, the default) or
+        length-prefixed samples (IN_AVCC, every NAL unit behind its big-endian length of 1, 2 or 4 bytes)"""
+        _chk(self.lib.ferhip_decs_set_input(self.h, int(fmt), int(length_size)), "ferhip_decs_set_input")
+
+    def set_config(self, s, record):
+        """ferhip_decs_set_config: the SPS and PPS of an AVCDecoderConfigurationRecord (bytes) to stream s, as if they had
+        arrived in a chunk -> the return code (0, or the FERHIP_E_* an in-band parameter set would have put in status[s])"""
+        r = np.frombuffer(bytes(record), np.uint8)
+        return int(self.lib.ferhip_decs_set_config(self.h, int(s), r.ctypes.data if r.size else None, r.size))
 
     def _slot(self):
         dw, dh = self.win[2:]

@@ -224,8 +224,25 @@ size_t ferhip_write_nal(int nal_ref_idc, int nal_type, const uint8_t *rbsp, size
  * internal device buffer when needed and makes exactly one device-to-host copy of `total` bytes.
  * The parameter sets are built on the host and kept in a small device table that exists only once the flag was used; a
  * stream's row is sent again only when it can have changed (its first use, ferhip_set_rate before the stream's first
- * picture, ferhip_reset_stream). */
+ * picture, ferhip_reset_stream).
+ *
+ * Length-prefixed framing.  With FERHIP_AU_AVCC (alone or with FERHIP_AU_PARAM_SETS) every NAL unit of an entry is written
+ * as a 4-byte big-endian length N followed by the N bytes of the unit, N = 1 header byte + the payload with its emulation
+ * prevention bytes: the NAL framing of ISO/IEC 14496-15 with lengthSizeMinusOne = 3, what an MP4, FLV or Matroska sample
+ * holds.  The length stands where the start code 00 00 00 01 stands, and both are four bytes, so nothing else changes:
+ * index[] of a pack with FERHIP_AU_AVCC equals index[] of the pack of the same picture without it, entry for entry
+ * (offset, bytes, nal_type, and index[S]), the 16-byte slot rule and the overflow rule are the same, and the two outputs
+ * differ only in those 4-byte prefixes.  With FERHIP_AU_PARAM_SETS the SPS, the stream's PPS and the IDR slice each carry
+ * their own length inside the one entry.  A context may be packed in both framings alternately, as it may be packed
+ * repeatedly.  (The flag's value is 4: the value 2 was already pinned as an invalid flag by the suite.)
+ * ferhip_write_avcc_config (host): the AVCDecoderConfigurationRecord of stream s for the avcC box -- configurationVersion 1,
+ * AVCProfileIndication, profile_compatibility and AVCLevelIndication = the first three bytes of the SPS RBSP, 0xFC | 3
+ * (lengthSizeMinusOne = 3), 0xE0 | 1 (one SPS), the u16 length of the SPS NAL unit and the unit (header byte + escaped
+ * payload: what ferhip_write_nal(1, 7, ...) writes behind its start code), 1 (one PPS), the u16 length of the PPS NAL unit
+ * of ferhip_write_pps_stream(c, s, ...) and the unit.  Returns the bytes written, 0 if cap is too small or s is out of
+ * range.  It follows ferhip_set_display_size and ferhip_set_rate exactly as the SPS and PPS writers do. */
 #define FERHIP_AU_PARAM_SETS 1
+#define FERHIP_AU_AVCC 4
 typedef struct { uint64_t offset; uint32_t bytes; int32_t nal_type; } ferhip_au; /* 16 bytes */
 int ferhip_pack_nal(ferhip_ctx *c, int flags, void *d_dst, size_t cap, ferhip_au *d_index /* [S+1] */);
 int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_au *h_index /* [S+1] */);
@@ -234,6 +251,11 @@ int ferhip_fetch_nal(ferhip_ctx *c, int flags, void *h_dst, size_t cap, ferhip_a
  * the kernels do not write keep the caller's values) and index[n + 1] as above.  n <= 65535. */
 int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
                             size_t n, uint8_t *out, size_t cap, ferhip_au *index /* [n+1] */);
+/* ... with flags: 0 or FERHIP_AU_AVCC (a payload of length 0 then gives 00 00 00 01 and its header byte); any other bit:
+ * FERHIP_E_ARG. */
+int ferhip_frame_nal_blocks_fmt(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,
+                                size_t n, int flags, uint8_t *out, size_t cap, ferhip_au *index /* [n+1] */);
+size_t ferhip_write_avcc_config(ferhip_ctx *c, int s, uint8_t *out, size_t cap);
 
 /* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134), each stream with its own PPS:
  * frames host [T][S][W*H*3/2]; out host [S][out_stride] Annex-B; out_len[S].
@@ -450,8 +472,8 @@ void ferhip_dec_destroy(ferhip_dec *d);
  * width, height: multiples of 16.  max_pictures: slice NAL units per stream and call.  One thread at a time per decoder;
  * it lives on the HIP device that is current at create.
  *
- * chunks[s], lens[s]: whole NAL units of stream s, Annex-B with 4-byte start codes, or NULL / 0 = nothing new for
- * stream s in this call.  out: [max_pictures][nstreams][W*H*3/2] I420, picture k of stream s of this call at
+ * chunks[s], lens[s]: whole NAL units of stream s, Annex-B with 4-byte start codes (or length-prefixed, once
+ * ferhip_decs_set_input asked for it: "length-prefixed input" below), or NULL / 0 = nothing new for stream s in this call.  out: [max_pictures][nstreams][W*H*3/2] I420, picture k of stream s of this call at
  * (k*nstreams + s)*W*H*3/2; out_on_device = 1: out is device memory on the decoder's device; out = NULL: no copy.
  * Slots of stream s from pictures[s] on are not written.  pictures[s] = pictures of stream s decoded in this call.
  * status[s] = 0 or the fault of stream s in this call: FERHIP_E_DEVICE (syntax error in slice data), FERHIP_E_UNSUP
@@ -532,6 +554,52 @@ int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, const uint32_t
 int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out, int out_on_device,
                            int *pictures, int *status);
 int ferhip_decs_timing(ferhip_decs *d, double *t /* [6] */, int reset);
+
+/* ---- length-prefixed (AVCC) input: demuxed samples, in host or in device memory ----
+ * The NAL framing of ISO/IEC 14496-15: every NAL unit is preceded by its length.  The definition, which is the contract of
+ * the host walk and of the kernels alike.  For a range s[0..n) and a length size L in {1, 2, 4}, start with pos = 0 and
+ * repeat while pos + L <= n:
+ *   1. Read len as the big-endian integer at s[pos..pos+L).
+ *   2. Set st = pos + L and en = st + len.
+ *   3. If len == 0, the unit is empty.
+ *   4. If en > n, the unit overruns.
+ *   5. Otherwise the unit is [st, en).  Its header byte is s[st], with nal_ref_idc = (s[st] & 0x7f) >> 5 and
+ *      nal_unit_type = s[st] & 0x1f.
+ *   6. The RBSP is s[st+1..en) without every byte s[p] = 03 that has p - 2 >= st + 1 and s[p-2] = s[p-1] = 0.  This is the
+ *      rule the Annex-B splitter states above.
+ *   7. Set pos = en.
+ * An empty unit, a unit with an empty RBSP (len == 1) or an overrunning unit ends its range: that unit and everything
+ * behind it are dropped, as an empty unit is dropped in Annex-B.  An overrun additionally faults the range; fewer than L
+ * bytes left over at the end of the range also count as an overrun, of a unit that cannot even state its length.
+ * Start-code patterns inside a unit mean nothing: boundaries come from the lengths alone.
+ * The output is the Annex-B splitter's: the same ferhip_nal_unit table, the same store with every unit at the next
+ * multiple of 16, the same prefixes.  The walk itself stops at the unit that ends a range, so neither the table nor the
+ * store holds anything of the units behind it.
+ *
+ * ferhip_decs_set_input(format, length_size): from the next ferhip_decs_decode or ferhip_decs_decode_dev call on, both calls
+ * take chunks of that framing.  FERHIP_E_ARG for an unknown format, and in FERHIP_IN_AVCC for a length_size outside
+ * {1, 2, 4}; in FERHIP_IN_ANNEXB length_size is ignored.  The default is Annex-B, and a decoder on which the call is never
+ * made behaves as before, byte for byte; the two framings may alternate from call to call on one decoder.
+ * ferhip_decs_decode walks the chunks on the host, ferhip_decs_decode_dev by kernels, still with one host synchronisation
+ * for the split unless its table or store has to grow.  Pictures, pictures[], status[] and the isolation rules are those
+ * of the Annex-B calls given the same NAL units.  A chunk that overruns gives status[s] = FERHIP_E_ARG: the units in front
+ * of the overrun decode, the stream restarts at its next IDR slice like after every other fault, the other streams are
+ * untouched.
+ * ferhip_decs_set_config(s, avcc, n): parses an AVCDecoderConfigurationRecord and feeds its SPS and then its PPS units to
+ * stream s exactly as if they had arrived as NAL units in a chunk, with the same outcome (FERHIP_E_UNSUP for an SPS of
+ * another picture size, and the stream then waits for its next IDR slice, ...).  FERHIP_E_ARG if the record is truncated,
+ * its configurationVersion is not 1, it holds no SPS or no PPS, s is out of range, or the decoder is in FERHIP_IN_AVCC and
+ * the record's lengthSizeMinusOne + 1 differs from the decoder's length_size.  It can be called in either input format.
+ * ferhip_split_avcc_blocks: known-answer surface with the contract of ferhip_split_nal_blocks (ranges are copied so that
+ * they end at the end of their allocation, `misalign` bytes past a 16-byte boundary); range_fault[r] (may be NULL) = 1 where
+ * range r overran.  FERHIP_E_ARG also for a length_size outside {1, 2, 4}. */
+#define FERHIP_IN_ANNEXB 0
+#define FERHIP_IN_AVCC 1
+int ferhip_decs_set_input(ferhip_decs *d, int format, int length_size);
+int ferhip_decs_set_config(ferhip_decs *d, int s, const uint8_t *avcc, size_t n);
+int ferhip_split_avcc_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, int length_size,
+                             uint8_t *out, size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits,
+                             int32_t *range_fault /* [n], may be NULL */);
 
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
