@@ -1,5 +1,5 @@
 // fer_ctx.h -- the context of libferhip and the owners of its resources, for the host translation units that drive it
-// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_decode_host.hip, fer_mbunit.hip).
+// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_nalsplit.hip, fer_decode_host.hip, fer_mbunit.hip).
 #pragma once
 #include "fer_internal.h"
 #include <stdio.h>
@@ -15,6 +15,41 @@
             return FERHIP_E_HIP;                                                                      \
         }                                                                                             \
     } while (0)
+
+// One growable buffer of `cap` elements, in device memory or (PINNED) pinned host memory, and its only owner: it is freed
+// with its holder.  reserve(need, want) keeps a buffer that holds `need` elements and otherwise allocates `want` (>= need;
+// the caller's growth rule) afresh: what it held is not copied.  A failed allocation leaves it empty, with HIP's error cleared.
+template <typename T, bool PINNED = false>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    int reserve(size_t need, size_t want = 0)
+    {
+        if (cap >= need && (p || !need)) return 0;
+        release();
+        want = want > need ? want : need;
+        if ((PINNED ? hipHostMalloc((void **)&p, want * sizeof(T)) : hipMalloc((void **)&p, want * sizeof(T))) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return FERHIP_E_HIP;
+        }
+        cap = want;
+        return 0;
+    }
+    void release()
+    {
+        if (p) PINNED ? (void)hipHostFree(p) : (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    operator T *() const { return p; }
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
 
 // A ring of pinned slots that feed asynchronous copies.  A pinned source is read when the copy executes, not when it is
 // enqueued, so a slot is rewritten only after the copy that last used it has run: next() waits for that copy's event,

@@ -204,6 +204,24 @@ static size_t find_zz(const uint8_t *s, size_t from, size_t n, uint8_t t0, uint8
     }
     return (size_t)-1;
 }
+// s[from..en) without every s[p] = 03 with s[p-2] = s[p-1] = 0 and p - 2 >= from (the emulation prevention byte of every
+// 00 00 03), appended at w; returns the new end
+static uint8_t *unescape_rbsp(const uint8_t *s, size_t from, size_t en, uint8_t *w)
+{
+    for (;;) {
+        size_t z = find_zz(s, from, en, 3, 3);
+        if (z == (size_t)-1) break;
+        memcpy(w, s + from, z + 2 - from);
+        w += z + 2 - from;
+        from = z + 3;
+    }
+    if (from < en) {
+        memcpy(w, s + from, en - from);
+        w += en - from;
+    }
+    return w;
+}
+
 // `store` receives the RBSP of every NAL unit back to back (never more than the stream itself) and must outlive `out`
 static void split_stream(const uint8_t *s, size_t n, std::vector<NalRef> &out, std::vector<uint8_t> &store)
 {
@@ -230,40 +248,12 @@ static void split_stream(const uint8_t *s, size_t n, std::vector<NalRef> &out, s
         nal.ref_idc = (s[st] & 0x7f) >> 5;
         nal.type = s[st] & 0x1f;
         uint8_t *w0 = w;
-        size_t from = st + 1;
-        for (;;) {  // drop the emulation prevention byte of every 00 00 03
-            size_t z = find_zz(s, from, en, 3, 3);
-            if (z == (size_t)-1) break;
-            memcpy(w, s + from, z + 2 - from);
-            w += z + 2 - from;
-            from = z + 3;
-        }
-        if (from < en) {
-            memcpy(w, s + from, en - from);
-            w += en - from;
-        }
+        w = unescape_rbsp(s, st + 1, en, w);
         nal.rbsp.p = w0;
         nal.rbsp.n = (size_t)(w - w0);
         if (nal.rbsp.empty()) break;
         out.push_back(std::move(nal));
     }
-}
-
-// s[from..en) without every s[p] = 03 with s[p-2] = s[p-1] = 0 and p - 2 >= from, appended at w; returns the new end
-static uint8_t *unescape_rbsp(const uint8_t *s, size_t from, size_t en, uint8_t *w)
-{
-    for (;;) {
-        size_t z = find_zz(s, from, en, 3, 3);
-        if (z == (size_t)-1) break;
-        memcpy(w, s + from, z + 2 - from);
-        w += z + 2 - from;
-        from = z + 3;
-    }
-    if (from < en) {
-        memcpy(w, s + from, en - from);
-        w += en - from;
-    }
-    return w;
 }
 
 // split a length-prefixed range (every unit behind its length of L = 1, 2 or 4 bytes, big-endian; the definition: ferhip.h)
@@ -1215,14 +1205,11 @@ static void decs_take(ferhip_decs *d, int s, std::vector<const NalRef *> &slices
 
 static int decs_run(ferhip_decs *d, uint8_t *out, int out_on_device, int *pictures, int *status);
 
-extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
-                                  int *pictures, int *status)
+// a call starts from empty results and empty unit lists; returns the bytes of its chunks (NULL / 0 = no chunk)
+static size_t decs_begin_call(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, int *pictures, int *status)
 {
-    if (!d || !chunks || !lens || !pictures || !status || decs_layout_check(d, out_on_device)) return FERHIP_E_ARG;
-    const int S = d->S;
-    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
     size_t bytes = 0;
-    for (int s = 0; s < S; s++) {
+    for (int s = 0; s < d->S; s++) {
         pictures[s] = status[s] = 0;
         d->nals[s].clear();
         d->cursor[s] = 0;
@@ -1230,6 +1217,16 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
         d->overrun[s] = 0;
         if (chunks[s] && lens[s]) bytes += lens[s];
     }
+    return bytes;
+}
+
+extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
+                                  int *pictures, int *status)
+{
+    if (!d || !chunks || !lens || !pictures || !status || decs_layout_check(d, out_on_device)) return FERHIP_E_ARG;
+    const int S = d->S;
+    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
+    const size_t bytes = decs_begin_call(d, chunks, lens, pictures, status);
     const double ts = dec_now();
     {  // NAL splitting: a few threads when there is much of it
         const int nth = bytes < ((size_t)1 << 20) ? 1 : std::max(1, std::min(std::min(S, 16), (int)std::thread::hardware_concurrency()));
@@ -1261,33 +1258,15 @@ extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_ch
     const int S = d->S;
     ferhip_ctx *c = d->ss.c;
     if (hipSetDevice(c->device) != hipSuccess) return FERHIP_E_HIP;
-    bool any = false;
-    for (int s = 0; s < S; s++) {
-        pictures[s] = status[s] = 0;
-        d->nals[s].clear();
-        d->cursor[s] = 0;
-        d->queued[s] = 0;
-        d->overrun[s] = 0;
-        any |= d_chunks[s] && lens[s];
-    }
-    if (!any) return 0;
+    if (!decs_begin_call(d, d_chunks, lens, pictures, status)) return 0;
     // range s = the chunk of stream s: one set of launches splits them all into the decoder's store
     const bool avcc = d->in_format == FERHIP_IN_AVCC;
     int rc = fer_split_run(d->split, c->st, d_chunks, lens, S, nullptr, 0, avcc ? d->length_size : 0);
     if (rc) return rc;
     const FerSplit &sp = d->split;
     for (int s = 0; avcc && s < S; s++) d->overrun[s] = sp.h_fault[s];
-    const ferhip_nal_unit *tab = sp.table();
-    const size_t nu = sp.head()->units;
     d->whole.clear();
-    uint32_t cut = ~0u;
-    for (size_t k = 0; k < nu; k++) {
-        const ferhip_nal_unit &u = tab[k];
-        if (u.range == cut) continue;
-        if (u.bytes == 0) {  // a unit without payload ends its stream's chunk (split_stream)
-            cut = u.range;
-            continue;
-        }
+    rc = fer_split_each_unit(sp, [&](size_t k, const ferhip_nal_unit &u) -> int {
         NalRef n;
         n.type = u.nal_type;
         n.ref_idc = u.ref_idc;
@@ -1304,7 +1283,9 @@ extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_ch
             n.rbsp.n = n.dev_n;
         }
         d->nals[u.range].push_back(n);
-    }
+        return 0;
+    });
+    if (rc) return rc;
     d->ss.dev_rbsp = sp.d_store;
     return decs_run(d, out, out_on_device, pictures, status);
 }

@@ -21,9 +21,12 @@
 //                output span is stored with 16-byte stores; the ragged bytes at its two ends share a 16-byte word with the
 //                neighbouring chunk and are stored byte-wise.  Chunk 0 also places the parameter sets (where asked for),
 //                the start code -- or the unit's length, which the index holds since k_nal_plan -- and the header byte.  An entry is written only if its 16-byte slots end within `cap`.
-// No workgroup waits for another one: the phases are separate launches on one stream.
+// No workgroup waits for another one: the phases are separate launches on one stream.  The scans (wavefront, workgroup,
+// chunks of a payload) and the store of a span from LDS are fer_scan.h's, shared with fer_nalsplit.hip; what is local is
+// the function (NalCompose) and the byte walk.
 // The host side follows the kernels: the context's buffers and parameter set table, and the three entry points.
 #include "fer_ctx.h"
+#include "fer_scan.h"
 #include <string.h>
 #include <algorithm>
 
@@ -64,16 +67,18 @@ __device__ __forceinline__ uint32_t nal_cnt(const uint4 &g, uint32_t z) { return
 __device__ __forceinline__ uint32_t nal_out(const uint4 &g, uint32_t z) { return (g.w >> (2u * z)) & 3u; }
 
 // f first, then g
-__device__ __forceinline__ uint4 nal_compose(const uint4 &f, const uint4 &g)
-{
-    const uint32_t o0 = f.w & 3u, o1 = (f.w >> 2) & 3u, o2 = (f.w >> 4) & 3u;
-    uint4 r;
-    r.x = f.x + nal_cnt(g, o0);
-    r.y = f.y + nal_cnt(g, o1);
-    r.z = f.z + nal_cnt(g, o2);
-    r.w = nal_out(g, o0) | nal_out(g, o1) << 2 | nal_out(g, o2) << 4;
-    return r;
-}
+struct NalCompose {
+    __device__ __forceinline__ uint4 operator()(const uint4 &f, const uint4 &g) const
+    {
+        const uint32_t o0 = f.w & 3u, o1 = (f.w >> 2) & 3u, o2 = (f.w >> 4) & 3u;
+        uint4 r;
+        r.x = f.x + nal_cnt(g, o0);
+        r.y = f.y + nal_cnt(g, o1);
+        r.z = f.z + nal_cnt(g, o2);
+        r.w = nal_out(g, o0) | nal_out(g, o1) << 2 | nal_out(g, o2) << 4;
+        return r;
+    }
+};
 
 // one byte of writeNAL's loop: returns 1 when an 03 goes in front of b
 __device__ __forceinline__ uint32_t nal_step(uint32_t b, uint32_t &z)
@@ -106,22 +111,6 @@ __device__ __forceinline__ uint4 nal_piece(const uint4 &v, int nvalid)
     return make_uint4(c0, c1, c2, z0 | z1 << 2 | z2 << 4);
 }
 
-__device__ __forceinline__ uint4 nal_shfl_up(const uint4 &f, int m)
-{
-    return make_uint4(__shfl_up(f.x, m), __shfl_up(f.y, m), __shfl_up(f.z, m), __shfl_up(f.w, m));
-}
-
-// inclusive scan over the wavefront, lane order
-__device__ __forceinline__ uint4 nal_wave_scan(uint4 f, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint4 t = nal_shfl_up(f, m);
-        if (lane >= m) f = nal_compose(t, f);
-    }
-    return f;
-}
-
 // length of payload s; never more than its slot holds (a picture that overflowed its RBSP buffer has FER_ERR bit 2 set and
 // a length beyond the slot)
 __device__ __forceinline__ uint32_t nal_len(const FerNalJob &j, int s) { return min(j.lens[s], (uint32_t)j.src_stride); }
@@ -145,10 +134,9 @@ __global__ __launch_bounds__(NAL_THREADS) void k_nal_count(FerNalJob j)
     for (uint32_t chunk = blockIdx.x; chunk < nch; chunk += gridDim.x) {
         int nvalid;
         const uint4 v = nal_load(j, s, len, chunk, tid, nvalid);
-        const uint4 incl = nal_wave_scan(nal_piece(v, nvalid), lane);
-        if (lane == 63) wtot[wave] = incl;
+        wg_put(wtot, wave_scan(nal_piece(v, nvalid), lane, NalCompose()), wave, lane);
         __syncthreads();
-        if (tid == 0) j.summ[(size_t)s * j.nchmax + chunk] = nal_compose(nal_compose(wtot[0], wtot[1]), nal_compose(wtot[2], wtot[3]));
+        if (tid == 0) j.summ[(size_t)s * j.nchmax + chunk] = wg_total(wtot, NalCompose());
         __syncthreads();
     }
 }
@@ -175,21 +163,13 @@ __global__ __launch_bounds__(64) void k_nal_plan(FerNalJob j)
         return;
     }
     const uint32_t nch = (len + NAL_CHUNK - 1) / NAL_CHUNK;
-    uint32_t z = 0u, base = 0u;  // the counter and the 03 bytes in front of the block of 64 chunks
-    for (uint32_t i0 = 0; i0 < nch; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        const uint4 f = i < nch ? j.summ[(size_t)s * j.nchmax + i] : nal_identity();
-        const uint4 incl = nal_wave_scan(f, lane);
-        uint4 excl = nal_shfl_up(incl, 1);
-        if (lane == 0) excl = nal_identity();
-        if (i < nch) j.cin[(size_t)s * j.nchmax + i] = make_uint2(nal_out(excl, z), base + nal_cnt(excl, z));
-        const uint4 tot = make_uint4(__shfl(incl.x, 63), __shfl(incl.y, 63), __shfl(incl.z, 63), __shfl(incl.w, 63));
-        base += nal_cnt(tot, z);
-        z = nal_out(tot, z);
-    }
+    // a payload starts from counter 0: what comes into a chunk is the function in front of it at that state
+    const uint4 tot = carry_scan(
+        nch, lane, nal_identity(), NalCompose(), [&](uint32_t i) { return j.summ[(size_t)s * j.nchmax + i]; },
+        [&](uint32_t i, const uint4 &in) { j.cin[(size_t)s * j.nchmax + i] = make_uint2(nal_out(in, 0u), nal_cnt(in, 0u)); });
     if (lane == 0) {
         const uint32_t ps = (j.ps && type == FERHIP_NAL_IDR) ? j.ps[(size_t)s * FER_NAL_PS_ROW + FER_NAL_PS_ROW - 1] : 0u;
-        j.ent[s] = make_uint2(ps + 5u + len + base, (uint32_t)type);
+        j.ent[s] = make_uint2(ps + 5u + len + nal_cnt(tot, 0u), (uint32_t)type);
     }
 }
 
@@ -202,12 +182,7 @@ __global__ __launch_bounds__(64) void k_nal_index(FerNalJob j)
         const int s = s0 + lane;
         const uint2 e = s < j.n ? j.ent[s] : make_uint2(0u, 0u);
         const unsigned long long r = ((unsigned long long)e.x + 15ull) & ~15ull;
-        unsigned long long incl = r;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned long long t = __shfl_up(incl, m);
-            if (lane >= m) incl += t;
-        }
+        const unsigned long long incl = wave_scan(r, lane, ScanAdd());
         const unsigned long long off = run + incl - r;
         if (s < j.n) {
             ferhip_au a;
@@ -243,17 +218,15 @@ __global__ __launch_bounds__(NAL_THREADS) void k_nal_emit(FerNalJob j)
     for (uint32_t chunk = blockIdx.x; chunk < nch; chunk += gridDim.x) {
         int nvalid;
         const uint4 v = nal_load(j, s, len, chunk, tid, nvalid);
-        const uint4 incl = nal_wave_scan(nal_piece(v, nvalid), lane);
-        if (lane == 63) wtot[wave] = incl;
-        uint4 excl = nal_shfl_up(incl, 1);
-        if (lane == 0) excl = nal_identity();
+        const uint4 incl = wave_scan(nal_piece(v, nvalid), lane, NalCompose());
+        wg_put(wtot, incl, wave, lane);
+        uint4 excl = wave_excl(incl, lane, nal_identity());
         // chunk 0 starts from counter 0 with nothing inserted in front of it
         const uint2 cin = chunk ? j.cin[(size_t)s * j.nchmax + chunk] : make_uint2(0u, 0u);
         __syncthreads();
-        uint4 pre = nal_identity();
-        for (int w = 0; w < wave; w++) pre = nal_compose(pre, wtot[w]);
-        excl = nal_compose(pre, excl);
-        const uint4 tot = nal_compose(nal_compose(wtot[0], wtot[1]), nal_compose(wtot[2], wtot[3]));
+        const uint4 pre = wg_front(wtot, wave, nal_identity(), NalCompose());
+        const uint4 tot = wg_total(wtot, NalCompose());
+        excl = NalCompose()(pre, excl);
         // the chunk's span of the output: [a, a + n), staged in img at [sh, sh + n) so that 16-byte words line up
         const uint32_t head = chunk ? 0u : pslen + 5u;
         const unsigned long long a = au.offset + (chunk ? (unsigned long long)pslen + 5ull + (unsigned long long)chunk * NAL_CHUNK + cin.y : 0ull);
@@ -297,16 +270,7 @@ __global__ __launch_bounds__(NAL_THREADS) void k_nal_emit(FerNalJob j)
 #undef NAL_DWORD
         }
         __syncthreads();
-        uint8_t *dst = j.dst + (a - sh);  // 16-byte aligned
-        const uint32_t nwords = (sh + n + 15u) >> 4;
-        for (uint32_t w = tid; w < nwords; w += NAL_THREADS) {
-            const uint32_t lo = w << 4, hi = lo + 16u;
-            if (lo >= sh && hi <= sh + n) {
-                *(uint4 *)(dst + lo) = *(const uint4 *)(img + lo);
-            } else {
-                for (uint32_t k = max(lo, sh); k < min(hi, sh + n); k++) dst[k] = img[k];
-            }
-        }
+        store_span<NAL_THREADS>(j.dst + (a - sh), img, sh, sh + n);  // the entry's slots end within cap (above): nothing to cut
         __syncthreads();
     }
 }
@@ -490,54 +454,43 @@ static int frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32
     }
     const size_t pitch = std::max<size_t>(((size_t)maxlen + 15) & ~(size_t)15, 16);
     const int nchmax = (int)std::max<size_t>(((size_t)maxlen + 4095) / 4096, 1);
-    uint8_t *src = nullptr, *dst = nullptr;
-    uint32_t *dl = nullptr;
-    int32_t *dt = nullptr;
-    uint4 *summ = nullptr;
-    uint2 *cin = nullptr, *ent = nullptr;
-    ferhip_au *idx = nullptr;
-    auto body = [&]() -> int {
-        CK(hipMalloc((void **)&src, pitch * n));
-        CK(hipMalloc((void **)&dst, std::max<size_t>(cap, 16)));
-        CK(hipMalloc((void **)&dl, sizeof(uint32_t) * n));
-        CK(hipMalloc((void **)&dt, sizeof(int32_t) * n));
-        CK(hipMalloc((void **)&summ, sizeof(uint4) * n * nchmax));
-        CK(hipMalloc((void **)&cin, sizeof(uint2) * n * nchmax));
-        CK(hipMalloc((void **)&ent, sizeof(uint2) * n));
-        CK(hipMalloc((void **)&idx, sizeof(ferhip_au) * (n + 1)));
-        CK(hipMemset(src, 0, pitch * n));
-        if (maxlen) CK(hipMemcpy2D(src, pitch, payloads, stride, maxlen, n, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dl, lens, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dt, nal_type, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
-        FerNalJob j;
-        j.src = src;
-        j.src_stride = pitch;
-        j.lens = dl;
-        j.hdr = nullptr;
-        j.types = dt;
-        j.ps = nullptr;
-        j.avcc = (flags & FERHIP_AU_AVCC) ? 1 : 0;
-        j.n = (int)n;
-        j.nchmax = nchmax;
-        j.summ = summ;
-        j.cin = cin;
-        j.ent = ent;
-        j.index = idx;
-        j.dst = dst;
-        j.cap = cap;
-        fer_launch_nal_plan(j, nullptr);
-        fer_launch_nal_emit(j, nullptr);
-        CK(hipGetLastError());
-        CK(hipDeviceSynchronize());
-        if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(index, idx, sizeof(ferhip_au) * (n + 1), hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    for (void *p : {(void *)src, (void *)dst, (void *)dl, (void *)dt, (void *)summ, (void *)cin, (void *)ent, (void *)idx})
-        if (p) hipFree(p);
-    return rc;
+    DevBuf<uint8_t> src, dst;
+    DevBuf<uint32_t> dl;
+    DevBuf<int32_t> dt;
+    DevBuf<uint4> summ;
+    DevBuf<uint2> cin, ent;
+    DevBuf<ferhip_au> idx;
+    if (src.reserve(pitch * n) || dst.reserve(std::max<size_t>(cap, 16)) || dl.reserve(n) || dt.reserve(n) || summ.reserve(n * nchmax) ||
+        cin.reserve(n * nchmax) || ent.reserve(n) || idx.reserve(n + 1))
+        return FERHIP_E_HIP;
+    CK(hipMemset(src, 0, pitch * n));
+    if (maxlen) CK(hipMemcpy2D(src, pitch, payloads, stride, maxlen, n, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dl, lens, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dt, nal_type, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
+    FerNalJob j;
+    j.src = src;
+    j.src_stride = pitch;
+    j.lens = dl;
+    j.hdr = nullptr;
+    j.types = dt;
+    j.ps = nullptr;
+    j.avcc = (flags & FERHIP_AU_AVCC) ? 1 : 0;
+    j.n = (int)n;
+    j.nchmax = nchmax;
+    j.summ = summ;
+    j.cin = cin;
+    j.ent = ent;
+    j.index = idx;
+    j.dst = dst;
+    j.cap = cap;
+    fer_launch_nal_plan(j, nullptr);
+    fer_launch_nal_emit(j, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(index, idx, sizeof(ferhip_au) * (n + 1), hipMemcpyDeviceToHost));
+    return 0;  // the temporaries go with their owners
 }
 
 extern "C" int ferhip_frame_nal_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type,

@@ -3,6 +3,7 @@
 // device store.
 #pragma once
 #include "fer_ctx.h"
+#include <new>
 
 #pragma GCC visibility push(hidden)
 
@@ -24,29 +25,34 @@ struct FerSplitHead {  // the totals of a job, in front of the table
     uint32_t units, pad;
 };
 
-// The buffers of a splitter.  Everything grows to the largest job seen and stays; one job at a time.
+// The buffers of a splitter, each with its own capacity (DevBuf, fer_ctx.h).  Everything grows to the largest job seen and
+// stays; one job at a time.  The buffers go with the splitter (their own destructors), the two events by its destructor: the
+// splitter's device must be current where it is destroyed.
 struct FerSplit {
-    FerSplitRange *d_rng = nullptr, *h_rng = nullptr;  // device / pinned [rng_cap]
-    uint2 *d_rtot = nullptr;                           // [rng_cap] units and bytes of every range
-    FerSplitBase *d_rbase = nullptr;                   // [rng_cap]
-    size_t rng_cap = 0;
-    uint4 *d_summ = nullptr, *d_cin = nullptr;         // [ch_cap] one summary per 4096-byte chunk, and what precedes it
-    size_t ch_cap = 0;
-    uint8_t *d_res = nullptr, *h_res = nullptr;        // device / pinned: FerSplitHead, table [tab_cap], prefixes [tab_cap][PREFIX]
-    size_t tab_cap = 0;
-    uint8_t *d_store = nullptr;                        // the units' RBSP
-    size_t store_cap = 0;
-    int32_t *d_fault = nullptr, *h_fault = nullptr;    // device / pinned [fault_cap]: a length-prefixed range overran
-    size_t fault_cap = 0;
-    FerAvccUnit *d_aunit = nullptr;                    // [aunit_cap >= tab_cap] the units of length-prefixed ranges
-    size_t aunit_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;           // around the launches of a job
+    ~FerSplit()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    DevBuf<FerSplitRange> d_rng;       // [n] the ranges of a job ...
+    PinBuf<FerSplitRange> h_rng;       // ... as the host writes them
+    DevBuf<uint2> d_rtot;              // [n] units and bytes of every range
+    DevBuf<FerSplitBase> d_rbase;      // [n]
+    DevBuf<uint4> d_summ, d_cin;       // one summary per 4096-byte chunk, and what precedes it
+    DevBuf<uint8_t> d_res;             // FerSplitHead, table [tab_cap], prefixes [tab_cap][PREFIX] ...
+    PinBuf<uint8_t> h_res;             // ... and the copy the host reads
+    size_t tab_cap = 0;                // units the two hold
+    DevBuf<uint8_t> d_store;           // the units' RBSP
+    DevBuf<int32_t> d_fault;           // [n]: a length-prefixed range overran
+    PinBuf<int32_t> h_fault;
+    DevBuf<FerAvccUnit> d_aunit;       // [>= tab_cap] the units of length-prefixed ranges
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;           // around the launches of a job's first pass
     double ms = 0;                                     // ... their time, summed over the jobs
     unsigned long long in_bytes = 0;                   // input bytes of those jobs
     // the last job's result (pinned memory, valid until the next job)
-    const FerSplitHead *head() const { return (const FerSplitHead *)h_res; }
-    const ferhip_nal_unit *table() const { return (const ferhip_nal_unit *)(h_res + sizeof(FerSplitHead)); }
-    const uint8_t *prefix(size_t k) const { return h_res + sizeof(FerSplitHead) + tab_cap * sizeof(ferhip_nal_unit) + k * FER_SPLIT_PREFIX; }
+    const FerSplitHead *head() const { return (const FerSplitHead *)h_res.p; }
+    const ferhip_nal_unit *table() const { return (const ferhip_nal_unit *)(h_res.p + sizeof(FerSplitHead)); }
+    const uint8_t *prefix(size_t k) const { return h_res.p + sizeof(FerSplitHead) + tab_cap * sizeof(ferhip_nal_unit) + k * FER_SPLIT_PREFIX; }
 };
 
 // Splits n ranges (device pointers, NULL / 0 = an empty range) on stream st and waits: afterwards table() holds head()->units
@@ -57,6 +63,31 @@ struct FerSplit {
 // for a range that overran, and the table holds the units in front of the range's first empty, header-only or overrunning one.
 int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, const size_t *lens, int n, uint8_t *dst, size_t cap,
                   int length_size = 0);
-void fer_split_free(FerSplit &sp);
+// Destroys the splitter now, while the caller has its device current, and leaves an empty one that can be used again.
+inline void fer_split_free(FerSplit &sp)
+{
+    sp.~FerSplit();
+    new (&sp) FerSplit();
+}
+
+// The empty-payload cut of split_stream (fer_decode_host.hip), which the device leaves to the host: a unit with bytes == 0
+// ends its range, and the later units of that range are skipped.  f(k, unit) for every entry k of the last job's table that
+// stays, in table order, until one returns non-zero; returns that value, or 0.
+template <typename F>
+static int fer_split_each_unit(const FerSplit &sp, F f)
+{
+    const ferhip_nal_unit *t = sp.table();
+    const size_t nt = sp.head()->units;
+    uint32_t cut = ~0u;  // the table is in range order: one range is cut at a time
+    for (size_t k = 0; k < nt; k++) {
+        if (t[k].range == cut) continue;
+        if (t[k].bytes == 0) {
+            cut = t[k].range;
+            continue;
+        }
+        if (int rc = f(k, t[k])) return rc;
+    }
+    return 0;
+}
 
 #pragma GCC visibility pop

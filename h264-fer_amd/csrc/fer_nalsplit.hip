@@ -11,7 +11,8 @@
 // than the last T at or in front of it, and what a run of bytes does to that state is a function that composes: a scan.
 // A run's function is (units begun, has a T or an H, payload bytes in front of its first T or H -- they belong to the
 // unit that comes in --, is a unit open at its end, that unit's payload bytes so far, the 16-rounded bytes of the units
-// begun and ended inside); see split_compose.
+// begun and ended inside); see SplitCompose.  The scans themselves -- over a wavefront, over the four wavefronts of a
+// workgroup, over the chunks of a range -- are fer_scan.h's, shared with fer_nalpack.hip.
 //
 //   k_split_count  grid (chunk, range): a lane takes 16 bytes of the range's 16-byte-aligned image (a range may start
 //                  anywhere: the bytes in front of it and behind it read as ff, which takes part in no pattern) with 8
@@ -19,7 +20,8 @@
 //                  (wavefront scan by shuffles, the four wavefronts through LDS); one function per 4096-byte chunk.
 //   k_split_plan   one wavefront per range composes the chunk functions in order: what comes into every chunk, and the
 //                  range's units and bytes.
-//   k_split_index  one wavefront: exclusive sums over the ranges, and the totals in front of the table.
+//   k_split_index  one wavefront: exclusive sums of the two counts of every range over the ranges (units and bytes; for
+//                  length-prefixed ranges units and chunk slots), and the totals in front of the table.
 //   k_split_emit   grid (chunk, range): every lane recomputes its function, the same scan gives it its unit, that unit's
 //                  offset and the bytes so far; a lane writes the table entry of a unit whose header byte it holds
 //                  (range, type, ref_idc, offset) and the size of a unit that ends in its bytes, and places the payload
@@ -38,18 +40,23 @@
 // chunks of its own 16-byte-aligned image; the walk ends a range at its first empty, header-only or overrunning unit, so
 // the table the device writes is already the one behind the cut.
 //   k_avcc_walk   one lane per range follows the length chain with byte loads, twice: first it counts the range's units and
-//                 their chunks and finds its fault, then (behind k_avcc_base) it writes one record per unit (range, header
-//                 byte, st, en, first chunk slot).
-//   k_avcc_base   one wavefront: exclusive sums of the units and chunks over the ranges, the total of the units.
+//                 their chunks and finds its fault, then (behind k_split_index, which turns the counts into every range's
+//                 first unit and first chunk slot) it writes one record per unit (range, header byte, st, en, first chunk
+//                 slot).
 //   k_avcc_count  grid (chunk, unit): the dropped 03 bytes of every chunk.
 //   k_avcc_plan   one wavefront per unit: exclusive sum of its chunk counts = the 03 bytes in front of every chunk, and the
 //                 unit's RBSP size.
 //   k_avcc_index  one wavefront: exclusive sum of the 16-rounded RBSP sizes over the units = their offsets; the table
 //                 entries and the totals in front of the table.
 //   k_avcc_emit   grid (chunk, unit): the chunk's surviving bytes are compacted in LDS in output order and the span is
-//                 stored with 16-byte stores, its ragged ends byte-wise (k_nal_emit's way); nothing at or behind `cap`.
+//                 stored with 16-byte stores, its ragged ends byte-wise (store_span, as in k_nal_emit); nothing at or behind
+//                 `cap`.
 //   k_split_prefix as above.
+// The host side follows the kernels: fer_split_run sizes the buffers of a FerSplit (each a DevBuf with its own capacity), runs
+// the launches and repeats them while the totals say that the table or the store was too small; the two known-answer entry
+// points are one function.
 #include "fer_nalsplit.h"
+#include "fer_scan.h"
 #include <string.h>
 #include <algorithm>
 
@@ -76,8 +83,11 @@ struct FerSplitJob {
     // length-prefixed ranges
     int lsize;            // bytes of a length: 1, 2 or 4
     FerAvccUnit *aunit;   // [tab_cap]
-    uint32_t *acnt, *acin;  // [chunk slots] dropped 03 bytes of a chunk / in front of it within its unit
     int32_t *fault;       // [n] the range overran
+    // ... keep 32-bit counts in the arrays of the chunk functions, four slots to an element: [chunk slots] the dropped 03
+    // bytes of a chunk / in front of it within its unit
+    __host__ __device__ uint32_t *acnt() const { return (uint32_t *)summ; }
+    __host__ __device__ uint32_t *acin() const { return (uint32_t *)cin; }
 };
 
 // A run's function as a uint4: x = units begun | has an event << 30 | open at the end << 31, y = head bytes, z = bytes of
@@ -89,40 +99,25 @@ __device__ __forceinline__ uint4 split_identity() { return make_uint4(0u, 0u, 0u
 __device__ __forceinline__ uint32_t split_r16(uint32_t v) { return (v + 15u) & ~15u; }
 
 // f first, then g (adjacent runs of one range)
-__device__ __forceinline__ uint4 split_compose(const uint4 &f, const uint4 &g)
-{
-    uint4 r;
-    const bool fopen = (f.x & SPL_OPEN) != 0;
-    r.x = ((f.x & SPL_CNT) + (g.x & SPL_CNT)) | ((f.x | g.x) & SPL_EV);
-    r.y = (f.x & SPL_EV) ? f.y : f.y + g.y;
-    if (g.x & SPL_EV) {  // g's first event ends what f left open; g's own end state stands
-        r.x |= g.x & SPL_OPEN;
-        r.z = g.z;
-        r.w = f.w + g.w + (fopen ? split_r16(f.z + g.y) : 0u);
-    } else {  // g changes nothing: its bytes go to the unit f left open, if any
-        r.x |= f.x & SPL_OPEN;
-        r.z = fopen ? f.z + g.y : 0u;
-        r.w = f.w;
+struct SplitCompose {
+    __device__ __forceinline__ uint4 operator()(const uint4 &f, const uint4 &g) const
+    {
+        uint4 r;
+        const bool fopen = (f.x & SPL_OPEN) != 0;
+        r.x = ((f.x & SPL_CNT) + (g.x & SPL_CNT)) | ((f.x | g.x) & SPL_EV);
+        r.y = (f.x & SPL_EV) ? f.y : f.y + g.y;
+        if (g.x & SPL_EV) {  // g's first event ends what f left open; g's own end state stands
+            r.x |= g.x & SPL_OPEN;
+            r.z = g.z;
+            r.w = f.w + g.w + (fopen ? split_r16(f.z + g.y) : 0u);
+        } else {  // g changes nothing: its bytes go to the unit f left open, if any
+            r.x |= f.x & SPL_OPEN;
+            r.z = fopen ? f.z + g.y : 0u;
+            r.w = f.w;
+        }
+        return r;
     }
-    return r;
-}
-
-__device__ __forceinline__ uint4 split_shfl_up(const uint4 &f, int m)
-{
-    return make_uint4(__shfl_up(f.x, m), __shfl_up(f.y, m), __shfl_up(f.z, m), __shfl_up(f.w, m));
-}
-__device__ __forceinline__ uint4 split_shfl(const uint4 &f, int l) { return make_uint4(__shfl(f.x, l), __shfl(f.y, l), __shfl(f.z, l), __shfl(f.w, l)); }
-
-// inclusive scan over the wavefront, lane order
-__device__ __forceinline__ uint4 split_wave_scan(uint4 f, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint4 t = split_shfl_up(f, m);
-        if (lane >= m) f = split_compose(t, f);
-    }
-    return f;
-}
+};
 
 // the bytes of dword x stand at image positions vd .. vd + 3: those outside [a, end) become ff
 __device__ __forceinline__ uint32_t split_mask(uint32_t x, int vd, int a, int end)
@@ -223,10 +218,9 @@ __global__ __launch_bounds__(SPL_THREADS) void k_split_count(FerSplitJob j)
     for (uint32_t chunk = blockIdx.x; chunk < nch; chunk += gridDim.x) {
         SplitLane L;
         split_lane(r, a, chunk, tid, L);
-        const uint4 incl = split_wave_scan(split_piece(L), lane);
-        if (lane == 63) wtot[wave] = incl;
+        wg_put(wtot, wave_scan(split_piece(L), lane, SplitCompose()), wave, lane);
         __syncthreads();
-        if (tid == 0) j.summ[r.choff + chunk] = split_compose(split_compose(wtot[0], wtot[1]), split_compose(wtot[2], wtot[3]));
+        if (tid == 0) j.summ[r.choff + chunk] = wg_total(wtot, SplitCompose());
         __syncthreads();
     }
 }
@@ -236,16 +230,9 @@ __global__ __launch_bounds__(64) void k_split_plan(FerSplitJob j)
     const FerSplitRange r = j.rng[blockIdx.x];
     const int lane = threadIdx.x;
     const uint32_t nch = split_nch(r, (uint32_t)((uintptr_t)r.p & 15u));
-    uint4 run = split_identity();  // everything in front of the block of 64 chunks
-    for (uint32_t i0 = 0; i0 < nch; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        const uint4 f = i < nch ? j.summ[r.choff + i] : split_identity();
-        const uint4 incl = split_wave_scan(f, lane);
-        uint4 excl = split_shfl_up(incl, 1);
-        if (lane == 0) excl = split_identity();
-        if (i < nch) j.cin[r.choff + i] = split_compose(run, excl);
-        run = split_compose(run, split_shfl(incl, 63));
-    }
+    const uint4 run = carry_scan(
+        nch, lane, split_identity(), SplitCompose(), [&](uint32_t i) { return j.summ[r.choff + i]; },
+        [&](uint32_t i, const uint4 &in) { j.cin[r.choff + i] = in; });
     if (lane == 0) j.rtot[blockIdx.x] = make_uint2(run.x & SPL_CNT, run.w + ((run.x & SPL_OPEN) ? split_r16(run.z) : 0u));
 }
 
@@ -257,17 +244,8 @@ __global__ __launch_bounds__(64) void k_split_index(FerSplitJob j)
     for (int s0 = 0; s0 < j.n; s0 += 64) {
         const int s = s0 + lane;
         const uint2 e = s < j.n ? j.rtot[s] : make_uint2(0u, 0u);
-        unsigned long long ib = e.y;
-        uint32_t iu = e.x;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned long long tb = __shfl_up(ib, m);
-            const uint32_t tu = __shfl_up(iu, m);
-            if (lane >= m) {
-                ib += tb;
-                iu += tu;
-            }
-        }
+        const unsigned long long ib = wave_scan((unsigned long long)e.y, lane, ScanAdd());
+        const uint32_t iu = wave_scan(e.x, lane, ScanAdd());
         if (s < j.n) {
             FerSplitBase b;
             b.bytes = bytes + ib - e.y;
@@ -303,16 +281,13 @@ __global__ __launch_bounds__(SPL_THREADS) void k_split_emit(FerSplitJob j)
         for (int w = tid; w < SPL_IMG / 16; w += SPL_THREADS) msk[w] = 0u;
         SplitLane L;
         split_lane(r, a, chunk, tid, L);
-        const uint4 incl = split_wave_scan(split_piece(L), lane);
-        if (lane == 63) wtot[wave] = incl;
-        uint4 excl = split_shfl_up(incl, 1);
-        if (lane == 0) excl = split_identity();
+        const uint4 incl = wave_scan(split_piece(L), lane, SplitCompose());
+        wg_put(wtot, incl, wave, lane);
+        uint4 excl = wave_excl(incl, lane, split_identity());
         const uint4 cin = j.cin[r.choff + chunk];
         __syncthreads();
-        uint4 pre = cin;
-        for (int w = 0; w < wave; w++) pre = split_compose(pre, wtot[w]);
-        excl = split_compose(pre, excl);  // everything of the range in front of this lane
-        const uint4 tot = split_compose(cin, split_compose(split_compose(wtot[0], wtot[1]), split_compose(wtot[2], wtot[3])));
+        excl = SplitCompose()(wg_front(wtot, wave, cin, SplitCompose()), excl);  // everything of the range in front of this lane
+        const uint4 tot = SplitCompose()(cin, wg_total(wtot, SplitCompose()));
         // the chunk's output lies in [lo, hi) of the range's part of the store; the image starts at lo rounded down to 16
         const uint32_t lo = cin.w + ((cin.x & SPL_OPEN) ? cin.z : 0u);
         const uint32_t hi = tot.w + ((tot.x & SPL_OPEN) ? tot.z : 0u);
@@ -363,6 +338,7 @@ __global__ __launch_bounds__(SPL_THREADS) void k_split_emit(FerSplitJob j)
             if (open && last >= 0 && last < 16 && cur < j.tab_cap) j.tab[cur].bytes = k;
         }
         __syncthreads();
+        // not store_span: several units share a chunk, so [lo, hi) has holes (the rounding behind a unit) besides its two ends
         const unsigned long long g0 = rb.bytes + ibase;  // a multiple of 16
         const uint32_t nwords = min((hi - ibase + 15u) >> 4, (uint32_t)(SPL_IMG / 16));
         for (uint32_t w = tid; w < nwords; w += SPL_THREADS) {
@@ -390,22 +366,12 @@ __global__ __launch_bounds__(SPL_THREADS) void k_split_prefix(FerSplitJob j)
     *(uint4 *)(j.pref + (size_t)u * FER_SPLIT_PREFIX + lane * 16u) = *(const uint4 *)(j.dst + e.offset + lane * 16u);
 }
 
-static void split_launch_plan(const FerSplitJob &j, unsigned gx, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_split_count, dim3(gx, j.n), dim3(SPL_THREADS), 0, st, j);
-    hipLaunchKernelGGL(k_split_plan, dim3(j.n), dim3(64), 0, st, j);
-    hipLaunchKernelGGL(k_split_index, dim3(1), dim3(64), 0, st, j);
-}
-static void split_launch_emit(const FerSplitJob &j, unsigned gx, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_split_emit, dim3(gx, j.n), dim3(SPL_THREADS), 0, st, j);
-    if (j.pref) hipLaunchKernelGGL(k_split_prefix, dim3((j.tab_cap + 3) / 4), dim3(SPL_THREADS), 0, st, j);
-}
-
 
 // ---- length-prefixed ranges
 
-// pass 0 (write == 0): rtot[r] = (units, chunk slots), fault[r]; pass 1: the units' records, from rbase[r] on
+// pass 0 (write == 0): rtot[r] = (units, chunk slots), fault[r]; pass 1: the units' records, from rbase[r] on.  Between the
+// two k_split_index sums rtot as it does for Annex-B ranges: rbase[r].bytes is then the range's first chunk slot (the slots of
+// a job are a 32-bit count, fer_split_run) and head->bytes their total, which nothing reads before k_avcc_index replaces it.
 __global__ __launch_bounds__(64) void k_avcc_walk(FerSplitJob j, int write)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
@@ -451,41 +417,6 @@ __global__ __launch_bounds__(64) void k_avcc_walk(FerSplitJob j, int write)
     if (!write) {
         j.rtot[s] = make_uint2(units, chunks);
         j.fault[s] = (int32_t)fault;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_avcc_base(FerSplitJob j)
-{
-    const int lane = threadIdx.x;
-    uint32_t units = 0u, chunks = 0u;
-    for (int s0 = 0; s0 < j.n; s0 += 64) {
-        const int s = s0 + lane;
-        const uint2 e = s < j.n ? j.rtot[s] : make_uint2(0u, 0u);
-        uint32_t iu = e.x, ic = e.y;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const uint32_t tu = __shfl_up(iu, m), tc = __shfl_up(ic, m);
-            if (lane >= m) {
-                iu += tu;
-                ic += tc;
-            }
-        }
-        if (s < j.n) {
-            FerSplitBase b;
-            b.bytes = chunks + ic - e.y;  // the range's first chunk slot
-            b.units = units + iu - e.x;
-            b.pad = 0;
-            j.rbase[s] = b;
-        }
-        units += __shfl(iu, 63);
-        chunks += __shfl(ic, 63);
-    }
-    if (lane == 0) {
-        FerSplitHead h;
-        h.bytes = 0;
-        h.units = units;
-        h.pad = 0;
-        *j.head = h;
     }
 }
 
@@ -538,9 +469,9 @@ __global__ __launch_bounds__(SPL_THREADS) void k_avcc_count(FerSplitJob j)
         uint32_t c = (uint32_t)__popc(D);
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-        if (lane == 0) wtot[wave] = c;
+        wg_put(wtot, c, wave, lane);  // every lane holds its wavefront's count
         __syncthreads();
-        if (tid == 0) j.acnt[rec.choff + chunk] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        if (tid == 0) j.acnt()[rec.choff + chunk] = wg_total(wtot, ScanAdd());
         __syncthreads();
     }
     }
@@ -554,19 +485,9 @@ __global__ __launch_bounds__(64) void k_avcc_plan(FerSplitJob j)
     const uint8_t *pay = j.rng[rec.range & 0xffffu].p + rec.st + 1u;
     const uint32_t paylen = rec.en - rec.st - 1u, nch = avcc_nch((uint32_t)((uintptr_t)pay & 15u), paylen);
     const int lane = threadIdx.x;
-    uint32_t run = 0u;
-    for (uint32_t i0 = 0; i0 < nch; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        const uint32_t c = i < nch ? j.acnt[rec.choff + i] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const uint32_t t = __shfl_up(incl, m);
-            if (lane >= m) incl += t;
-        }
-        if (i < nch) j.acin[rec.choff + i] = run + incl - c;
-        run += __shfl(incl, 63);
-    }
+    const uint32_t run = carry_scan(
+        nch, lane, 0u, ScanAdd(), [&](uint32_t i) { return j.acnt()[rec.choff + i]; },
+        [&](uint32_t i, uint32_t in) { j.acin()[rec.choff + i] = in; });
     if (lane == 0) j.tab[u].bytes = paylen - run;
 }
 
@@ -579,12 +500,7 @@ __global__ __launch_bounds__(64) void k_avcc_index(FerSplitJob j)
         const uint32_t u = u0 + lane;
         const uint32_t b = u < nu ? j.tab[u].bytes : 0u;
         const unsigned long long r = ((unsigned long long)b + 15ull) & ~15ull;
-        unsigned long long incl = r;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned long long t = __shfl_up(incl, m);
-            if (lane >= m) incl += t;
-        }
+        const unsigned long long incl = wave_scan(r, lane, ScanAdd());
         if (u < nu) {
             const FerAvccUnit rec = j.aunit[u];
             const uint32_t c = rec.range >> 16;
@@ -617,20 +533,14 @@ __global__ __launch_bounds__(SPL_THREADS) void k_avcc_emit(FerSplitJob j)
         uint32_t V, D;
         avcc_lane(pay, a, paylen, chunk, tid, w, V, D);
         const uint32_t K = V & ~D, c = (uint32_t)__popc(K);
-        uint32_t incl = c;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const uint32_t t = __shfl_up(incl, m);
-            if (lane >= m) incl += t;
-        }
-        if (lane == 63) wtot[wave] = incl;
+        const uint32_t incl = wave_scan(c, lane, ScanAdd());
+        wg_put(wtot, incl, wave, lane);
         __syncthreads();
-        uint32_t pre = 0u;
-        for (int k = 0; k < wave; k++) pre += wtot[k];
-        const uint32_t n = wtot[0] + wtot[1] + wtot[2] + wtot[3];  // the chunk's surviving bytes
+        const uint32_t pre = wg_front(wtot, wave, 0u, ScanAdd());
+        const uint32_t n = wg_total(wtot, ScanAdd());  // the chunk's surviving bytes
         // the chunk's span of the store: [o, o + n), staged in img at [sh, sh + n) so that 16-byte words line up
         const uint32_t inb = chunk ? chunk * SPL_CHUNK - a : 0u;  // payload bytes in front of the chunk
-        const unsigned long long o = uoff + (inb - j.acin[rec.choff + chunk]);
+        const unsigned long long o = uoff + (inb - j.acin()[rec.choff + chunk]);
         const uint32_t sh = (uint32_t)o & 15u;
         {
             uint32_t p = sh + pre + incl - c;
@@ -640,82 +550,48 @@ __global__ __launch_bounds__(SPL_THREADS) void k_avcc_emit(FerSplitJob j)
                 if (K >> k & 1u) img[p++] = (uint8_t)(x[k >> 2] >> (8 * (k & 3)));
         }
         __syncthreads();
-        const unsigned long long g0 = o - sh;  // a multiple of 16
-        const uint32_t nwords = (sh + n + 15u) >> 4;
-        for (uint32_t q = tid; q < nwords; q += SPL_THREADS) {
-            const uint32_t lo = q << 4, hi = lo + 16u;
-            if (lo >= sh && hi <= sh + n && g0 + hi <= j.cap) {
-                *(uint4 *)(j.dst + g0 + lo) = *(const uint4 *)(img + lo);
-            } else {
-                for (uint32_t k = max(lo, sh); k < min(hi, sh + n); k++)
-                    if (g0 + k < j.cap) j.dst[g0 + k] = img[k];
-            }
-        }
+        store_span<SPL_THREADS>(j.dst + (o - sh), img, sh, span_cut(o - sh, sh + n, j.cap));
         __syncthreads();
     }
     }
 }
 
-// the launches of a length-prefixed job; gx = workgroups per unit (a unit of more chunks walks them with that stride)
-static void avcc_launch(const FerSplitJob &j, unsigned gx, hipStream_t st)
+// The launches of pass `pass` of a job; gx = workgroups per range (Annex-B) or unit (length-prefixed): one of more chunks
+// walks them with that stride.  A pass behind the first one follows a table or a store that had to grow.  Annex-B: the plan
+// stands (chunk functions, range sums), so only k_split_index -- a new table has no totals yet -- and the emit are repeated.
+// Length-prefixed: the whole job, which is a handful of small launches.
+static void split_launch(const FerSplitJob &j, unsigned gx, int pass, hipStream_t st)
 {
-    const unsigned gr = (unsigned)((j.n + 63) / 64);
-    hipLaunchKernelGGL(k_avcc_walk, dim3(gr), dim3(64), 0, st, j, 0);
-    hipLaunchKernelGGL(k_avcc_base, dim3(1), dim3(64), 0, st, j);
-    hipLaunchKernelGGL(k_avcc_walk, dim3(gr), dim3(64), 0, st, j, 1);
-    const unsigned gy = (unsigned)std::min<uint32_t>(j.tab_cap, 32768u);  // more units than that: a workgroup takes several
-    hipLaunchKernelGGL(k_avcc_count, dim3(gx, gy), dim3(SPL_THREADS), 0, st, j);
-    hipLaunchKernelGGL(k_avcc_plan, dim3(j.tab_cap), dim3(64), 0, st, j);
-    hipLaunchKernelGGL(k_avcc_index, dim3(1), dim3(64), 0, st, j);
-    hipLaunchKernelGGL(k_avcc_emit, dim3(gx, gy), dim3(SPL_THREADS), 0, st, j);
+    if (j.lsize) {
+        const unsigned gr = (unsigned)((j.n + 63) / 64);
+        hipLaunchKernelGGL(k_avcc_walk, dim3(gr), dim3(64), 0, st, j, 0);
+        hipLaunchKernelGGL(k_split_index, dim3(1), dim3(64), 0, st, j);
+        hipLaunchKernelGGL(k_avcc_walk, dim3(gr), dim3(64), 0, st, j, 1);
+        const unsigned gy = (unsigned)std::min<uint32_t>(j.tab_cap, 32768u);  // more units than that: a workgroup takes several
+        hipLaunchKernelGGL(k_avcc_count, dim3(gx, gy), dim3(SPL_THREADS), 0, st, j);
+        hipLaunchKernelGGL(k_avcc_plan, dim3(j.tab_cap), dim3(64), 0, st, j);
+        hipLaunchKernelGGL(k_avcc_index, dim3(1), dim3(64), 0, st, j);
+        hipLaunchKernelGGL(k_avcc_emit, dim3(gx, gy), dim3(SPL_THREADS), 0, st, j);
+    } else {
+        if (pass == 0) {
+            hipLaunchKernelGGL(k_split_count, dim3(gx, j.n), dim3(SPL_THREADS), 0, st, j);
+            hipLaunchKernelGGL(k_split_plan, dim3(j.n), dim3(64), 0, st, j);
+        }
+        hipLaunchKernelGGL(k_split_index, dim3(1), dim3(64), 0, st, j);
+        hipLaunchKernelGGL(k_split_emit, dim3(gx, j.n), dim3(SPL_THREADS), 0, st, j);
+    }
     if (j.pref) hipLaunchKernelGGL(k_split_prefix, dim3((j.tab_cap + 3) / 4), dim3(SPL_THREADS), 0, st, j);
 }
 
 // ---- host side
-template <typename T>
-static int split_grow(T **p, size_t *cap, size_t want, bool pinned = false)
-{
-    if (*cap >= want && *p) return 0;
-    if (*p) pinned ? (void)hipHostFree(*p) : (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if ((pinned ? hipHostMalloc((void **)p, want * sizeof(T)) : hipMalloc((void **)p, want * sizeof(T))) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return FERHIP_E_HIP;
-    }
-    *cap = want;
-    return 0;
-}
-
-void fer_split_free(FerSplit &sp)
-{
-    for (void *p : {(void *)sp.d_rng, (void *)sp.d_rtot, (void *)sp.d_rbase, (void *)sp.d_summ, (void *)sp.d_cin, (void *)sp.d_res, (void *)sp.d_store, (void *)sp.d_fault,
-                    (void *)sp.d_aunit})
-        if (p) hipFree(p);
-    if (sp.h_rng) hipHostFree(sp.h_rng);
-    if (sp.h_fault) hipHostFree(sp.h_fault);
-    if (sp.h_res) hipHostFree(sp.h_res);
-    if (sp.ev0) hipEventDestroy(sp.ev0);
-    if (sp.ev1) hipEventDestroy(sp.ev1);
-    sp = FerSplit();
-}
-
 static size_t split_res_bytes(size_t tab_cap) { return sizeof(FerSplitHead) + tab_cap * (sizeof(ferhip_nal_unit) + FER_SPLIT_PREFIX); }
 
-// the table and the prefix array for tab_cap units, device and pinned
-static int split_grow_table(FerSplit &sp, size_t want)
+// the table and the prefix array for `units` (>= tab_cap) units, device and pinned
+static int split_reserve_table(FerSplit &sp, size_t units)
 {
-    if (sp.tab_cap >= want && sp.d_res && sp.h_res) return 0;
-    size_t c0 = sp.d_res ? sp.tab_cap : 0, c1 = sp.h_res ? sp.tab_cap : 0;
-    c0 = split_res_bytes(c0);
-    c1 = split_res_bytes(c1);
-    if (split_grow(&sp.d_res, &c0, split_res_bytes(want)) || split_grow(&sp.h_res, &c1, split_res_bytes(want), true)) {
-        sp.tab_cap = 0;
-        return FERHIP_E_HIP;
-    }
-    sp.tab_cap = want;
-    return 0;
+    const bool ok = !sp.d_res.reserve(split_res_bytes(units)) && !sp.h_res.reserve(split_res_bytes(units));
+    sp.tab_cap = ok ? units : 0;
+    return ok ? 0 : FERHIP_E_HIP;
 }
 
 int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, const size_t *lens, int n, uint8_t *dst, size_t cap, int length_size)
@@ -724,24 +600,8 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
     const bool avcc = length_size != 0;
     if (!sp.ev0) CK(hipEventCreate(&sp.ev0));
     if (!sp.ev1) CK(hipEventCreate(&sp.ev1));
-    if (sp.rng_cap < (size_t)n) {
-        const size_t want = (size_t)n;
-        size_t c0 = sp.d_rng ? sp.rng_cap : 0, c1 = sp.h_rng ? sp.rng_cap : 0, c2 = sp.d_rtot ? sp.rng_cap : 0, c3 = sp.d_rbase ? sp.rng_cap : 0;
-        if (split_grow(&sp.d_rng, &c0, want) || split_grow(&sp.h_rng, &c1, want, true) || split_grow(&sp.d_rtot, &c2, want) ||
-            split_grow(&sp.d_rbase, &c3, want)) {
-            sp.rng_cap = 0;
-            return FERHIP_E_HIP;
-        }
-        sp.rng_cap = want;
-    }
-    if (avcc && sp.fault_cap < (size_t)n) {
-        size_t c0 = sp.d_fault ? sp.fault_cap : 0, c1 = sp.h_fault ? sp.fault_cap : 0;
-        if (split_grow(&sp.d_fault, &c0, sp.rng_cap) || split_grow(&sp.h_fault, &c1, sp.rng_cap, true)) {
-            sp.fault_cap = 0;
-            return FERHIP_E_HIP;
-        }
-        sp.fault_cap = sp.rng_cap;
-    }
+    if (sp.d_rng.reserve(n) || sp.h_rng.reserve(n) || sp.d_rtot.reserve(n) || sp.d_rbase.reserve(n)) return FERHIP_E_HIP;
+    if (avcc && (sp.d_fault.reserve(n, sp.d_rng.cap) || sp.h_fault.reserve(n, sp.d_rng.cap))) return FERHIP_E_HIP;
     size_t nchunks = 0, nchmax = 1, in_bytes = 0, need = 0;
     for (int s = 0; s < n; s++) {
         const size_t len = ptrs[s] ? lens[s] : 0;
@@ -757,132 +617,63 @@ int fer_split_run(FerSplit &sp, hipStream_t st, const uint8_t *const *ptrs, cons
         need += (len + 15) & ~(size_t)15;
     }
     if (nchunks >> 32) return FERHIP_E_ARG;
-    if (int rc = split_grow_table(sp, std::max<size_t>(sp.tab_cap, std::max<size_t>(64, 4 * (size_t)n)))) return rc;
+    if (int rc = split_reserve_table(sp, std::max<size_t>(sp.tab_cap, std::max<size_t>(64, 4 * (size_t)n)))) return rc;
     // length-prefixed: a unit's payload is chunked on an image of its own, which costs a unit up to two chunk slots more than
-    // its bytes alone; the slots are 32-bit counts in the arrays of the chunk functions (four to an element)
+    // its bytes alone; the slots are 32-bit counts in the arrays of the chunk functions (four to an element), and the records
+    // (one per table entry) and the slots follow the table when it grows
     auto avcc_slots = [&]() { return (in_bytes / SPL_CHUNK + 2 * sp.tab_cap + 4) / 4 + 1; };
     if (avcc) nchunks = avcc_slots();
-    if (sp.ch_cap < nchunks) {
-        const size_t want = nchunks + nchunks / 4 + 64;
-        size_t c0 = sp.d_summ ? sp.ch_cap : 0, c1 = sp.d_cin ? sp.ch_cap : 0;
-        if (split_grow(&sp.d_summ, &c0, want) || split_grow(&sp.d_cin, &c1, want)) {
-            sp.ch_cap = 0;
-            return FERHIP_E_HIP;
-        }
-        sp.ch_cap = want;
-    }
+    if (sp.d_summ.reserve(nchunks, nchunks + nchunks / 4 + 64) || sp.d_cin.reserve(nchunks, nchunks + nchunks / 4 + 64)) return FERHIP_E_HIP;
+    if (avcc && sp.d_aunit.reserve(sp.tab_cap)) return FERHIP_E_HIP;
     // a unit's RBSP is shorter than its bytes in the range, but every unit is rounded up to 16: the store holds the ranges'
     // lengths, which is enough unless units of a few bytes abound; the true total tells, and the emit launch is repeated.
     // k_dec_parse reads whole dwords up to 4 bytes behind a unit: 64 spare bytes like the host path's buffer
-    if (!dst && sp.store_cap < need + 64) {
-        size_t c = sp.d_store ? sp.store_cap : 0;
-        if (split_grow(&sp.d_store, &c, need + need / 4 + 4096)) {
-            sp.store_cap = 0;
-            return FERHIP_E_HIP;
-        }
-        sp.store_cap = c;
-    }
+    if (!dst && sp.d_store.reserve(need + 64, need + need / 4 + 4096)) return FERHIP_E_HIP;
     const unsigned gx = (unsigned)std::min<size_t>(nchmax, 64);  // a range of more chunks walks them with that stride
-    FerSplitJob j;
-    auto bind = [&]() {
+    CK(hipMemcpyAsync(sp.d_rng, sp.h_rng, sizeof(FerSplitRange) * n, hipMemcpyHostToDevice, st));
+    // A pass is the launches and one fetch of the totals; they tell whether the table or the store was too small, and then the
+    // buffers grow and the job is repeated.  Annex-B totals come from the plan and are exact: one repeat at the most.  Length-
+    // prefixed: the first total of the bytes covers the units of the old table only, so behind a table that grew the store is
+    // looked at once more: two repeats at the most.
+    for (int pass = 0;; pass++) {
+        FerSplitJob j;
         j.rng = sp.d_rng;
         j.n = n;
         j.summ = sp.d_summ;
         j.cin = sp.d_cin;
         j.rtot = sp.d_rtot;
         j.rbase = sp.d_rbase;
-        j.head = (FerSplitHead *)sp.d_res;
+        j.head = (FerSplitHead *)sp.d_res.p;
         j.tab = (ferhip_nal_unit *)(sp.d_res + sizeof(FerSplitHead));
         j.tab_cap = (uint32_t)sp.tab_cap;
-        j.dst = dst ? dst : sp.d_store;
-        j.cap = dst ? cap : sp.store_cap - 64;
+        j.dst = dst ? dst : sp.d_store.p;
+        j.cap = dst ? cap : sp.d_store.cap - 64;
         j.pref = dst ? nullptr : sp.d_res + sizeof(FerSplitHead) + sp.tab_cap * sizeof(ferhip_nal_unit);
         j.lsize = length_size;
         j.aunit = sp.d_aunit;
-        j.acnt = (uint32_t *)sp.d_summ;
-        j.acin = (uint32_t *)sp.d_cin;
         j.fault = sp.d_fault;
-    };
-    auto grow_units = [&]() -> int {  // length-prefixed: one record per table entry
-        if (!avcc || (sp.aunit_cap >= sp.tab_cap && sp.d_aunit)) return 0;
-        size_t c = sp.d_aunit ? sp.aunit_cap : 0;
-        if (split_grow(&sp.d_aunit, &c, sp.tab_cap)) {
-            sp.aunit_cap = 0;
-            return FERHIP_E_HIP;
-        }
-        sp.aunit_cap = c;
-        return 0;
-    };
-    if (int rc = grow_units()) return rc;
-    auto fetch = [&]() -> int {  // the totals, the table and (the decoder's jobs) the prefixes in one copy
+        if (pass == 0) CK(hipEventRecord(sp.ev0, st));
+        split_launch(j, gx, pass, st);
+        if (pass == 0) CK(hipEventRecord(sp.ev1, st));
+        CK(hipGetLastError());
+        // the totals, the table and (the decoder's jobs) the prefixes in one copy
         const size_t nb = dst ? sizeof(FerSplitHead) + sp.tab_cap * sizeof(ferhip_nal_unit) : split_res_bytes(sp.tab_cap);
         CK(hipMemcpyAsync(sp.h_res, sp.d_res, nb, hipMemcpyDeviceToHost, st));
         if (avcc) CK(hipMemcpyAsync(sp.h_fault, sp.d_fault, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
         CK(hipStreamSynchronize(st));
-        return 0;
-    };
-    bind();
-    CK(hipMemcpyAsync(sp.d_rng, sp.h_rng, sizeof(FerSplitRange) * n, hipMemcpyHostToDevice, st));
-    CK(hipEventRecord(sp.ev0, st));
-    if (avcc) {
-        avcc_launch(j, gx, st);
-    } else {
-        split_launch_plan(j, gx, st);
-        split_launch_emit(j, gx, st);
-    }
-    CK(hipEventRecord(sp.ev1, st));
-    CK(hipGetLastError());
-    if (int rc = fetch()) return rc;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, sp.ev0, sp.ev1) == hipSuccess) sp.ms += ms;
-    sp.in_bytes += in_bytes;
-    const size_t units = sp.head()->units, total = (size_t)sp.head()->bytes;
-    const bool more_units = units > sp.tab_cap, more_store = !dst && total > sp.store_cap - 64;
-    if (more_units || more_store) {  // the plan stands (chunk functions, range bases): only the emit is repeated
+        if (pass == 0) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, sp.ev0, sp.ev1) == hipSuccess) sp.ms += ms;
+            sp.in_bytes += in_bytes;
+        }
+        const size_t units = sp.head()->units, total = (size_t)sp.head()->bytes;
+        const bool more_units = units > sp.tab_cap, more_store = !dst && total > sp.d_store.cap - 64;
+        if (pass == 2 || (!more_units && !more_store)) return 0;
         if (more_units)
-            if (int rc = split_grow_table(sp, units + units / 4 + 64)) return rc;
-        auto grow_store = [&](size_t bytes) -> int {
-            size_t c = sp.store_cap;
-            if (split_grow(&sp.d_store, &c, bytes + bytes / 4 + 4096)) {
-                sp.store_cap = 0;
-                return FERHIP_E_HIP;
-            }
-            sp.store_cap = c;
-            return 0;
-        };
-        if (more_store)
-            if (int rc = grow_store(total)) return rc;
-        if (avcc && more_units) {  // the records and the chunk slots follow the table
-            if (int rc = grow_units()) return rc;
-            if (sp.ch_cap < avcc_slots()) {
-                const size_t want = avcc_slots();
-                size_t c0 = sp.d_summ ? sp.ch_cap : 0, c1 = sp.d_cin ? sp.ch_cap : 0;
-                if (split_grow(&sp.d_summ, &c0, want) || split_grow(&sp.d_cin, &c1, want)) {
-                    sp.ch_cap = 0;
-                    return FERHIP_E_HIP;
-                }
-                sp.ch_cap = want;
-            }
-        }
-        bind();
-        if (avcc) {
-            avcc_launch(j, gx, st);  // the whole job: it is a handful of small launches
-        } else {
-            hipLaunchKernelGGL(k_split_index, dim3(1), dim3(64), 0, st, j);  // a new table has no totals yet
-            split_launch_emit(j, gx, st);
-        }
-        CK(hipGetLastError());
-        if (int rc = fetch()) return rc;
-        // length-prefixed: the first total covered the units of the old table only, so the store is looked at once more
-        if (avcc && more_units && !dst && (size_t)sp.head()->bytes > sp.store_cap - 64) {
-            if (int rc = grow_store((size_t)sp.head()->bytes)) return rc;
-            bind();
-            avcc_launch(j, gx, st);
-            CK(hipGetLastError());
-            if (int rc = fetch()) return rc;
-        }
+            if (int rc = split_reserve_table(sp, units + units / 4 + 64)) return rc;
+        if (more_store && sp.d_store.reserve(total + 64, total + total / 4 + 4096)) return FERHIP_E_HIP;
+        if (avcc && (sp.d_aunit.reserve(sp.tab_cap) || sp.d_summ.reserve(avcc_slots()) || sp.d_cin.reserve(avcc_slots()))) return FERHIP_E_HIP;
     }
-    return 0;
 }
 
 // known-answer surface: host ranges through the same kernels, on the null stream with buffers of its own
@@ -894,51 +685,32 @@ static int split_blocks(const uint8_t *ranges, size_t stride, const uint32_t *le
     for (size_t i = 0; i < n; i++)
         if (lens[i] > stride || lens[i] > SPL_MAX_LEN || (lens[i] && !ranges)) return FERHIP_E_ARG;
     // every range ends at the end of an allocation of its own and starts `misalign` bytes behind a 16-byte boundary
-    std::vector<uint8_t *> alloc(n, nullptr);
+    std::vector<DevBuf<uint8_t>> alloc(n);
     std::vector<const uint8_t *> ptrs(n, nullptr);
     std::vector<size_t> ln(n, 0);
-    uint8_t *dst = nullptr;
+    DevBuf<uint8_t> dst;
     FerSplit sp;
-    auto body = [&]() -> int {
-        for (size_t i = 0; i < n; i++) {
-            if (!lens[i]) continue;
-            CK(hipMalloc((void **)&alloc[i], (size_t)misalign + lens[i]));
-            CK(hipMemcpy(alloc[i] + misalign, ranges + i * stride, lens[i], hipMemcpyHostToDevice));
-            ptrs[i] = alloc[i] + misalign;
-            ln[i] = lens[i];
-        }
-        CK(hipMalloc((void **)&dst, std::max<size_t>(cap, 16)));
-        if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
-        if (int rc = fer_split_run(sp, nullptr, ptrs.data(), ln.data(), (int)n, dst, cap, length_size)) return rc;
-        if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    int rc = body();
-    if (!rc) {
-        // the empty-payload cut of split_stream: a unit without payload ends its range
-        const ferhip_nal_unit *t = sp.table();
-        const size_t nt = sp.head()->units;
-        size_t k = 0;
-        uint32_t cut = ~0u;
-        for (size_t i = 0; i < nt; i++) {
-            if (t[i].range == cut) continue;
-            if (t[i].bytes == 0) {
-                cut = t[i].range;
-                continue;
-            }
-            if (k < units_cap) units[k] = t[i];
-            k++;
-        }
-        *nunits = k;
-        if (range_fault)
-            for (size_t i = 0; i < n; i++) range_fault[i] = length_size ? sp.h_fault[i] : 0;
-        if (k > units_cap || (size_t)sp.head()->bytes > cap) rc = FERHIP_E_ARG;
+    for (size_t i = 0; i < n; i++) {
+        if (!lens[i]) continue;
+        if (alloc[i].reserve((size_t)misalign + lens[i])) return FERHIP_E_HIP;
+        CK(hipMemcpy(alloc[i] + misalign, ranges + i * stride, lens[i], hipMemcpyHostToDevice));
+        ptrs[i] = alloc[i] + misalign;
+        ln[i] = lens[i];
     }
-    for (uint8_t *p : alloc)
-        if (p) hipFree(p);
-    if (dst) hipFree(dst);
-    fer_split_free(sp);
-    return rc;
+    if (dst.reserve(std::max<size_t>(cap, 16))) return FERHIP_E_HIP;
+    if (cap) CK(hipMemcpy(dst, out, cap, hipMemcpyHostToDevice));
+    if (int rc = fer_split_run(sp, nullptr, ptrs.data(), ln.data(), (int)n, dst, cap, length_size)) return rc;
+    if (cap) CK(hipMemcpy(out, dst, cap, hipMemcpyDeviceToHost));
+    size_t k = 0;
+    fer_split_each_unit(sp, [&](size_t, const ferhip_nal_unit &u) {
+        if (k < units_cap) units[k] = u;
+        k++;
+        return 0;
+    });
+    *nunits = k;
+    if (range_fault)
+        for (size_t i = 0; i < n; i++) range_fault[i] = length_size ? sp.h_fault[i] : 0;
+    return k > units_cap || (size_t)sp.head()->bytes > cap ? FERHIP_E_ARG : 0;
 }
 
 extern "C" int ferhip_split_nal_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, uint8_t *out,

@@ -364,6 +364,35 @@ def test_live_decode_avcc_equals_annexb(pkg, source):
             dec.close()
 
 
+def test_live_decode_dev_grows_the_table_and_the_store(pkg):
+    """2000 access unit delimiters in front of every stream's SPS + PPS + IDR: more units than a fresh splitter's table
+    holds, so the job is repeated; only that second pass sees the bytes of all units -- 16 of the store for every short
+    unit, more than the first store has -- and the job is repeated once more.  The next call finds the buffers as they
+    were left.  Two-byte lengths: units of this fixture are longer than the 255 bytes a one-byte length can state
+    (test_live_decode_avcc_equals_annexb asserts it)."""
+    W, H, units = _sources(pkg)["encoded_48x32"]
+    S, N, L = 2, 2000, 2
+    real = [us[:3] for us in units[:S]]
+    assert all([u[0] & 31 for u in r] == [7, 8, 5] for r in real)
+    assert max(len(u) for r in real for u in r) < 65536
+    aud = (2).to_bytes(L, "big") + b"\x09\xF0"
+    first = [aud * N + _frame(r, L) for r in real]
+    table, total, faults = am.layout([np.frombuffer(c, np.uint8) for c in first], L)
+    need = sum(_r16(len(c)) for c in first)
+    assert len(table) == S * (N + 3) > max(64, 4 * S) and faults == [0] * S, "the first table"
+    assert sum(_r16(t[3]) for t in table[:64]) <= need + need // 4 + 4096 - 64 < total, "the first store: enough for the first pass only"
+    calls = [first, [_frame(us[3:4], L) for us in units[:S]]]
+    dec = pkg.LiveDecoder(S, W, H, 1)
+    dec.set_input(pkg.IN_AVCC, L)
+    host = _run(pkg, dec, calls)
+    dec.close()
+    assert all(n == [1] * S and st == [0] * S for _, n, st in host)
+    dec = pkg.LiveDecoder(S, W, H, 1)
+    dec.set_input(pkg.IN_AVCC, L)
+    _same(host, _run(pkg, dec, calls, device_in=True))
+    dec.close()
+
+
 def test_live_decode_set_config_and_set_input_arguments(pkg):
     W, H, units = _sources(pkg)["encoded_48x32"]
     _, recs = _encode_48x32(pkg)

@@ -203,6 +203,25 @@ def test_live_decode_from_device_memory(pkg, name):
     _same(ref, _run(pkg, calls, 3, P, device_out=True))
 
 
+def test_live_decode_dev_grows_the_table_and_the_store(pkg):
+    """2000 access unit delimiters in front of every stream's first access unit: more units than a fresh splitter's table
+    holds and, at 16 bytes of the store for every six-byte unit, more RBSP than its first store does, so fer_split_run
+    repeats the job with both grown; the next call finds the buffers as they were left"""
+    S, N = 2, 2000
+    aus = _golden_aus(pkg)[:S]
+    first = [b"\x00\x00\x00\x01\x09\xF0" * N + a[0] for a in aus]
+    units, _, total = sm.layout([np.frombuffer(c, np.uint8) for c in first])
+    need = sum((len(c) + 15) & ~15 for c in first)
+    assert len(units) == S * (N + 3) > max(64, 4 * S), "the first table"
+    assert total > need + need // 4 + 4096 - 64, "the first store"
+    calls = [first, [a[1] for a in aus]]
+    host = _run(pkg, calls, S)
+    assert all(n == [1] * S and st == [0] * S for _, n, st in host)
+    dec = pkg.LiveDecoder(S, W, H, 1)
+    _same(host, _run(pkg, calls, S, device_in=True, dec=dec))
+    dec.close()
+
+
 def test_live_decode_dev_arguments(pkg):
     lib = pkg.load_library()
     aus = _golden_aus(pkg)
