@@ -471,7 +471,10 @@ extern "C" int ferhip_set_pictures(ferhip_ctx *c, const ferhip_pic *pics, int fo
     (void)hipSetDevice(c->device);
     int rc = send_pics(c, pics, format);
     if (rc) return rc;
-    fer_launch_pic_ingest(c->d, c->planes[c->cur_set], c->d_pics, format, c->disp_w, c->disp_h, c->st);
+    if (fer_pic_packed(format))
+        fer_launch_pic_ingest_packed(c->d, c->planes[c->cur_set], c->d_pics, format, c->csc, c->disp_w, c->disp_h, c->st);
+    else
+        fer_launch_pic_ingest(c->d, c->planes[c->cur_set], c->d_pics, format, c->disp_w, c->disp_h, c->st);
     CK(hipGetLastError());
     return 0;
 }
@@ -483,9 +486,21 @@ extern "C" int ferhip_get_recon_pictures(ferhip_ctx *c, const ferhip_pic *pics, 
     int rc = send_pics(c, pics, format);
     if (rc) return rc;
     const int win[4] = {0, 0, c->disp_w, c->disp_h};
-    fer_launch_pic_emit(c->d, c->planes[c->cur_set ^ 1], c->d_pics, format, win, c->st);  // the reconstruction is the reference set
+    const uint8_t *set = c->planes[c->cur_set ^ 1];  // the reconstruction is the reference set
+    if (fer_pic_packed(format))
+        fer_launch_pic_emit_packed(c->d, set, c->d_pics, nullptr, c->d.S, nullptr, format, c->csc, 0, 0, win, c->st);
+    else
+        fer_launch_pic_emit(c->d, set, c->d_pics, format, win, c->st);
     CK(hipGetLastError());
     CK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// the matrix of the RGB formats (FERHIP_CSC_*), from the next ferhip_set_pictures / ferhip_get_recon_pictures on
+extern "C" int ferhip_set_csc(ferhip_ctx *c, int matrix)
+{
+    if (!c || (matrix != FERHIP_CSC_BT601 && matrix != FERHIP_CSC_BT709)) return FERHIP_E_ARG;
+    c->csc = matrix;
     return 0;
 }
 

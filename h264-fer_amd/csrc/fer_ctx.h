@@ -120,6 +120,7 @@ struct ferhip_ctx {
     // pictures by descriptor (ferhip_set_pictures, ferhip_get_recon_pictures): the [S] table and its pinned ring, on first use
     ferhip_pic *d_pics = nullptr;  // device [S]
     PinnedRing pic_ring;           // [S] ferhip_pic
+    int csc = FERHIP_CSC_BT601;    // ferhip_set_csc: the matrix of the BGRA / RGBA formats
     // NAL framing on the device (fer_nalpack.hip): everything is allocated on first use, the parameter set table and its
     // pinned ring only once FERHIP_AU_PARAM_SETS was asked for
     bool nal_ready = false;            // a picture call has been made: hdr and out_bytes describe a picture

@@ -519,6 +519,7 @@ struct DecIsolate {
     bool layout_set = false;
     int fmt = FERHIP_FMT_I420;
     uint32_t pitch_y = 0, pitch_c = 0;
+    int csc = FERHIP_CSC_BT601;  // ferhip_decs_set_csc: the matrix of a BGRA / RGBA layout (k_pic_emit_packed)
     bool pitched() const { return layout_set && !(fmt == FERHIP_FMT_I420 && pitch_y == (uint32_t)win[2] && pitch_c == (uint32_t)win[2] / 2u); }
 };
 
@@ -750,7 +751,10 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         bind_planes(c);
         if (iso) {
             uint8_t *to = iso->out_dev ? iso->out : iso->d_stage;
-            if (iso->out && iso->pitched())
+            if (iso->out && iso->pitched() && fer_pic_packed(iso->fmt))
+                fer_launch_pic_emit_packed(d, c->planes[c->cur_set ^ 1], nullptr, iso->d_map + t * S, iso->nmap[t], to, iso->fmt, iso->csc, iso->pitch_y,
+                                           fer_pic_slot_bytes(iso->fmt, iso->pitch_y, iso->pitch_c, (uint32_t)iso->win[3]), iso->win, c->st);
+            else if (iso->out && iso->pitched())
                 fer_launch_pic_emit_slots(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, iso->fmt, iso->pitch_y, iso->pitch_c,
                                           fer_pic_slot_bytes(iso->fmt, iso->pitch_y, iso->pitch_c, (uint32_t)iso->win[3]), iso->win, c->st);
             else if (iso->out && iso->windowed)
@@ -1100,7 +1104,7 @@ extern "C" int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, i
 // when a decode call is made (decs_layout_check), since ferhip_decs_set_display may change it in between
 extern "C" int ferhip_decs_set_layout(ferhip_decs *d, int format, uint32_t pitch_y, uint32_t pitch_c)
 {
-    if (!d || (format != FERHIP_FMT_I420 && format != FERHIP_FMT_NV12)) return FERHIP_E_ARG;
+    if (!d || (format != FERHIP_FMT_I420 && format != FERHIP_FMT_NV12 && !fer_pic_packed(format))) return FERHIP_E_ARG;
     d->iso.layout_set = true;
     d->iso.fmt = format;
     d->iso.pitch_y = pitch_y;
@@ -1108,12 +1112,22 @@ extern "C" int ferhip_decs_set_layout(ferhip_decs *d, int format, uint32_t pitch
     return 0;
 }
 
-// a layout other than the default: device output only, and pitches that hold a row of the current window
-static int decs_layout_check(const ferhip_decs *d, int out_on_device)
+// the matrix of a BGRA / RGBA output layout (FERHIP_CSC_*), from the next decode call on
+extern "C" int ferhip_decs_set_csc(ferhip_decs *d, int matrix)
+{
+    if (!d || (matrix != FERHIP_CSC_BT601 && matrix != FERHIP_CSC_BT709)) return FERHIP_E_ARG;
+    d->iso.csc = matrix;
+    return 0;
+}
+
+// a layout other than the default: device output only, and pitches that hold a row of the current window; a packed format
+// is written in aligned dwords, so its slots must start at multiples of 4
+static int decs_layout_check(const ferhip_decs *d, const uint8_t *out, int out_on_device)
 {
     const DecIsolate &iso = d->iso;
     if (!iso.pitched()) return 0;
     if (!out_on_device) return FERHIP_E_ARG;
+    if (fer_pic_packed(iso.fmt) && ((uintptr_t)out & 3u)) return FERHIP_E_ARG;
     return fer_pic_layout_check(iso.fmt, iso.pitch_y, iso.pitch_c, (uint32_t)iso.win[2]);
 }
 
@@ -1223,7 +1237,7 @@ static size_t decs_begin_call(ferhip_decs *d, const uint8_t *const *chunks, cons
 extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, const size_t *lens, uint8_t *out, int out_on_device,
                                   int *pictures, int *status)
 {
-    if (!d || !chunks || !lens || !pictures || !status || decs_layout_check(d, out_on_device)) return FERHIP_E_ARG;
+    if (!d || !chunks || !lens || !pictures || !status || decs_layout_check(d, out, out_on_device)) return FERHIP_E_ARG;
     const int S = d->S;
     if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
     const size_t bytes = decs_begin_call(d, chunks, lens, pictures, status);
@@ -1254,7 +1268,7 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
 extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out,
                                       int out_on_device, int *pictures, int *status)
 {
-    if (!d || !d_chunks || !lens || !pictures || !status || decs_layout_check(d, out_on_device)) return FERHIP_E_ARG;
+    if (!d || !d_chunks || !lens || !pictures || !status || decs_layout_check(d, out, out_on_device)) return FERHIP_E_ARG;
     const int S = d->S;
     ferhip_ctx *c = d->ss.c;
     if (hipSetDevice(c->device) != hipSuccess) return FERHIP_E_HIP;

@@ -53,3 +53,8 @@ void fer_launch_pic_emit(const FerDev &d, const uint8_t *set, const ferhip_pic *
 // ... or, for the pictures map[j] = (stream, slot), j < n, -> the pitched slot at dst + slot * slot_bytes (Y, then Cb, Cr or CbCr)
 void fer_launch_pic_emit_slots(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, int format, uint32_t pitch_y,
                                uint32_t pitch_c, size_t slot_bytes, const int *win, hipStream_t st);
+// the same two ways for the packed formats (FERHIP_FMT_YUY2, UYVY, BGRA, RGBA), converted in the pass; csc = FERHIP_CSC_*.
+// emit: through d_pics (n = S), or, with d_pics null, the pictures map[j], j < n, to the slots of `pitch` * dh bytes in dst
+void fer_launch_pic_ingest_packed(const FerDev &d, uint8_t *set, const ferhip_pic *d_pics, int format, int csc, int dw, int dh, hipStream_t st);
+void fer_launch_pic_emit_packed(const FerDev &d, const uint8_t *set, const ferhip_pic *d_pics, const int2 *map, int n, uint8_t *dst, int format,
+                                int csc, uint32_t pitch, size_t slot_bytes, const int *win, hipStream_t st);

@@ -114,6 +114,7 @@ def load_library():
     lib.ferhip_get_recon_display.argtypes = [vp, vp, i]
     lib.ferhip_set_pictures.argtypes = [vp, vp, i]
     lib.ferhip_get_recon_pictures.argtypes = [vp, vp, i]
+    lib.ferhip_set_csc.argtypes = [vp, i]
     lib.ferhip_encode_picture.argtypes = [vp, C.POINTER(i), vp, sz, C.POINTER(C.c_uint32)]
     lib.ferhip_encode_picture_dev.argtypes = [vp, C.POINTER(i), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
     lib.ferhip_select_nal_type.argtypes = [vp, C.POINTER(i)]
@@ -160,6 +161,7 @@ def load_library():
     lib.ferhip_decs_get_crop.argtypes = [vp, i, C.POINTER(i)]
     lib.ferhip_decs_set_display.argtypes = [vp, i, i, i, i]
     lib.ferhip_decs_set_layout.argtypes = [vp, i, C.c_uint32, C.c_uint32]
+    lib.ferhip_decs_set_csc.argtypes = [vp, i]
     lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
     lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
@@ -185,6 +187,8 @@ def load_library():
 
 
 FMT_I420, FMT_NV12 = 0, 1
+FMT_YUY2, FMT_UYVY, FMT_BGRA, FMT_RGBA = 4, 5, 8, 9  # packed: one plane, converted on the device (see ferhip.h)
+CSC_BT601, CSC_BT709 = 0, 1
 
 
 class Pic(C.Structure):
@@ -367,6 +371,10 @@ class FerHip:
         if len(pics) != self.S:
             raise ValueError(f"{len(pics)} descriptors for {self.S} streams")
         _chk(self.lib.ferhip_set_pictures(self.ctx, pic_table(pics), int(fmt)), "ferhip_set_pictures")
+
+    def set_csc(self, matrix):
+        """ferhip_set_csc: CSC_BT601 (the default) or CSC_BT709 for set_pictures / get_recon_pictures in FMT_BGRA / FMT_RGBA"""
+        _chk(self.lib.ferhip_set_csc(self.ctx, int(matrix)), "ferhip_set_csc")
 
     def get_recon_pictures(self, pics, fmt=FMT_I420):
         """ferhip_get_recon_pictures: the dw x dh window of the last reconstruction, written through the descriptors"""
@@ -836,10 +844,15 @@ class LiveDecoder:
 
     def set_layout(self, fmt, pitch_y, pitch_c):
         """ferhip_decs_set_layout: from the next decode() on (device output only), every slot of `out` holds its picture as
-        pitched I420 (Y, Cb, Cr) or NV12 (Y, CbCr): pitch_y * dh + (2 or 1) * pitch_c * dh/2 bytes (self.fsz follows)"""
+        pitched I420 (Y, Cb, Cr) or NV12 (Y, CbCr): pitch_y * dh + (2 or 1) * pitch_c * dh/2 bytes (self.fsz follows); or in
+        a packed format (FMT_YUY2, FMT_UYVY, FMT_BGRA, FMT_RGBA): pitch_y * dh bytes, pitch_y and `out` multiples of 4"""
         _chk(self.lib.ferhip_decs_set_layout(self.h, int(fmt), int(pitch_y), int(pitch_c)), "ferhip_decs_set_layout")
         self.layout = (int(fmt), int(pitch_y), int(pitch_c))
         self._slot()
+
+    def set_csc(self, matrix):
+        """ferhip_decs_set_csc: CSC_BT601 (the default) or CSC_BT709 for a FMT_BGRA / FMT_RGBA output layout"""
+        _chk(self.lib.ferhip_decs_set_csc(self.h, int(matrix)), "ferhip_decs_set_csc")
 
     def set_input(self, fmt, length_size=4):
         """ferhip_decs_set_input: from the next decode() / decode_dev() on the chunks are Annex-B (IN_ANNEXB, the default) or
@@ -858,6 +871,9 @@ class LiveDecoder:
             self.fsz = dw * dh * 3 // 2
         else:
             fmt, py, pc = self.layout
+            if fmt in (FMT_YUY2, FMT_UYVY, FMT_BGRA, FMT_RGBA):  # one plane; pitch_c is ignored
+                self.fsz = py * dh
+                return
             self.fsz = py * dh + (1 if fmt == FMT_NV12 else 2) * pc * (dh // 2)
 
     def decode(self, chunks, out=None, dev_lens=None):

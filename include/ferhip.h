@@ -166,6 +166,50 @@ typedef struct ferhip_pic {
 int ferhip_set_pictures(ferhip_ctx *c, const ferhip_pic *pics /* host, [nstreams] */, int format);
 int ferhip_get_recon_pictures(ferhip_ctx *c, const ferhip_pic *pics /* host, [nstreams]; planes are written */, int format);
 
+/* ---- packed 4:2:2 and 32-bit RGB pictures, converted on the device in the same pass ----
+ * A capture card delivers packed 4:2:2, a compositor, a renderer or a tensor pipeline 32-bit RGB, and a display or a model
+ * wants RGB back.  ferhip_set_pictures, ferhip_get_recon_pictures and ferhip_decs_set_layout take four more formats, all
+ * "packed": one plane, so only plane[0] and pitch[0] of a descriptor are looked at.  plane[0] and pitch[0] must be multiples
+ * of 4 and pitch[0] >= the row's bytes (2*dw or 4*dw), reserved must be 0, else FERHIP_E_ARG; plane[0] == NULL still means
+ * that the stream is absent.  dw is even, so a row is a whole number of aligned 4-byte words: exactly the bytes of the rows
+ * are read (in) or written (out), pitch gaps and surroundings are never touched.  The format values 2, 3, 6, 7, 10 and -1
+ * are not formats and stay FERHIP_E_ARG (2, 7 and -1 are pinned as invalid by the tests of the planar formats).
+ *
+ * The conversion, in integers; all shifts are arithmetic (floor), (dw, dh) is the display size.  Limited range only.
+ *   4:2:2 in   Y(x, y) = the luma byte.  With c(p, y) the Cb (or Cr) byte of pixel pair p in row y:
+ *              C(p, q) = (c(p, 2q) + c(p, 2q + 1) + 1) >> 1
+ *   RGB in     (A is ignored)   Y(x, y)  = 16  + ((yr*R + yg*G + yb*B + 128) >> 8)
+ *              Rs, Gs, Bs = the sums of R, G, B over the 2x2 block (2p..2p+1, 2q..2q+1)
+ *                               Cb(p, q) = 128 + ((br*Rs + bg*Gs + bb*Bs + 512) >> 10)
+ *                               Cr(p, q) = 128 + ((rr*Rs + rg*Gs + rb*Bs + 512) >> 10)
+ *              (yr, yg, yb | br, bg, bb | rr, rg, rb) = (66, 129, 25 | -38, -74, 112 | 112, -94, -18)   FERHIP_CSC_BT601
+ *                                                       (47, 157, 16 | -26, -86, 112 | 112, -102, -10)  FERHIP_CSC_BT709
+ *              No clamp is needed: Y stays in 16..235 and chroma in 16..240 for every input.
+ *   padding    then as everywhere: coded sample (x, y) of a plane = converted sample (min(x, pw - 1), min(y, ph - 1)), so
+ *              ferhip_set_pictures fills the picture set exactly as ferhip_set_frames_display would from the converted I420
+ *              picture packed tight.  Quality measurement, the AUTO IDR decision and rate control see the converted pictures.
+ *   4:2:2 out  the luma byte = Y(x, y); rows 2q and 2q + 1 both carry C(p, q).  So out followed by in is the identity.
+ *   RGB out    chroma is nearest, C(x >> 1, y >> 1).  With c = Y - 16, d = Cb - 128, e = Cr - 128:
+ *                               R = clip255((298*c + rv*e + 128) >> 8)
+ *                               G = clip255((298*c + gu*d + gv*e + 128) >> 8)
+ *                               B = clip255((298*c + bu*d + 128) >> 8),   A = 255
+ *              (rv, gu, gv, bu) = (409, -100, -208, 516) FERHIP_CSC_BT601, (459, -55, -136, 541) FERHIP_CSC_BT709
+ * ferhip_set_csc chooses the matrix that ferhip_set_pictures and ferhip_get_recon_pictures of the context use in BGRA and
+ * RGBA, ferhip_decs_set_csc the one of a live decoder's RGB output layout; it applies from the next call on, has no effect
+ * on the other formats, and any other value is FERHIP_E_ARG.  The SPS carries no VUI, so a stream does not announce its
+ * matrix: a receiver has to be told.
+ * ferhip_decs_set_layout with a packed format: a slot is pitch_y * dh bytes and pitch_c is ignored.  pitch_y must be a
+ * multiple of 4 and >= the row bytes of the window current at the decode call, and out must be device memory at a multiple
+ * of 4: else that decode call returns FERHIP_E_ARG before it takes anything.
+ * Host-memory sources, full-range matrices and other chroma filters are not provided. */
+#define FERHIP_FMT_YUY2 4 /* one plane, 2*dw bytes per row: Y0 Cb Y1 Cr per pixel pair */
+#define FERHIP_FMT_UYVY 5 /* one plane, 2*dw bytes per row: Cb Y0 Cr Y1 */
+#define FERHIP_FMT_BGRA 8 /* one plane, 4*dw bytes per row: B G R A per pixel */
+#define FERHIP_FMT_RGBA 9 /* one plane, 4*dw bytes per row: R G B A */
+#define FERHIP_CSC_BT601 0 /* default */
+#define FERHIP_CSC_BT709 1
+int ferhip_set_csc(ferhip_ctx *c, int matrix);
+
 /* ---- RBSP_encode for slice NAL units (F/rbsp_encoding.cpp:139-323) ----
  * nal_type[s]: FERHIP_NAL_IDR / FERHIP_NAL_SLICE / FERHIP_NAL_AUTO / FERHIP_NAL_NONE per stream on input, the
  * type actually used on output (NULL = AUTO for all).  After the call the picture buffers
@@ -507,7 +551,8 @@ void ferhip_dec_destroy(ferhip_dec *d);
  * call is made (pitch_y >= dw; pitch_c >= dw/2 for I420, >= dw for NV12), and a layout other than the default needs
  * out_on_device = 1: else that decode call returns FERHIP_E_ARG before it takes anything.  The default is I420 with pitches
  * equal to the row bytes; (FERHIP_FMT_I420, dw, dw/2) is the default again, and a decoder on which the call is never made
- * behaves as before, byte for byte.
+ * behaves as before, byte for byte.  The packed formats (FERHIP_FMT_YUY2, UYVY, BGRA, RGBA: one plane of pitch_y * dh bytes,
+ * converted on the way out) and ferhip_decs_set_csc are described with ferhip_set_csc above.
  * ferhip_decode_streams and the single-stream ferhip_dec_* always deliver the full coded pictures. */
 typedef struct ferhip_decs ferhip_decs;
 int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, int height, int max_pictures);
@@ -517,6 +562,7 @@ int ferhip_decs_reset_stream(ferhip_decs *d, int s);
 int ferhip_decs_get_crop(ferhip_decs *d, int s, int crop[4] /* left, right, top, bottom */);
 int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, int dh);
 int ferhip_decs_set_layout(ferhip_decs *d, int format, uint32_t pitch_y, uint32_t pitch_c);
+int ferhip_decs_set_csc(ferhip_decs *d, int matrix); /* FERHIP_CSC_*: the matrix of a BGRA / RGBA output layout (see ferhip_set_csc) */
 void ferhip_decs_destroy(ferhip_decs *d);
 
 /* ---- Annex-B input in device memory: the splitter on the device ----
