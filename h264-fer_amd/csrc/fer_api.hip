@@ -312,6 +312,38 @@ static int send_mask(ferhip_ctx *c, const uint8_t *present, const uint8_t **d_ma
     return 0;
 }
 
+// A device buffer on first use.  dalloc clears on the null stream and the buffer's users run on streams that do not wait
+// for that one, so the clear is waited for here.  On failure *p stays null and a later call tries again.
+template <typename T>
+static int dalloc_first_use(ferhip_ctx *c, T **p, size_t n)
+{
+    if (*p) return 0;
+    T *v = nullptr;
+    if (dalloc(c, &v, n) || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        return FERHIP_E_HIP;
+    }
+    *p = v;
+    return 0;
+}
+
+// host pictures [S][fsz] to the same places of a device buffer, on stream st: only the pictures of present streams cross
+// the bus (null = every stream), one copy per run of neighbouring present streams
+static int copy_present_runs(uint8_t *dst, const void *src, size_t fsz, int S, const uint8_t *present, hipStream_t st)
+{
+    for (int s = 0; s < S;) {
+        if (present && !present[s]) {
+            s++;
+            continue;
+        }
+        int e = s;
+        while (e < S && (!present || present[e])) e++;
+        CK(hipMemcpyAsync(dst + (size_t)s * fsz, (const uint8_t *)src + (size_t)s * fsz, (size_t)(e - s) * fsz, hipMemcpyHostToDevice, st));
+        s = e;
+    }
+    return 0;
+}
+
 // present (host [S], or null = every stream): only the pictures of streams with a non-zero byte are read from src
 static int copy_frames(ferhip_ctx *c, uint8_t *set, const uint8_t *src, uint8_t *dst, hipMemcpyKind kind,
                        const uint8_t *present = nullptr)
@@ -368,7 +400,7 @@ extern "C" int ferhip_set_frames_live(ferhip_ctx *c, const void *src, int host, 
     return 0;
 }
 
-// ---- display size: pictures coded at W x H that the SPS crops to dw x dh (fer_pad.hip, fer_headers.hip) ----
+// ---- display size: pictures coded at W x H that the SPS crops to dw x dh (k_pad_ingest of fer_pic.hip, fer_headers.hip) ----
 extern "C" int ferhip_set_display_size(ferhip_ctx *c, int dw, int dh)
 {
     if (!c) return FERHIP_E_ARG;
@@ -397,27 +429,11 @@ extern "C" int ferhip_set_frames_display(ferhip_ctx *c, const void *src, int hos
     (void)hipSetDevice(c->device);
     const FerDev &d = c->d;
     if (!host) return pad_frames(c, (const uint8_t *)src, present);
-    // host pictures: the present ones cross the bus into a device buffer of the display size (one copy per run of
-    // neighbouring present streams), the pad kernel takes them from there
+    // host pictures: the present ones cross the bus into a device buffer, the pad kernel takes them from there
     const size_t fsz = (size_t)c->disp_w * c->disp_h * 3 / 2;
-    if (!c->disp_stage) {
-        if (dalloc(c, &c->disp_stage, d.ysz * 3 / 2 * d.S) || hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
-            (void)hipGetLastError();
-            return FERHIP_E_HIP;
-        }
-    }
-    for (int s = 0; s < d.S;) {
-        if (present && !present[s]) {
-            s++;
-            continue;
-        }
-        int e = s;
-        while (e < d.S && (!present || present[e])) e++;
-        CK(hipMemcpyAsync(c->disp_stage + (size_t)s * fsz, (const uint8_t *)src + (size_t)s * fsz, (size_t)(e - s) * fsz, hipMemcpyHostToDevice,
-                          c->st));
-        s = e;
-    }
-    int rc = pad_frames(c, c->disp_stage, present);
+    int rc = dalloc_first_use(c, &c->disp_stage, d.ysz * 3 / 2 * d.S);
+    if (!rc) rc = copy_present_runs(c->disp_stage, src, fsz, d.S, present, c->st);
+    if (!rc) rc = pad_frames(c, c->disp_stage, present);
     if (rc) return rc;
     CK(hipStreamSynchronize(c->st));
     return 0;
@@ -451,13 +467,7 @@ static int send_pics(ferhip_ctx *c, const ferhip_pic *pics, int format)
     const int S = c->d.S;
     int rc = fer_pic_check(pics, S, format, (uint32_t)c->disp_w);
     if (rc) return rc;
-    if (!c->d_pics) {
-        if (c->pic_ring.create(sizeof(ferhip_pic) * S)) return FERHIP_E_HIP;
-        if (dalloc(c, &c->d_pics, (size_t)S) || hipDeviceSynchronize() != hipSuccess) {  // dalloc clears on the null stream
-            (void)hipGetLastError();
-            return FERHIP_E_HIP;
-        }
-    }
+    if (!c->d_pics && (c->pic_ring.create(sizeof(ferhip_pic) * S) || dalloc_first_use(c, &c->d_pics, (size_t)S))) return FERHIP_E_HIP;
     ferhip_pic *h = (ferhip_pic *)c->pic_ring.next();
     if (!h) return FERHIP_E_HIP;
     for (int s = 0; s < S; s++) h[s] = pics[s].plane[0] ? pics[s] : ferhip_pic{};
@@ -535,8 +545,7 @@ static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *p
         CK(hipStreamCreateWithFlags(&stc, hipStreamNonBlocking));
         bool ok = true;
         for (int i = 0; i < 2 && ok; i++)
-            ok = !dalloc(c, &c->stage[i], bytes) && !ealloc(c, &c->up_done[i]) && !ealloc(c, &c->up_used[i]);
-        if (ok) ok = hipDeviceSynchronize() == hipSuccess;  // dalloc clears on the null stream
+            ok = !dalloc_first_use(c, &c->stage[i], bytes) && !ealloc(c, &c->up_done[i]) && !ealloc(c, &c->up_used[i]);
         if (!ok) {
             (void)hipGetLastError();
             hipStreamDestroy(stc);
@@ -549,25 +558,9 @@ static int upload_frames(ferhip_ctx *c, const void *pinned_src, const uint8_t *p
     const int k = c->up_next;
     CK(hipStreamWaitEvent(c->st_copy, c->up_used[k], 0));  // the repack that last read this slot
     c->up_disp[k] = display;
-    if (!present) {
-        c->up_mask[k].clear();
-        CK(hipMemcpyAsync(c->stage[k], pinned_src, fsz * d.S, hipMemcpyHostToDevice, c->st_copy));
-    } else {
-        // only the pictures of present streams cross the bus, one copy per run of neighbouring present streams; the mask
-        // stays with the staging slot until ferhip_set_frames_uploaded repacks it
-        c->up_mask[k].assign(present, present + d.S);
-        for (int s = 0; s < d.S;) {
-            if (!present[s]) {
-                s++;
-                continue;
-            }
-            int e = s;
-            while (e < d.S && present[e]) e++;
-            CK(hipMemcpyAsync(c->stage[k] + (size_t)s * fsz, (const uint8_t *)pinned_src + (size_t)s * fsz, (size_t)(e - s) * fsz,
-                              hipMemcpyHostToDevice, c->st_copy));
-            s = e;
-        }
-    }
+    c->up_mask[k].clear();  // the mask stays with the staging slot until ferhip_set_frames_uploaded repacks it
+    if (present) c->up_mask[k].assign(present, present + d.S);
+    if (copy_present_runs(c->stage[k], pinned_src, fsz, d.S, present, c->st_copy)) return FERHIP_E_HIP;
     CK(hipEventRecord(c->up_done[k], c->st_copy));
     c->up_next ^= 1;
     c->up_ready++;

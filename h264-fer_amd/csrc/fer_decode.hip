@@ -12,6 +12,8 @@
 //                 (F/mocomp.cpp), dequantisation + inverse transform, clipped reconstruction.
 //   k_dec_intra   intra macroblocks along the anti-diagonal wavefront x + 2y (they read
 //                 reconstructed neighbours): intraPrediction (F/intra.cpp:770) + residual.
+//   k_dec_out     the live decoder's output of whole pictures as tight I420 at a 16-byte aligned address; every other
+//                 output (a window, an unaligned address, a pitched layout, NV12) is k_pic_emit's in fer_pic.hip.
 //
 // Supported syntax: what the reference encoder emits plus intra macroblocks inside P slices and
 // non-zero mb_qp_delta.  All four P sub-macroblock types are parsed (like the reference's DeriveMVs, the first vector
@@ -1126,9 +1128,11 @@ void fer_launch_decode_recon(const FerDev &d, bool anyP, bool anyIntra, hipStrea
     }
 }
 
-// The decoded pictures of one step, from the plane-major picture set `set` ([S] Y, [S] Cb, [S] Cr) into I420 slots of
-// W*H*3/2 bytes: map[j] = (stream, slot), blockIdx.y = j.  Consecutive lanes move consecutive V-sized pieces of a slot
-// (every plane is a multiple of 64 bytes, so a piece never straddles two); no other slot is touched.
+// The decoded pictures of one step, whole and as tight I420, from the plane-major picture set `set` ([S] Y, [S] Cb, [S] Cr)
+// into slots of W*H*3/2 bytes at a 16-byte aligned dst: map[j] = (stream, slot), blockIdx.y = j.  Consecutive lanes move
+// consecutive V-sized pieces of a slot (every plane is a multiple of 64 bytes, so a piece never straddles two); no other slot
+// is touched.  Every other output of the live decoder -- a window, an unaligned dst, pitched slots, NV12 -- is k_pic_emit's
+// (fer_pic.hip).
 template <typename V>
 __global__ __launch_bounds__(256) void k_dec_out(const uint8_t *__restrict__ set, const int2 *__restrict__ map, uint8_t *__restrict__ dst,
                                                  int S, size_t ysz, size_t csz)
@@ -1147,74 +1151,6 @@ __global__ __launch_bounds__(256) void k_dec_out(const uint8_t *__restrict__ set
 void fer_launch_decode_out(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, hipStream_t st)
 {
     if (n <= 0) return;
-    const size_t fsz = d.ysz + 2 * d.csz;
-    if (((uintptr_t)dst & 15) == 0) {
-        const unsigned nb = (unsigned)std::min<size_t>((fsz / 16 + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_dec_out<uint4>, dim3(nb, n), dim3(256), 0, st, set, map, dst, d.S, d.ysz, d.csz);
-    } else {  // a caller's buffer that is not 16-byte aligned (a view into a larger tensor): byte by byte
-        const unsigned nb = (unsigned)std::min<size_t>((fsz + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_dec_out<uint8_t>, dim3(nb, n), dim3(256), 0, st, set, map, dst, d.S, d.ysz, d.csz);
-    }
-}
-
-// The window (x0, y0, dw, dh) of the decoded pictures of one step, as I420 slots of dw*dh*3/2 bytes: a slot is one run of
-// bytes (the rows of a window are packed), at any alignment.  A lane owns one aligned dword of the slot and stores it whole
-// when its four bytes lie in one row of one plane: they are read as the one or two aligned dwords that hold them and shifted
-// into place.  A dword that holds the end of a row and the start of the next, and the bytes in front of the first and behind
-// the last aligned dword of the slot, go byte by byte.  No byte outside the slot is written.
-struct DecWinSrc {
-    const uint8_t *p;  // the sample
-    uint32_t rem;      // samples from it to the end of the window's row
-};
-__device__ __forceinline__ DecWinSrc dec_win_src(const uint8_t *set, int s, int S, uint32_t W, uint32_t ysz, uint32_t x0, uint32_t y0, uint32_t dw,
-                                                 uint32_t wy, uint32_t b)
-{
-    const uint32_t csz = ysz >> 2, wc = wy >> 2;
-    uint32_t pw = dw, PW = W, px = x0, py = y0;
-    const uint8_t *base = set + (size_t)s * ysz;
-    if (b >= wy) {
-        const uint32_t cr = b >= wy + wc ? 1u : 0u;
-        b -= wy + cr * wc;
-        pw = dw >> 1, PW = W >> 1, px = x0 >> 1, py = y0 >> 1;
-        base = set + (size_t)S * ((size_t)ysz + (size_t)cr * csz) + (size_t)s * csz;
-    }
-    const uint32_t r = b / pw, c = b - r * pw;
-    DecWinSrc q;
-    q.p = base + (size_t)(py + r) * PW + px + c;
-    q.rem = pw - c;
-    return q;
-}
-
-__global__ __launch_bounds__(256) void k_dec_out_win(const uint8_t *__restrict__ set, const int2 *__restrict__ map, uint8_t *__restrict__ dst,
-                                                     int S, uint32_t W, uint32_t ysz, uint32_t x0, uint32_t y0, uint32_t dw, uint32_t dh)
-{
-    const int2 m = map[blockIdx.y];
-    const uint32_t wy = dw * dh, ofsz = wy + (wy >> 1);
-    uint8_t *o = dst + (size_t)m.y * ofsz;
-    const uint32_t head = (uint32_t)(0u - (uint32_t)(uintptr_t)o) & 3u;  // bytes in front of the slot's first aligned dword (ofsz >= 6)
-    const uint32_t npiece = 1u + (ofsz - head + 3u) / 4u;                // piece 0 = the head, piece k = dword k - 1
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npiece; k += gridDim.x * blockDim.x) {
-        const uint32_t b0 = k ? head + 4u * (k - 1u) : 0u, b1 = k ? min(b0 + 4u, ofsz) : head;
-        if (b1 - b0 == 4u) {
-            const DecWinSrc q = dec_win_src(set, m.x, S, W, ysz, x0, y0, dw, wy, b0);
-            if (q.rem >= 4u) {
-                const uint32_t sh = (uint32_t)(uintptr_t)q.p & 3u;
-                const uint32_t *a = (const uint32_t *)((uintptr_t)q.p & ~(uintptr_t)3);
-                const uint32_t w0 = a[0], w1 = sh ? a[1] : 0u;  // a[1] holds wanted bytes whenever it is read
-                *(uint32_t *)(o + b0) = __builtin_amdgcn_alignbyte(w1, w0, sh);
-                continue;
-            }
-        }
-#pragma unroll 1
-        for (uint32_t b = b0; b < b1; b++) o[b] = *dec_win_src(set, m.x, S, W, ysz, x0, y0, dw, wy, b).p;
-    }
-}
-
-void fer_launch_decode_out_win(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, const int *win, hipStream_t st)
-{
-    if (n <= 0) return;
-    const size_t ofsz = (size_t)win[2] * win[3] * 3 / 2;
-    const unsigned nb = (unsigned)std::min<size_t>((ofsz / 4 + 2 + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_dec_out_win, dim3(nb, n), dim3(256), 0, st, set, map, dst, d.S, (uint32_t)d.W, (uint32_t)d.ysz, (uint32_t)win[0],
-                       (uint32_t)win[1], (uint32_t)win[2], (uint32_t)win[3]);
+    const unsigned nb = (unsigned)std::min<size_t>(((d.ysz + 2 * d.csz) / 16 + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_dec_out<uint4>, dim3(nb, n), dim3(256), 0, st, set, map, dst, d.S, d.ysz, d.csz);
 }

@@ -498,29 +498,33 @@ static int dec_copy_stream(ferhip_ctx *c, uint8_t *dst, const uint8_t *src, int 
 // Per-stream error isolation of a window (the live decoder, ferhip_decs_*).  Without it the first stream that fails
 // fails the window.  With it a stream's fault ends that stream's part of the window: the faulted picture and the ones
 // after it are not reconstructed, status[s] records the FERHIP_E_* and the other streams go on.  The output then goes
-// through k_dec_out, which writes only the slots of pictures that were decoded.
+// through k_dec_out or k_pic_emit, which write only the slots of pictures that were decoded.
 struct DecIsolate {
     int *status = nullptr;       // [S] 0, or the first fault of stream s in this call
     std::vector<char> stop;      // [S] stream s faulted inside a window: it takes no more pictures in this call
     uint8_t *out = nullptr;      // [max_pictures][S][fsz]: picture k of stream s at (k * S + s) * fsz, or NULL
     bool out_dev = false;        // out is device memory
-    int2 *d_map = nullptr;       // [TWmax][S] device: the (stream, slot) pairs of every step for k_dec_out
+    int2 *d_map = nullptr;       // [TWmax][S] device: the (stream, slot) pairs of every step for the output kernel
     std::vector<int2> map;       // ... host side
     std::vector<int> nmap;       // [TW] pairs per step
     std::vector<size_t> fin;     // host output: slot (k * S + s) of the caller's buffer of every staged picture, in order
     uint8_t *d_stage = nullptr, *h_stage = nullptr;  // host output: the window's pictures, packed, on the device and pinned
     size_t stage_cap = 0;        // pictures
     // ferhip_decs_set_display: the window (x0, y0, dw, dh) of every picture that goes to `out`; ofsz = bytes of one slot
-    bool windowed = false;
     int win[4] = {};
     size_t ofsz = 0;
-    // ferhip_decs_set_layout: the slots of device output are pitched I420 or NV12 (k_pic_emit); layout_set stays false on
-    // a decoder that never makes the call, and the pitches then follow the window
+    // ferhip_decs_set_layout: the slots of device output are pitched I420 or NV12 (k_pic_emit) or a packed format
+    // (k_pic_emit_packed); layout_set stays false on a decoder that never makes the call, and the slots are then tight I420
     bool layout_set = false;
     int fmt = FERHIP_FMT_I420;
     uint32_t pitch_y = 0, pitch_c = 0;
-    int csc = FERHIP_CSC_BT601;  // ferhip_decs_set_csc: the matrix of a BGRA / RGBA layout (k_pic_emit_packed)
-    bool pitched() const { return layout_set && !(fmt == FERHIP_FMT_I420 && pitch_y == (uint32_t)win[2] && pitch_c == (uint32_t)win[2] / 2u); }
+    int csc = FERHIP_CSC_BT601;  // ferhip_decs_set_csc: the matrix of a BGRA / RGBA layout
+    uint32_t row_y() const { return layout_set ? pitch_y : (uint32_t)win[2]; }
+    uint32_t row_c() const { return layout_set ? pitch_c : (uint32_t)win[2] / 2u; }
+    // a layout other than tight I420 slots of the window: it needs device output and a check of its pitches
+    bool own_layout() const { return !(fmt == FERHIP_FMT_I420 && row_y() == (uint32_t)win[2] && row_c() == (uint32_t)win[2] / 2u); }
+    // whole coded pictures as tight I420 at a 16-byte aligned address: k_dec_out's case
+    bool whole(const FerDev &d, const uint8_t *to) const { return !own_layout() && win[2] == d.W && win[3] == d.H && !((uintptr_t)to & 15u); }
 };
 
 // After the parse of an isolated window: find each faulted stream's first faulted picture (B.state[pic * 4 + 3]), drop it
@@ -749,19 +753,19 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
         fer_launch_decode_recon(ds, ss.anyP[t] != 0, true, c->st);
         c->cur_set ^= 1;  // the decoded picture becomes the reference (modificationProcess -> frameDeepCopy)
         bind_planes(c);
-        if (iso) {
+        if (iso && iso->out) {  // (the staged pictures of host output are tight slots)
             uint8_t *to = iso->out_dev ? iso->out : iso->d_stage;
-            if (iso->out && iso->pitched() && fer_pic_packed(iso->fmt))
-                fer_launch_pic_emit_packed(d, c->planes[c->cur_set ^ 1], nullptr, iso->d_map + t * S, iso->nmap[t], to, iso->fmt, iso->csc, iso->pitch_y,
-                                           fer_pic_slot_bytes(iso->fmt, iso->pitch_y, iso->pitch_c, (uint32_t)iso->win[3]), iso->win, c->st);
-            else if (iso->out && iso->pitched())
-                fer_launch_pic_emit_slots(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, iso->fmt, iso->pitch_y, iso->pitch_c,
-                                          fer_pic_slot_bytes(iso->fmt, iso->pitch_y, iso->pitch_c, (uint32_t)iso->win[3]), iso->win, c->st);
-            else if (iso->out && iso->windowed)
-                fer_launch_decode_out_win(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, iso->win, c->st);
-            else if (iso->out)
-                fer_launch_decode_out(d, c->planes[c->cur_set ^ 1], iso->d_map + t * S, iso->nmap[t], to, c->st);
-        } else if (out) {
+            const uint8_t *set = c->planes[c->cur_set ^ 1];
+            const int2 *map = iso->d_map + t * S;
+            const uint32_t py = iso->row_y(), pc = iso->row_c();
+            const size_t slot = fer_pic_slot_bytes(iso->fmt, py, pc, (uint32_t)iso->win[3]);
+            if (fer_pic_packed(iso->fmt))
+                fer_launch_pic_emit_packed(d, set, nullptr, map, iso->nmap[t], to, iso->fmt, iso->csc, py, slot, iso->win, c->st);
+            else if (iso->whole(d, to))
+                fer_launch_decode_out(d, set, map, iso->nmap[t], to, c->st);
+            else
+                fer_launch_pic_emit_slots(d, set, map, iso->nmap[t], to, iso->fmt, py, pc, slot, iso->win, c->st);
+        } else if (!iso && out) {
             int rc = ferhip_get_recon(c, out + (t0 + t) * S * ss.fsz, 1);
             if (rc) return rc;
         }
@@ -1096,7 +1100,6 @@ extern "C" int ferhip_decs_set_display(ferhip_decs *d, int x0, int y0, int dw, i
     iso.win[2] = dw;
     iso.win[3] = dh;
     iso.ofsz = ofsz;
-    iso.windowed = !(x0 == 0 && y0 == 0 && dw == d->W && dh == d->H);
     return 0;
 }
 
@@ -1125,10 +1128,10 @@ extern "C" int ferhip_decs_set_csc(ferhip_decs *d, int matrix)
 static int decs_layout_check(const ferhip_decs *d, const uint8_t *out, int out_on_device)
 {
     const DecIsolate &iso = d->iso;
-    if (!iso.pitched()) return 0;
+    if (!iso.own_layout()) return 0;
     if (!out_on_device) return FERHIP_E_ARG;
     if (fer_pic_packed(iso.fmt) && ((uintptr_t)out & 3u)) return FERHIP_E_ARG;
-    return fer_pic_layout_check(iso.fmt, iso.pitch_y, iso.pitch_c, (uint32_t)iso.win[2]);
+    return fer_pic_layout_check(iso.fmt, iso.pitch_y, iso.pitch_c, (uint32_t)iso.win[2]);  // (the internal tight pitches never get here)
 }
 
 extern "C" int ferhip_decs_set_input(ferhip_decs *d, int format, int length_size)

@@ -38,11 +38,10 @@ void fer_launch_carry_ref(const FerDev &d, hipStream_t st);
 void fer_launch_reset_stream(const FerDev &d, int s, int qpw, hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);
-// map[j] = (stream, slot): picture of stream map[j].x in `set` -> dst + map[j].y * W*H*3/2 (I420), for j < n
+// map[j] = (stream, slot): picture of stream map[j].x in `set` -> dst + map[j].y * W*H*3/2 (I420), for j < n; dst is
+// 16-byte aligned (any other output of the live decoder goes through fer_launch_pic_emit_slots)
 void fer_launch_decode_out(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, hipStream_t st);
-// the same for the window win = (x0, y0, dw, dh) of every picture: slots of dw*dh*3/2 bytes, dst of any alignment
-void fer_launch_decode_out_win(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, const int *win, hipStream_t st);
-// display-size ingest (fer_pad.hip): src = [S][dw*dh*3/2] I420 in device memory, any alignment -> `set`, padded by edge
+// display-size ingest (fer_pic.hip): src = [S][dw*dh*3/2] I420 in device memory, any alignment -> `set`, padded by edge
 // replication to the coded size; present: device [S], 0 = the stream is left out (null = every stream)
 void fer_launch_pad_ingest(const FerDev &d, uint8_t *set, const uint8_t *src, int dw, int dh, const uint8_t *present, hipStream_t st);
 // pictures by descriptor (fer_pic.hip).  d_pics: device [S], a stream with plane[0] == NULL is left out.

@@ -1,5 +1,6 @@
-// fer_pad_run.h -- device helpers shared by the ingest kernels (fer_pad.hip, fer_pic.hip): a run of coded samples of one
-// row, fetched from a source row of any alignment as the aligned dwords that hold it and padded by edge replication.
+// fer_pad_run.h -- device helpers under the ingest kernels of fer_pic.hip (pad_run under ingest_planar_word, which
+// k_pad_ingest and k_pic_ingest share; pad_run_pairs under k_pic_ingest's NV12 chroma): a run of coded samples of one row,
+// fetched from a source row of any alignment as the aligned dwords that hold it and padded by edge replication.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -40,9 +41,10 @@ __device__ __forceinline__ void pad_run(const uint8_t *row, uint32_t col, uint32
 
 // pad_run's replication for a run that is already in registers: the first nvalid (1 .. 4N) bytes of out[] stay, the rest
 // repeat the last of them
-// (pad_run keeps its own copy of these lines on purpose: with the tail written in place k_pad_ingest compiles to the
-// instructions it had before the header existed, with the tail called from here it takes two more VGPRs.  Merge the two
-// only with the kernel's ISA and register count in hand.)
+// (pad_run keeps its own copy of these lines on purpose.  With pad_run ending in pad_edge<N>(out, c1 - c0 + 1u) both
+// kernels that call it through ingest_planar_word take two more VGPRs and two more instructions on gfx950 at -O3:
+// k_pad_ingest 26 -> 28 VGPRs, 429 -> 431 instructions; k_pic_ingest 30 -> 32 VGPRs, 1014 -> 1016.  Neither count changes
+// the occupancy, but the merge was to cost nothing; it is on record in DESIGN.md, R16.)
 template <int N>
 __device__ __forceinline__ void pad_edge(uint32_t (&out)[N], uint32_t nvalid)
 {

@@ -1,115 +1,147 @@
-// fer_pic.hip -- pictures by descriptor (ferhip_set_pictures, ferhip_get_recon_pictures, ferhip_decs_set_layout): between the
-// context's plane-major picture set of the coded size W x H ([S] Y, [S] Cb, [S] Cr) and pictures that lie where a producer
-// or consumer keeps them: a base pointer and a row pitch per stream and plane, any byte alignment, I420 or NV12.
+// fer_pic.hip -- the planar picture movers: between the context's plane-major picture set of the coded size W x H ([S] Y,
+// [S] Cb, [S] Cr) and pictures of the display size dw x dh that lie where a producer or consumer keeps them, at any byte
+// alignment.  On the way in the coded picture is padded by edge replication:
+//     coded sample (x, y) of a plane = source sample (min(x, pw - 1), min(y, ph - 1)),  (pw, ph) = the plane's display size.
 //
-//   k_pic_ingest  grid (chunk, stream), one launch for every present stream and all planes; a stream whose descriptor has
-//                 plane[0] == NULL exits after that one load.  k_pad_ingest with a row address of plane + min(y, ph - 1) *
-//                 pitch: a lane owns one 16-byte word of the destination, fetches its run as the aligned dwords that hold it
-//                 (pad_run, fer_pad_run.h) and stores the word whole.  For NV12 a chroma lane owns the Cb word and the Cr
-//                 word at the same (x, y): the 32 interleaved bytes of the run are fetched once, as up to nine aligned
-//                 dwords, and separated with v_perm_b32 (pad_run_pairs).  A chroma plane of width W/2 = 8 (mod 16) has
-//                 words of two 8-sample runs in neighbouring rows, as in k_pad_ingest.
+//   ingest_planar_word  the body both ingest kernels share: three plane bases and three row pitches in, one 16-byte word of
+//                 the destination out.  A word lies in one row when the plane's coded width is a multiple of 16; a chroma
+//                 plane of width W/2 = 8 (mod 16) has words that hold the last 8 samples of one row and the first 8 of the
+//                 next, which are fetched as two runs of 8.  A run of source bytes starts anywhere: it is read as the
+//                 aligned dwords that hold it and shifted into place (pad_run, fer_pad_run.h).  Only dwords that hold a byte
+//                 of the run are read; the replicated right edge is the run's last byte, taken from the registers; the
+//                 replicated bottom rows read the last source row again (cache hits).
+//   k_pad_ingest  (ferhip_set_frames_display, ferhip_upload_frames_display) grid (chunk, stream), one launch for every stream
+//                 of the `present` mask and all three planes.  The pictures are I420, stream-major [S][dw*dh*3/2]: the bases
+//                 follow from the stream, the pitches are dw, dw/2, dw/2, and the row offset is a 32-bit product.
+//   k_pic_ingest  (ferhip_set_pictures) the same grid; bases and pitches come from the stream's descriptor, the row offset is
+//                 a size_t product, and a stream whose descriptor has plane[0] == NULL exits after that one load.  For NV12 a
+//                 chroma lane owns the Cb word and the Cr word at the same (x, y): the 32 interleaved bytes of the run are
+//                 fetched once, as up to nine aligned dwords, and separated with v_perm_b32 (pad_run_pairs).
 //   k_pic_emit    grid (piece, picture), the way back: the window (x0, y0, dw, dh) of a picture of the set into pitched I420
 //                 or NV12.  A lane owns one aligned dword of a destination row; its four samples come from the one or two
 //                 aligned source dwords that hold them (for NV12 chroma from the Cb and the Cr dwords, interleaved with
 //                 v_perm_b32).  A dword that is not wholly inside its row's bytes is written byte by byte, so the pitch gaps
 //                 and a neighbour's bytes are never written.  The destination of a picture comes from the descriptor table
-//                 (ferhip_get_recon_pictures) or from the live decoder's map and slot size (ferhip_decs_set_layout).
-// No LDS, no scratch.  k_pic_ingest moves (dw*dh + W*H) * 3/2 bytes per stream like k_pad_ingest, k_pic_emit dw*dh*3 bytes.
+//                 (ferhip_get_recon_pictures) or from the live decoder's map, pitches and slot size: every output of the
+//                 live decoder but whole coded pictures at a 16-byte aligned address (k_dec_out, fer_decode.hip).
+// No LDS, no scratch.  The ingest kernels move (dw*dh + W*H) * 3/2 bytes per stream and are bound by HBM like k_repack,
+// k_pic_emit moves dw*dh*3 bytes.
 // The packed formats (YUY2, UYVY, BGRA, RGBA: one plane, converted in the pass) have kernels of their own at the end of the
 // file, k_pic_ingest_packed and k_pic_emit_packed; the two above are launched for I420 and NV12 only.
 #include "fer_internal.h"
 #include "fer_pad_run.h"
 #include "fer_pic_host.h"
 
-struct FerPicIn {
-    uint8_t *set;            // the picture set, coded size, plane-major
-    const ferhip_pic *pics;  // device [S]
+struct FerPicSet {
+    uint8_t *set;  // the picture set, coded size, plane-major
     uint32_t W, H, dw, dh;
-    int S, nv12;
+    int S;
 };
+static FerPicSet pic_set(const FerDev &d, uint8_t *set, int dw, int dh) { return {set, (uint32_t)d.W, (uint32_t)d.H, (uint32_t)dw, (uint32_t)dh, d.S}; }
 
-__global__ __launch_bounds__(256) void k_pic_ingest(FerPicIn j)
+// The 16-byte word at offset o of stream s's coded I420 picture (Y, Cb, Cr one behind the other, ysz = W * H), from planes
+// p[] of the display size with row pitches t[].  OFF is the type of the row-offset product: uint32_t where every plane and
+// its pitches stay below 2^24 bytes, else size_t.
+template <typename OFF>
+__device__ __forceinline__ void ingest_planar_word(const FerPicSet &j, uint32_t ysz, uint32_t s, const uint8_t *const (&p)[3], const uint32_t (&t)[3],
+                                                   uint32_t o)
+{
+    const uint32_t csz = ysz >> 2;
+    uint32_t PW, pw, ph, pitch;  // o becomes the offset in the plane
+    const uint8_t *sp;
+    uint8_t *dp;
+    if (o < ysz) {
+        PW = j.W, pw = j.dw, ph = j.dh;
+        sp = p[0], pitch = t[0];
+        dp = j.set + (size_t)s * ysz;
+    } else {
+        const uint32_t cr = o >= ysz + csz ? 1u : 0u;
+        o -= ysz + cr * csz;
+        PW = j.W >> 1, pw = j.dw >> 1, ph = j.dh >> 1;
+        sp = cr ? p[2] : p[1], pitch = cr ? t[2] : t[1];
+        dp = j.set + (size_t)j.S * (ysz + cr * csz) + (size_t)s * csz;
+    }
+    uint4 v;
+    if ((PW & 15u) == 0u) {  // the word lies in one row
+        const uint32_t y = o / PW, x = o - y * PW;
+        uint32_t r[4];
+        pad_run<4>(sp + (OFF)min(y, ph - 1u) * pitch, x, pw, r);
+        v = make_uint4(r[0], r[1], r[2], r[3]);
+    } else {  // PW = 8 (mod 16): each half lies in one row, the two in neighbouring rows or side by side
+        const uint32_t y0 = o / PW, x0 = o - y0 * PW;
+        const uint32_t y1 = (o + 8u) / PW, x1 = o + 8u - y1 * PW;
+        uint32_t a[2], b[2];
+        pad_run<2>(sp + (OFF)min(y0, ph - 1u) * pitch, x0, pw, a);
+        pad_run<2>(sp + (OFF)min(y1, ph - 1u) * pitch, x1, pw, b);
+        v = make_uint4(a[0], a[1], b[0], b[1]);
+    }
+    *(uint4 *)(dp + o) = v;
+}
+
+__global__ __launch_bounds__(256) void k_pad_ingest(FerPicSet j, const uint8_t *src, const uint8_t *present)
 {
     const uint32_t s = blockIdx.y;
-    const ferhip_pic *pd = j.pics + s;
-    const uint8_t *p0 = (const uint8_t *)pd->plane[0];
-    if (!p0) return;
-    const uint8_t *p1 = (const uint8_t *)pd->plane[1], *p2 = (const uint8_t *)pd->plane[2];
-    const uint32_t t0 = pd->pitch[0], t1 = pd->pitch[1], t2 = pd->pitch[2];
+    if (present && !present[s]) return;
+    const uint32_t ysz = j.W * j.H, dys = j.dw * j.dh, dcs = dys >> 2;  // (an encoder context's planes stay below 2^24)
+    src += (size_t)s * (dys + 2u * dcs);
+    const uint8_t *const p[3] = {src, src + dys, src + dys + dcs};
+    const uint32_t t[3] = {j.dw, j.dw >> 1, j.dw >> 1};
+    const uint32_t nword = (ysz + (ysz >> 1)) >> 4;
+    for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < nword; u += gridDim.x * blockDim.x)
+        ingest_planar_word<uint32_t>(j, ysz, s, p, t, u << 4);
+}
+
+void fer_launch_pad_ingest(const FerDev &d, uint8_t *set, const uint8_t *src, int dw, int dh, const uint8_t *present, hipStream_t st)
+{
+    const uint32_t nword = (uint32_t)(d.ysz * 3 / 2 / 16);
+    const unsigned nb = (nword + 255u) / 256u;
+    hipLaunchKernelGGL(k_pad_ingest, dim3(nb < 256u ? nb : 256u, d.S), dim3(256), 0, st, pic_set(d, set, dw, dh), src, present);
+}
+
+__global__ __launch_bounds__(256) void k_pic_ingest(FerPicSet j, const ferhip_pic *pics, int nv12)
+{
+    const uint32_t s = blockIdx.y;
+    const ferhip_pic *pd = pics + s;
+    if (!pd->plane[0]) return;
+    const uint8_t *const p[3] = {(const uint8_t *)pd->plane[0], (const uint8_t *)pd->plane[1], (const uint8_t *)pd->plane[2]};
+    const uint32_t t[3] = {pd->pitch[0], pd->pitch[1], pd->pitch[2]};
     const uint32_t ysz = j.W * j.H, csz = ysz >> 2;  // (an encoder context's planes stay below 2^24)
     const uint32_t nyw = ysz >> 4, ncw = csz >> 4;
-    const uint32_t nword = nyw + (j.nv12 ? ncw : 2u * ncw);
+    const uint32_t nword = nyw + (nv12 ? ncw : 2u * ncw);
     for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < nword; u += gridDim.x * blockDim.x) {
-        if (j.nv12 && u >= nyw) {  // the Cb word and the Cr word at one place, from one run of CbCr pairs
+        if (!nv12 || u < nyw) {
+            ingest_planar_word<size_t>(j, ysz, s, p, t, u << 4);
+        } else {  // the Cb word and the Cr word at one place, from one run of CbCr pairs
             const uint32_t o = (u - nyw) << 4, PW = j.W >> 1, pw = j.dw >> 1, ph = j.dh >> 1;
             uint8_t *dcb = j.set + (size_t)j.S * ysz + (size_t)s * csz, *dcr = dcb + (size_t)j.S * csz;
             uint4 vb, vr;
             if ((PW & 15u) == 0u) {
                 const uint32_t y = o / PW, x = o - y * PW;
                 uint32_t b[4], r[4];
-                pad_run_pairs<4>(p1 + (size_t)min(y, ph - 1u) * t1, x, pw, b, r);
+                pad_run_pairs<4>(p[1] + (size_t)min(y, ph - 1u) * t[1], x, pw, b, r);
                 vb = make_uint4(b[0], b[1], b[2], b[3]);
                 vr = make_uint4(r[0], r[1], r[2], r[3]);
             } else {
                 const uint32_t y0 = o / PW, x0 = o - y0 * PW;
                 const uint32_t y1 = (o + 8u) / PW, x1 = o + 8u - y1 * PW;
                 uint32_t b0[2], r0[2], b1[2], r1[2];
-                pad_run_pairs<2>(p1 + (size_t)min(y0, ph - 1u) * t1, x0, pw, b0, r0);
-                pad_run_pairs<2>(p1 + (size_t)min(y1, ph - 1u) * t1, x1, pw, b1, r1);
+                pad_run_pairs<2>(p[1] + (size_t)min(y0, ph - 1u) * t[1], x0, pw, b0, r0);
+                pad_run_pairs<2>(p[1] + (size_t)min(y1, ph - 1u) * t[1], x1, pw, b1, r1);
                 vb = make_uint4(b0[0], b0[1], b1[0], b1[1]);
                 vr = make_uint4(r0[0], r0[1], r1[0], r1[1]);
             }
             *(uint4 *)(dcb + o) = vb;
             *(uint4 *)(dcr + o) = vr;
-            continue;
         }
-        uint32_t o = u << 4, PW, pw, ph, pitch;  // offset in the stream's coded picture, then in its plane
-        const uint8_t *sp;
-        uint8_t *dp;
-        if (o < ysz) {
-            PW = j.W, pw = j.dw, ph = j.dh;
-            sp = p0, pitch = t0;
-            dp = j.set + (size_t)s * ysz;
-        } else {
-            const uint32_t cr = o >= ysz + csz ? 1u : 0u;
-            o -= ysz + cr * csz;
-            PW = j.W >> 1, pw = j.dw >> 1, ph = j.dh >> 1;
-            sp = cr ? p2 : p1, pitch = cr ? t2 : t1;
-            dp = j.set + (size_t)j.S * (ysz + cr * csz) + (size_t)s * csz;
-        }
-        uint4 v;
-        if ((PW & 15u) == 0u) {  // the word lies in one row
-            const uint32_t y = o / PW, x = o - y * PW;
-            uint32_t r[4];
-            pad_run<4>(sp + (size_t)min(y, ph - 1u) * pitch, x, pw, r);
-            v = make_uint4(r[0], r[1], r[2], r[3]);
-        } else {  // PW = 8 (mod 16): each half lies in one row, the two in neighbouring rows or side by side
-            const uint32_t y0 = o / PW, x0 = o - y0 * PW;
-            const uint32_t y1 = (o + 8u) / PW, x1 = o + 8u - y1 * PW;
-            uint32_t a[2], b[2];
-            pad_run<2>(sp + (size_t)min(y0, ph - 1u) * pitch, x0, pw, a);
-            pad_run<2>(sp + (size_t)min(y1, ph - 1u) * pitch, x1, pw, b);
-            v = make_uint4(a[0], a[1], b[0], b[1]);
-        }
-        *(uint4 *)(dp + o) = v;
     }
 }
 
 void fer_launch_pic_ingest(const FerDev &d, uint8_t *set, const ferhip_pic *d_pics, int format, int dw, int dh, hipStream_t st)
 {
-    FerPicIn j;
-    j.set = set;
-    j.pics = d_pics;
-    j.W = (uint32_t)d.W;
-    j.H = (uint32_t)d.H;
-    j.dw = (uint32_t)dw;
-    j.dh = (uint32_t)dh;
-    j.S = d.S;
-    j.nv12 = format == FERHIP_FMT_NV12;
-    const uint32_t nword = (uint32_t)((d.ysz + (j.nv12 ? d.csz : 2 * d.csz)) / 16);
+    const int nv12 = format == FERHIP_FMT_NV12;
+    const uint32_t nword = (uint32_t)((d.ysz + (nv12 ? d.csz : 2 * d.csz)) / 16);
     const unsigned nb = (nword + 255u) / 256u;
-    hipLaunchKernelGGL(k_pic_ingest, dim3(nb < 256u ? nb : 256u, d.S), dim3(256), 0, st, j);
+    hipLaunchKernelGGL(k_pic_ingest, dim3(nb < 256u ? nb : 256u, d.S), dim3(256), 0, st, pic_set(d, set, dw, dh), d_pics, nv12);
 }
 
 struct FerPicOut {

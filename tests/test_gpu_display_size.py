@@ -52,18 +52,25 @@ def test_ingest_host_source(ingest):
     assert np.array_equal(_cur(enc), _model(pics, dw, dh, W, H))
 
 
-@pytest.mark.parametrize("mis", [0, 1, 2, 7])
-def test_ingest_device_source_at_any_alignment(pkg, ingest, mis):
+@pytest.mark.parametrize("mis,mask", [pytest.param(0, None, id="0"), pytest.param(1, None, id="1"), pytest.param(2, None, id="2"),
+                                      pytest.param(7, None, id="7"), pytest.param(3, [1, 0, 1], id="3-present101")])
+def test_ingest_device_source_at_any_alignment(pkg, ingest, mis, mask):
     enc, W, H, dw, dh = ingest
-    pics = _rand_pics(np.random.default_rng(2 + mis), S, dw, dh)
+    rng = np.random.default_rng(2 + mis)
+    want = pics = _rand_pics(rng, S, dw, dh)
+    if mask:  # an absent stream keeps its picture, and its slot is never read
+        before = _rand_pics(rng, S, dw, dh)
+        enc.set_frames_display(before)
+        want = np.stack([pics[s] if mask[s] else before[s] for s in range(S)])
+        pics = np.stack([pics[s] if mask[s] else np.full_like(pics[s], POISON) for s in range(S)])
     buf = pkg.DeviceBuffer(pics.nbytes + 32)
     buf.upload(np.full(pics.nbytes + 32, POISON, np.uint8))
     buf.upload(pics, offset=mis)
     assert buf.ptr % 16 == 0
-    enc.set_frames_display(buf.ptr + mis)
+    enc.set_frames_display(buf.ptr + mis, present=mask)
     got = _cur(enc)
     buf.free()
-    assert np.array_equal(got, _model(pics, dw, dh, W, H))
+    assert np.array_equal(got, _model(want, dw, dh, W, H))
 
 
 def test_ingest_upload_path(pkg, ingest):
@@ -292,11 +299,11 @@ def _windowed(ref, win):
 
 
 @pytest.mark.parametrize("win", WINDOWS)
-@pytest.mark.parametrize("mode", ["host", "device", "device+4", "dev_chunks_host", "dev_chunks_device+4"])
+@pytest.mark.parametrize("mode", ["host", "device", "device+4", "dev_chunks_host", "dev_chunks_device+4", "device+1", "device+3"])
 def test_decode_windowed_output(pkg, dec_streams, win, mode):
     streams, ref, _ = dec_streams
     got, _ = _live(pkg, streams, 1, win, out="host" if mode.endswith("host") else "device", dev_chunks=mode.startswith("dev_chunks"),
-                   out_mis=4 if mode.endswith("+4") else 0)
+                   out_mis=int(mode.partition("+")[2] or 0))
     for s in range(3):
         assert np.array_equal(got[s], _windowed(ref[s], win)), f"stream {s}"
 

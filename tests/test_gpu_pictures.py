@@ -123,6 +123,29 @@ def test_ingest_bytes(pkg, pool, W, H, ddw, ddh, fmt):
     enc.close()
 
 
+def test_tight_i420_descriptors_equal_the_display_size_ingest(pkg):
+    """A packed [S][dw*dh*3/2] array is a descriptor table with pitches dw, dw/2, dw/2: both ingest kernels run the same body
+    over it and must fill the same picture set, at an odd base address and a chroma width of 8 (mod 16)."""
+    W, H, dw, dh = 80, 48, 66, 48
+    dys, fsz = dw * dh, dw * dh * 3 // 2
+    frames = np.random.default_rng(23).integers(1, 255, (S, fsz), dtype=np.uint8)
+    buf = pkg.DeviceBuffer(S * fsz + 32)
+    buf.upload(np.full(S * fsz + 32, 0xEE, np.uint8))
+    buf.upload(frames, offset=3)
+    base = [buf.ptr + 3 + s * fsz for s in range(S)]
+    enc = pkg.FerHip(W, H, S, qp=20, window=16)
+    enc.set_display_size(dw, dh)
+    enc.set_pictures([([b, b + dys, b + dys + dys // 4], [dw, dw // 2, dw // 2]) for b in base], pic.I420)
+    by_desc = _cur(enc)
+    enc.set_frames(np.zeros((S, enc.fsz), np.uint8))
+    enc.set_frames_display(buf.ptr + 3)
+    by_display = _cur(enc)
+    enc.close()
+    buf.free()
+    assert np.array_equal(by_desc, by_display)
+    assert np.array_equal(by_desc, np.stack([pm.pad_picture(f, dw, dh, W, H) for f in frames]))
+
+
 # ---------------------------------------------------------------- 2. absent streams
 @pytest.mark.parametrize("fmt", FMTS, ids=FMT_ID.get)
 @pytest.mark.parametrize("W,H,dw,dh", [(48, 32, 46, 18), (64, 32, 64, 32)])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Rate of the display-size ingest (ferhip_set_frames_display, k_pad_ingest of fer_pad.hip) against the coded-size ingest
+"""Rate of the display-size ingest (ferhip_set_frames_display, k_pad_ingest of fer_pic.hip) against the coded-size ingest
 of the same context (ferhip_set_frames, k_repack), both from device memory.
 
   S 1920x1080 streams in a 1920x1088 context, and S 1366x768 streams in a 1376x768 context.

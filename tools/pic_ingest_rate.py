@@ -21,10 +21,12 @@ record in front of every kernel, and every eighth call may wait in the pinned ri
 kernels alone are read from `rocprofv3 --kernel-trace` over the same command.
 
   --emit   instead: S 1920x1088 streams of --pictures pictures are encoded, then decoded picture by picture by the live
-           decoder into device slots with the window (0, 0, 1920, 1080), in the default layout (k_dec_out_win) and as NV12 and
-           I420 at pitch 2048 (k_pic_emit): one launch of the output kernel per picture.  The mode times nothing itself (a
-           decode call is dominated by the parse): run it under `rocprofv3 --kernel-trace` and read the launches' device
-           times there, leaving out the first few of each layout as warm-up.
+           decoder into device slots with the window (0, 0, 1920, 1080), in the default layout (tight slots) and as NV12 and
+           I420 at pitch 2048: one launch of k_pic_emit per picture in all three.  The mode times nothing itself (a decode
+           call is dominated by the parse): run it under `rocprofv3 --kernel-trace` and read the launches' device times
+           there, leaving out the first few of each layout as warm-up.
+  --emit --full --out-offset 1   the default layout only, whole 1920x1088 pictures into a buffer that starts one byte past a
+           16-byte boundary (k_pic_emit; at offset 0 the same pictures go through k_dec_out).
 
     python tools/pic_ingest_rate.py --streams 256 --reps 50 --rounds 5
 """
@@ -55,16 +57,18 @@ def emit(a, pkg, torch):
             streams[s] += enc.write_nal(nt[s], rbsp[s])
     enc.close()
     aus = [pkg.access_units(s) for s in streams]
-    for name, layout in (("default", None), ("nv12", (pkg.FMT_NV12, PITCH, PITCH)), ("i420", (pkg.FMT_I420, PITCH, PITCH // 2))):
+    layouts = (("default", None), ("nv12", (pkg.FMT_NV12, PITCH, PITCH)), ("i420", (pkg.FMT_I420, PITCH, PITCH // 2)))
+    for name, layout in layouts[:1] if a.full else layouts:
         dec = pkg.LiveDecoder(S, W, H, 1)
-        dec.set_display(0, 0, W, dh)
+        dec.set_display(0, 0, W, H if a.full else dh)
         if layout:
             dec.set_layout(*layout)
-        out = pkg.DeviceBuffer(S * dec.fsz + 16)
+        out = pkg.DeviceBuffer(S * dec.fsz + 32)
+        assert out.ptr % 16 == 0
         for t in range(T):
-            _, pics, st = dec.decode([x[t] for x in aus], out)
+            _, pics, st = dec.decode([x[t] for x in aus], out.ptr + a.out_offset if a.out_offset else out)
             assert pics == [1] * S and st == [0] * S
-        print(json.dumps(dict(emit=name, streams=S, slot=dec.fsz, pictures=T)), flush=True)
+        print(json.dumps(dict(emit=name, streams=S, slot=dec.fsz, pictures=T, full=a.full, out_offset=a.out_offset)), flush=True)
         dec.close()
         out.free()
 
@@ -77,6 +81,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--emit", action="store_true")
     ap.add_argument("--pictures", type=int, default=55, help="--emit: pictures per stream")
+    ap.add_argument("--full", action="store_true", help="--emit: whole coded pictures in the default layout only")
+    ap.add_argument("--out-offset", type=int, default=0, help="--emit: bytes from a 16-byte boundary to the output buffer")
     a = ap.parse_args()
     import torch
     pkg = load_pkg()
