@@ -7,7 +7,9 @@
 //                 picture region share one L2): the box sums of the source block, the complete stage-3 search
 //                 (wide integer window read from the plane-0 feature map + local quarter-pel window whose features
 //                 are computed on chip from the padded interpolated planes, local_metrics<R1>), its top-33 list
-//                 and the SAD of each survivor (lane per candidate, sad_keys<K>);
+//                 and the SAD of each survivor (lane per candidate, sad_keys<K>).  Bound by the latency of three dependent
+//                 memory phases, so it is built to keep seven wavefronts on a SIMD: 72 registers without scratch and one
+//                 5632-byte LDS array whose regions the phases hand on to each other (PRE_WAVES);
 //   k_me_walk     neighbour-independent, one wavefront per partition: the stage-2 bucket walk over the sum-sorted
 //                 16-byte feature records (walk_buckets_q, lane-held batch descriptor tables); partitions whose
 //                 candidate set overflows FER_ST2_CAP leave a summary (stop step, per-bucket lower bound, the
@@ -363,20 +365,25 @@ struct LocalLoads {
     static constexpr int ROUNDS = (8 * LocalGeo<R1>::PW + 63) / 64;
     uint4 w[2][ROUNDS];
 };
+// (half_lo .. half_hi: the groups of 8 planes to request; a caller short of registers asks for the second group when the
+// row phase of the first begins, local_metrics' hook)
 template <int R1>
-__device__ __forceinline__ void local_request(const IPlanes &ip, int W, int H, int px0, int py0, int lane, LocalLoads<R1> &ld)
+__device__ __forceinline__ void local_request(const IPlanes &ip, int W, int H, int px0, int py0, int lane, LocalLoads<R1> &ld,
+                                              int half_lo = 0, int half_hi = 2)
 {
     using G = LocalGeo<R1>;
     constexpr int N1 = G::N1, PW = G::PW;
 #pragma unroll
     for (int half = 0; half < 2; half++)
 #pragma unroll
-        for (int k = 0; k < LocalLoads<R1>::ROUNDS; k++) ld.w[half][k] = make_uint4(0, 0, 0, 0);
+        for (int k = 0; k < LocalLoads<R1>::ROUNDS; k++)
+            if (half >= half_lo && half < half_hi) ld.w[half][k] = make_uint4(0, 0, 0, 0);
     if (px0 + N1 - 1 < 0 || px0 >= W || py0 + N1 - 1 < 0 || py0 >= H) return;
     const uint8_t *mbase = ip.base - ((size_t)FER_IP_T * ip.pitch + FER_IP_L);
     const uint32_t obase = __umul24((uint32_t)(py0 + FER_IP_T), (uint32_t)ip.pitch) + (uint32_t)((px0 & ~3) + FER_IP_L);
 #pragma unroll
     for (int half = 0; half < 2; half++) {
+        if (half < half_lo || half >= half_hi) continue;
 #pragma unroll
         for (int k = 0; k < LocalLoads<R1>::ROUNDS; k++) {
             const int tt = min(k * 64 + lane, 8 * PW - 1);
@@ -389,9 +396,16 @@ __device__ __forceinline__ void local_request(const IPlanes &ip, int W, int H, i
 }
 // half_lo .. half_hi: which groups of 8 planes this call computes (two wavefronts may split them, each with its own htab; the
 // caller orders the shared mtab).  pre: the patch rows requested earlier with local_request (all 16 planes), or null.
-template <int R1>
+// hook(half) runs when the row phase of a group begins: the place to issue loads that the phases behind it should cover.
+struct NoHook {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+// LEAN: the column phase keeps a running sum for the fifth feature, where the plain form holds a second array of prefix sums (seven
+// registers less for a caller that has loads in flight across the search; the same unsigned arithmetic, so the same values).
+template <int R1, class HOOK = NoHook, bool LEAN = false>
 __device__ __forceinline__ void local_metrics(const IPlanes &ip, int W, int H, int px0, int py0, const SuPk &sp, int lane,
-                                              uint32_t *htab, int *mtab, int half_lo = 0, int half_hi = 2, const LocalLoads<R1> *pre = nullptr)
+                                              uint32_t *htab, int *mtab, int half_lo = 0, int half_hi = 2, const LocalLoads<R1> *pre = nullptr,
+                                              HOOK hook = HOOK())
 {
     using G = LocalGeo<R1>;
     constexpr int N1 = G::N1, PW = G::PW;
@@ -409,6 +423,7 @@ __device__ __forceinline__ void local_metrics(const IPlanes &ip, int W, int H, i
     const uint8_t *mbase = ip.base - ((size_t)FER_IP_T * ip.pitch + FER_IP_L);
     const uint32_t obase = __umul24((uint32_t)(py0 + FER_IP_T), (uint32_t)ip.pitch) + (uint32_t)((px0 & ~3) + FER_IP_L);
     for (int half = half_lo; half < half_hi; half++) {
+        hook(half);
         // ---- horizontal sums: row tasks (plane, row)
 #pragma unroll
         for (int t0 = 0; t0 < 8 * PW; t0 += 64) {
@@ -441,14 +456,20 @@ __device__ __forceinline__ void local_metrics(const IPlanes &ip, int W, int H, i
         // ---- column tasks (plane, column offset): prefix sums down the PW rows, N1 metrics
         if (lane < 8 * N1) {
             const int fl = lane / N1, ix = lane - fl * N1;
-            uint32_t P84[PW + 1], Pc[PW + 1];
+            uint32_t P84[PW + 1], Pc[LEAN ? 1 : PW + 1], k4l[N1];
             P84[0] = 0;
             Pc[0] = 0;
 #pragma unroll
             for (int r = 0; r < PW; r++) {
                 const uint2 h = *(const uint2 *)(htab + ((size_t)(fl * PW + r) * N1 + ix) * 2);
                 P84[r + 1] = P84[r] + h.x;  // (sum of h8) | (sum of h4) << 16: neither field can carry
-                Pc[r + 1] = Pc[r] + h.y;
+                if constexpr (LEAN) {
+                    if (r < N1) k4l[r] = Pc[0];  // the prefix in front of row r ...
+                    Pc[0] += h.y;
+                    if (r >= 7) k4l[r - 7] = Pc[0] - k4l[r - 7];  // ... leaves the sum of rows r - 7 .. r
+                } else {
+                    Pc[r + 1] = Pc[r] + h.y;
+                }
             }
             const int refx = px0 + ix, wx = iabs(ix - R1) + 4;
             const bool xok = refx >= 0 && refx < W;
@@ -457,7 +478,11 @@ __device__ __forceinline__ void local_metrics(const IPlanes &ip, int W, int H, i
                 const uint32_t all = P84[iy + 8] - P84[iy];
                 const uint32_t k1 = (P84[iy + 4] - P84[iy]) & 0xffffu;
                 const uint32_t k3 = ((P84[iy + 2] - P84[iy]) + (P84[iy + 6] - P84[iy + 4])) & 0xffffu;
-                const uint32_t k4 = Pc[iy + 8] - Pc[iy];
+                uint32_t k4;
+                if constexpr (LEAN)
+                    k4 = k4l[iy];
+                else
+                    k4 = Pc[iy + 8] - Pc[iy];
                 const int D = feat_dist_w((all & 0xffffu) | (k1 << 16), (all >> 16) | (k3 << 16), k4, sp);
                 const int refy = py0 + iy;
                 const int m = (int)__umul24((uint32_t)(wx + iabs(iy - R1)), (uint32_t)D) | ((xok && refy >= 0 && refy < H) ? 0 : -1);
@@ -527,21 +552,35 @@ __device__ __forceinline__ int sad_lane(const IPlanes &ip, int W, int H, int sx,
     return (int)sad;
 }
 
+// the lane's bit of a wave-uniform mask as a predicate: the mask itself serves as the condition, where a shift and a
+// test per lane would take it through a vector register and back
+__device__ __forceinline__ bool wave_mask_bit(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// ... and the other way round: the compare's result is the mask (__ballot takes an int: the predicate goes through a 0 / 1 value)
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 // ------------------------------------------------------------------ k_me_pre
-#define ME_WIDE_LDS 1156  // (2*16+2)^2: WindowSize <= 32 takes the LDS route (4.6 KB per wave)
+#define ME_WIDE_LDS 1156  // (2*16+2)^2: the metrics of the full evaluation at WindowSize <= 32
+#define ME_ROW_LDS 960    // the row sums of the local search at WindowSize 32 (LocalGeo<2>::HTAB)
+#define ME_PRE_LDS 1408   // ME_ROW_LDS + 448 dwords: the kernel's whole LDS, 5632 bytes
 #define ME_SEL_NB 25      // 64-candidate batches of stage 3 at WindowSize 32: 18 wide + 7 local
 #ifndef PRE_WAVES
-#define PRE_WAVES 5  // wavefronts per SIMD the kernel is compiled for (register budget; flat from 5 up, its LDS allows 6.25)
+#define PRE_WAVES 7  // wavefronts per SIMD the kernel is compiled for: 72 registers, and 28 x 5632 bytes of LDS fit a CU
 #endif
 template <int WIN>  // WindowSize known at compile time (0 = read it from d): divisions by the window become shifts/muls
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, PRE_WAVES))) void k_me_pre(FerDev d)
 {
     const int window = WIN ? WIN : d.window;
-    // LDS of the wavefront: region A = the row sums of the local search, then the wide search's metrics; region B =
-    // the local search's metrics, then the scratch of the selection
-    __shared__ __attribute__((aligned(16))) int wide_m[ME_WIDE_LDS];
-    __shared__ __attribute__((aligned(16))) int sel_lds[448];
-    static_assert(LocalGeo<2>::HTAB <= ME_WIDE_LDS && LocalGeo<2>::NB * 64 <= 448, "LDS regions of k_me_pre");
+    // LDS of the wavefront, one array of 5632 bytes (seven wavefronts per SIMD fit the CU's 160 KB).  Region A = its first
+    // ME_ROW_LDS dwords: the row sums of the local search, then the arrival numbers of the pruned wide search's survivors.
+    // The pruned route's selection takes its scratch behind the survivors, so that region B = the 448 dwords behind region
+    // A keeps the local search's metrics for as long as the full evaluation may still be needed.  The full evaluation moves
+    // them into registers, lays its ME_WIDE_LDS metrics over both regions, reads those back into registers as well and
+    // then runs its selection on region B.
+    __shared__ __attribute__((aligned(16))) int pre_lds[ME_PRE_LDS];
+    int *const wide_m = pre_lds, *const sel_lds = pre_lds + ME_ROW_LDS;
+    static_assert(LocalGeo<2>::HTAB <= ME_ROW_LDS && LocalGeo<2>::NB * 64 <= ME_PRE_LDS - ME_ROW_LDS && ME_WIDE_LDS <= ME_PRE_LDS &&
+                      128 + 256 <= ME_ROW_LDS && 256 <= ME_PRE_LDS - ME_ROW_LDS && ME_ROW_LDS % 4 == 0,
+                  "LDS regions of k_me_pre");
     const int lane = threadIdx.x;
     const int s = blockIdx.y;
     if (d.hdr[s * 4 + 3] != 0) return;
@@ -573,7 +612,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
     constexpr int RRL = (WIN == 16) ? 1 : 2;
     LocalLoads<RRL> ld;
     const bool fast_path = (WIN == 32 || WIN == 16) && !FER_DBGF(d, 3) && !d.basic;
-    if (fast_path) local_request<RRL>(ip, W, H, sx - RRL, sy - RRL, lane, ld);
+    if (fast_path) local_request<RRL>(ip, W, H, sx - RRL, sy - RRL, lane, ld, 0, 1);  // (the second group: below)
     // box sums of the source block, F/moestimation.cpp:440-451
     int px = lane & 7, py = lane >> 3;
     int v = Y[(size_t)(sy + py) * W + sx + px];
@@ -605,7 +644,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
     if ((WIN == 32 || WIN == 16) && !FER_DBGF(d, 3)) {
         // n = WIN + 1: a batch of the wide search is 64 / WIN rows of the first WIN columns, so the column, its validity and its
         // weight are per-lane constants and a row step is one address increment; the last column follows
-        constexpr int WCH = 6;
+        constexpr int WCH = 3;
         constexpr int NN = (WIN ? WIN : 32) + 1;
         constexpr int NBc = WIN ? WIN : 32, RPB = 64 / NBc, NWB = (NN + RPB - 1) / RPB;
         constexpr int LB = LocalGeo<RRL>::NB;  // batches of the local search
@@ -637,15 +676,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
             k0w[b2] = *(const uint32_t *)((const char *)F0 + (colo + __umul24((uint32_t)ry, rowb)));
         }
         const uint32_t k0c = feat0_load(F0, W, H, sy - R + min(lane, NN - 1), sx + R).a;  // column n - 1
-        // the local search first (its row sums borrow the LDS of the wide search's metrics)
-        local_metrics<RRL>(ip, W, H, sx - r2, sy - r2, sp, lane, (uint32_t *)wide_m, sel_lds, 0, 2, &ld);
-        int vloc[LB];
+        // the local search first (its row sums borrow the LDS of the wide search's metrics); the patch rows of its second
+        // group of planes are requested when the row phase of the first begins: all 16 at once would not fit the registers
+        auto second_group = [&](int half) {
+            if (half == 0) local_request<RRL>(ip, W, H, sx - RRL, sy - RRL, lane, ld, 1, 2);
+        };
+        local_metrics<RRL, decltype(second_group), true>(ip, W, H, sx - r2, sy - r2, sp, lane, (uint32_t *)wide_m, sel_lds, 0, 2, &ld, second_group);
         unsigned lminl = 0xffffffffu;
 #pragma unroll
-        for (int u = 0; u < LB; u++) {
-            vloc[u] = sel_lds[u * 64 + lane];
-            lminl = min(lminl, (unsigned)vloc[u]);
-        }
+        for (int u = 0; u < LB; u++) lminl = min(lminl, (unsigned)sel_lds[u * 64 + lane]);
         int T = 0x7fffffff;
         if (__popcll(__ballot(lminl < (1u << 21))) >= 33) {
             int lo = 0, hi = (1 << 21) - 1;
@@ -663,27 +702,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
         const uint32_t s0 = (uint32_t)su[0];
         bool done = false;
         if (T != 0x7fffffff) {
+            // Per batch only the bound itself is vector work.  Its weight times 5 is a per-lane base and a compile-time step
+            // (all rows of a batch lie on one side of the centre row: R is a multiple of RPB); the rows inside the picture and
+            // the window are a wave-uniform interval of iy, held as a bit mask, and a batch's RPB bits of it spread over the
+            // lane groups and meet the lanes' column mask on the scalar side; the compare's own mask is ANDed with that.
+            static_assert((NBc / 2) % RPB == 0 && NN <= 64, "a batch stays on one side of the centre row");
+            const int iy_lo = max(0, R - sy), iy_hi = min(NN - 1, H - 1 - (sy - R));  // (iy_lo <= R <= iy_hi: the block is inside)
+            const unsigned long long rowv = ((2ull << iy_hi) - 1ull) & ~((1ull << iy_lo) - 1ull);
+            const unsigned long long colv = wave_ballot(xok);
+            constexpr unsigned long long GRP = NBc == 64 ? ~0ull : (1ull << NBc) - 1ull;
+            const uint32_t w5lo = 5u * (uint32_t)(wx + R - r0), w5hi = 5u * (uint32_t)(wx - R + r0);
+            const int arr0 = ix * NN + r0;
 #pragma unroll
             for (int b2 = 0; b2 < NWB; b2++) {
-                const int iy = b2 * RPB + r0;
-                const int ry = sy - R + iy;
-                const uint32_t lb = __umul24(5u * (uint32_t)(wx + iabs(iy - R)), __builtin_amdgcn_sad_u16(k0w[b2] & 0xffffu, s0, 0u));
-                const bool take = xok && ry >= 0 && ry < H && iy < NN && lb <= (uint32_t)T;
-                const unsigned long long mk = __ballot(take);
+                unsigned long long valid = 0;
+#pragma unroll
+                for (int j = 0; j < RPB; j++)
+                    if ((rowv >> (b2 * RPB + j)) & 1ull) valid |= GRP << (j * NBc);
+                valid &= colv;
+                const uint32_t w5 = b2 * RPB < R ? w5lo - 5u * (uint32_t)(b2 * RPB) : w5hi + 5u * (uint32_t)(b2 * RPB);
+                const uint32_t lb = __umul24(w5, __builtin_amdgcn_sad_u16(k0w[b2] & 0xffffu, s0, 0u));
+                const unsigned long long mk = wave_ballot(lb <= (uint32_t)T) & valid;
                 if (mk) {
                     const int slot = ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                    if (take && slot < 128) surv[slot] = ix * NN + iy;
+                    if (wave_mask_bit(mk) && slot < 128) surv[slot] = arr0 + b2 * RPB;
                     ns += __popcll(mk);
                 }
             }
-            {  // column n - 1
-                const int iy = lane, ry = sy - R + iy;
-                const uint32_t lb = __umul24(5u * (uint32_t)(R + 4 + iabs(iy - R)), __builtin_amdgcn_sad_u16(k0c & 0xffffu, s0, 0u));
-                const bool take = iy < NN && sx + R < W && ry >= 0 && ry < H && lb <= (uint32_t)T;
-                const unsigned long long mk = __ballot(take);
+            {  // column n - 1: lane = iy, so the row mask is the lanes' own
+                const uint32_t lb = __umul24(5u * (uint32_t)(R + 4 + iabs(lane - R)), __builtin_amdgcn_sad_u16(k0c & 0xffffu, s0, 0u));
+                const unsigned long long mk = sx + R < W ? wave_ballot(lb <= (uint32_t)T) & rowv : 0ull;
                 if (mk) {
                     const int slot = ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                    if (take && slot < 128) surv[slot] = (NN - 1) * NN + iy;
+                    if (wave_mask_bit(mk) && slot < 128) surv[slot] = (NN - 1) * NN + lane;
                     ns += __popcll(mk);
                 }
             }
@@ -706,10 +757,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
                     }
                 }
 #pragma unroll
-                for (int u = 0; u < LB; u++) v[2 + u] = vloc[u];
-                WAVE_LDS_SYNC();  // the selection reuses sel_lds
+                for (int u = 0; u < LB; u++) v[2 + u] = sel_lds[u * 64 + lane];
+                WAVE_LDS_SYNC();
+                // (the selection's scratch lies behind the survivors in region A: the local metrics stay in region B for
+                // the full evaluation, which has to run when the selection gives up)
                 auto arrv = [&](int u) { return u < 2 ? ar[u < 2 ? u : 0] : wb * 64 + (u - 2) * 64 + lane; };
-                done = select_topk_ex<2 + LB, false>(v, 33, lane, sel_lds, L, arrv, fin, arrv);
+                done = select_topk_ex<2 + LB, false>(v, 33, lane, wide_m + 128, L, arrv, fin, arrv);
             }
         }
         PP_MARK(1)
@@ -724,8 +777,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
 #endif
         if (!done) {
             // ---- the full evaluation: lanes run along x (contiguous 12-byte records); metrics land in LDS at their
-            // arrival index (tx outer, ty inner).  Records are fetched six batches at a time with clamped coordinates
-            // (no control flow around the loads), then masked; the next six are in flight while six are evaluated.
+            // arrival index (tx outer, ty inner).  Records are fetched three batches at a time with clamped coordinates
+            // (no control flow around the loads), then masked; the next three are in flight while three are evaluated
+            // (six and six did not fit the 72 registers of seven wavefronts; one partition in thirty comes here).
+            WAVE_LDS_SYNC();
+            int vloc[LB];  // the local metrics leave region B, which the wide metrics are about to cover
+#pragma unroll
+            for (int u = 0; u < LB; u++) vloc[u] = sel_lds[u * 64 + lane];
             WAVE_LDS_SYNC();
             auto wide_load = [&](int iy0, FeatRec (&fr)[WCH]) {
 #pragma unroll
@@ -858,11 +916,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
 // j > 0, and those of step 0 as well when skip0 is set.
 // probe(bucket) may return a number of candidates the slice of that bucket is KNOWN to hold (0 = unknown): when that
 // alone takes the count past halt_cnt the slice is not read (only walks that ask "is this partition crowded" pass one).
-// the lane's bit of a wave-uniform mask as a predicate: the mask itself serves as the condition, where a shift and a
-// test per lane would take it through a vector register and back
-__device__ __forceinline__ bool wave_mask_bit(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-// ... and the other way round: the compare's result is the mask (__ballot takes an int: the predicate goes through a 0 / 1 value)
-__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 struct NoProbe {
     __device__ __forceinline__ int operator()(int) const { return 0; }
 };
