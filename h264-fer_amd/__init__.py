@@ -7,7 +7,7 @@ benchmark can drive it the way the reference's GUI drives ``fer_h264::Starter``
 There is no CPU fallback: if the library or a GPU is missing, calls raise.
 """
 from .ferhip import (FerHip, FerHipError, Decoder, LiveDecoder, access_units, DeviceBuffer, Y4MReader, decode_streams, unescape_nal, lib_path,  # noqa: F401
-                     load_library, mb_unit, cavlc_blocks, mc_sub_mb_parts, MBU_QT, MBU_DEC4, MBU_DEC16, MBU_DECC, MBU_SKIP, TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT, RC_CQP, RC_ABR, RC_QUALITY, QM_SSE, QM_SSIM,
+                     load_library, mb_unit, cavlc_blocks, cavlc_parse_blocks, residual_mbs, RES_WRITE, RES_PARSE, mc_sub_mb_parts, MBU_QT, MBU_DEC4, MBU_DEC16, MBU_DECC, MBU_SKIP, TUNE_RESOLVE_WGS, TUNE_RESOLVE_GROUP, TUNE_SPECULATE, TUNE_OVERLAP_SORT, RC_CQP, RC_ABR, RC_QUALITY, QM_SSE, QM_SSIM,
                      QUALITY_RING, Quality, NAL_SLICE, NAL_IDR, NAL_AUTO, NAL_NONE, AU_PARAM_SETS, AU, frame_nal_blocks, frame_nal_blocks_raw,
                      NAL_UNIT, SPLIT_PREFIX, split_nal_blocks, split_nal_blocks_raw, FMT_I420, FMT_NV12, FMT_YUY2, FMT_UYVY, FMT_BGRA, FMT_RGBA, CSC_BT601, CSC_BT709, Pic, pic_table,
                      AU_AVCC, IN_ANNEXB, IN_AVCC, split_avcc_blocks_raw)

@@ -242,3 +242,24 @@ __device__ inline void cavlc_block_core(BitW &w, unsigned nz, int maxNumCoeff, i
     }
 }
 
+// residual_write(), F/residual.cpp:300-372: the residual blocks of macroblock mb of stream s in the reference's order, each
+// with the nC its neighbours give it (cavlc_nC over the FerDev side information, which holds this macroblock's own tc and
+// cbp already).  lv = the macroblock's FER_LEVELS levels; st = the thread's staging column in LDS, STRIDE apart.
+template <bool WRITE, int STRIDE>
+__device__ __forceinline__ void cavlc_residual_mb(BitW &w, const FerDev &d, int s, int mb, const int16_t *lv, int cbpL, int cbpC,
+                                                  bool i16, int16_t *st)
+{
+    if (i16) cavlc_block_staged<WRITE>(w, lv + FER_LV_DC16, 16, cavlc_nC(d, s, mb, true, 0, 0), st, STRIDE);
+    for (int i8 = 0; i8 < 4; i8++)
+        if (cbpL & (1 << i8))
+            for (int i4x = 0; i4x < 4; i4x++) {
+                int blk = i8 * 4 + i4x;
+                cavlc_block_staged<WRITE>(w, lv + blk * 16, i16 ? 15 : 16, cavlc_nC(d, s, mb, true, blk, 0), st, STRIDE);
+            }
+    if (cbpC & 3)
+        for (int k = 0; k < 2; k++) cavlc_block_staged<WRITE>(w, lv + FER_LV_CDC + k * 4, 4, -1, st, STRIDE);
+    if (cbpC & 2)
+        for (int k = 0; k < 2; k++)
+            for (int b = 0; b < 4; b++)
+                cavlc_block_staged<WRITE>(w, lv + FER_LV_CAC + (k * 4 + b) * 15, 15, cavlc_nC(d, s, mb, false, b, k), st, STRIDE);
+}

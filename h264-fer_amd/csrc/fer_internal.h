@@ -36,6 +36,10 @@ int fer_quality_groups(const FerDev &d);
 void fer_launch_quality(const FerDev &d, int flags, int slot, hipStream_t st);
 void fer_launch_carry_ref(const FerDev &d, hipStream_t st);
 void fer_launch_reset_stream(const FerDev &d, int s, int qpw, hipStream_t st);
+// the decode tables of the current device (DecLuts of fer_decode_dev.h), built on first use on stream st and waited for;
+// null if they cannot be allocated
+struct DecLuts;
+const DecLuts *dec_luts(hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);
 // map[j] = (stream, slot): picture of stream map[j].x in `set` -> dst + map[j].y * W*H*3/2 (I420), for j < n; dst is

@@ -2,6 +2,7 @@
 // shims over a one-stream context of the context-based ABI.  No hot-path arithmetic here.
 #include "../../include/ferhip.h"
 #include "../../include/ferhip_legacy.h"
+#include "fer_seam_host.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -254,7 +255,7 @@ int ***mvL0x = nullptr, ***mvL0y = nullptr;
 frame_type dpb;
 int ferhip_chroma_qp(int qpy);
 }
-static int g_mv_nmb = 0;
+static int g_mv_nmb = 0;  // macroblocks of the last AllocateMemory
 
 static int pred_class_of(int t)  // MbPartPredMode(mb_type, 0), F/h264_globals.h:123 over the tables of F/h264_globals.cpp:25-132
 {
@@ -270,6 +271,13 @@ static void mb_origin(int &xP, int &yP)
     const int mbw = frame.Lwidth >> 4;
     xP = (CurrMbAddr % mbw) << 4;
     yP = (CurrMbAddr / mbw) << 4;
+}
+// CurrMbAddr indexes `frame` in the shims below: it must name a macroblock of it
+static bool frame_mb_ok(const char *name)
+{
+    if (fer_seam_mb_addr_ok(CurrMbAddr, (frame.Lwidth >> 4) * (frame.Lheight >> 4))) return true;
+    legacy_block(name, FERHIP_E_ARG);
+    return false;
 }
 static void job_preds(ferhip_mb_job &J, int predL[16][16], int predCb[8][8], int predCr[8][8])
 {
@@ -302,6 +310,7 @@ static void put_chroma(const ferhip_mb_result &R, int plane)  // plane 0 = Cb, 1
 extern "C" void quantizationTransform(int predL[16][16], int predCb[8][8], int predCr[8][8], unsigned char reconstruct)
 {
     if (!frame.L) return;
+    if (!frame_mb_ok("quantizationTransform")) return;
     ferhip_mb_job *J = new ferhip_mb_job();
     ferhip_mb_result *R = new ferhip_mb_result();
     J->op = FERHIP_MBU_QT;
@@ -341,6 +350,7 @@ static void decode_op(const char *name, int op, int predL[16][16], int predCb[8]
                       int *dc, int (*ac)[16], int *cdc, int (*cac)[16], int plane)
 {
     if (!frame.L) return;
+    if (!frame_mb_ok(name)) return;
     ferhip_mb_job *J = new ferhip_mb_job();
     ferhip_mb_result *R = new ferhip_mb_result();
     J->op = op;
@@ -422,10 +432,139 @@ extern "C" unsigned int residual_block_cavlc_size(int coeffLevel[16], int startI
     return cavlc_one(coeffLevel, maxNumCoeff, false, "residual_block_cavlc_size");
 }
 
-// AllocateMemory() of F/mode_pred.cpp:22-39: the vector arrays [macroblock][subMbIdx][subMbPartIdx]
+// residual_block_cavlc, F/residual.cpp:1069: one block read from the ferhip_legacy_nbits bits of ferhip_legacy_bits at the
+// cursor ferhip_legacy_bitpos, with nC stated in ferhip_legacy_nC like the writer's.  A malformed block (one that runs
+// past the written bits included) leaves the cursor alone and zeroes the block.
+extern "C" {
+unsigned int ferhip_legacy_bitpos = 0;
+int CodedBlockPatternLuma = 0, CodedBlockPatternChroma = 0;
+int *CodedBlockPatternLumaArray = nullptr, *CodedBlockPatternChromaArray = nullptr;
+int mb_type_array[FERHIP_LEGACY_MAX_MBS];
+int totalcoeff_array_luma[FERHIP_LEGACY_MAX_MBS][16], totalcoeff_array_chroma[2][FERHIP_LEGACY_MAX_MBS][4];
+}
+extern "C" void residual_block_cavlc(int coeffLevel[16], int startIdx, int endIdx, int maxNumCoeff)
+{
+    (void)startIdx;  // 0 and maxNumCoeff - 1 at every call site of the reference
+    (void)endIdx;
+    int32_t nc = ferhip_legacy_nC, mx = maxNumCoeff, tc = -1, coef[16];
+    uint64_t pos = ferhip_legacy_bitpos;
+    uint32_t used = 0;
+    const unsigned nbits = ferhip_legacy_nbits < sizeof(ferhip_legacy_bits) * 8 ? ferhip_legacy_nbits : (unsigned)sizeof(ferhip_legacy_bits) * 8;
+    int rc = ferhip_cavlc_parse_blocks(ferhip_legacy_bits, (nbits + 7) / 8, &pos, &nc, &mx, 1, coef, &tc, &used);
+    if (!rc && (tc < 0 || pos + used > nbits)) rc = FERHIP_E_DEVICE;
+    legacy_block("residual_block_cavlc", rc);
+    const int m = maxNumCoeff < 0 ? 0 : (maxNumCoeff > 16 ? 16 : maxNumCoeff);  // the caller's array may hold no more (ChromaDCLevel: 4)
+    for (int i = 0; i < m; i++) coeffLevel[i] = rc ? 0 : coef[i];
+    if (!rc) ferhip_legacy_bitpos += used;
+}
+
+static bool is_p_skip(int t) { return t == 31; }  // P_Skip of F/h264_globals.h:26-62, whatever the slice type (F/residual.cpp:473)
+
+// the macroblock CurrMbAddr and its neighbours A and B, from the globals, as a job of ferhip_residual_mbs; false: the state
+// does not describe a macroblock of the picture AllocateMemory sized
+static bool residual_job(ferhip_res_job &J, int op)
+{
+    const int mbw = frame.Lwidth >> 4;
+    if (mbw <= 0 || !CodedBlockPatternLumaArray || !fer_seam_mb_addr_ok(CurrMbAddr, g_mv_nmb < FERHIP_LEGACY_MAX_MBS ? g_mv_nmb : FERHIP_LEGACY_MAX_MBS))
+        return false;
+    J.op = op;
+    J.cls = pred_class_of(mb_type);
+    J.cbp_luma = CodedBlockPatternLuma;
+    J.cbp_chroma = CodedBlockPatternChroma;
+    J.avail = (CurrMbAddr % mbw != 0 ? 1 : 0) | (CurrMbAddr >= mbw ? 2 : 0);
+    for (int k = 0; k < 2; k++) {
+        if (!(J.avail & (1 << k))) continue;
+        const int m = k == 0 ? CurrMbAddr - 1 : CurrMbAddr - mbw;
+        ferhip_res_nb &N = J.nb[k];
+        N.p_skip = is_p_skip(mb_type_array[m]);
+        N.cbp_luma = CodedBlockPatternLumaArray[m];
+        N.cbp_chroma = CodedBlockPatternChromaArray[m];
+        for (int b = 0; b < 16; b++) N.tc_luma[b] = totalcoeff_array_luma[m][b];
+        for (int b = 0; b < 8; b++) N.tc_chroma[b >> 2][b & 3] = totalcoeff_array_chroma[b >> 2][m][b & 3];
+    }
+    return true;
+}
+
+// residual_write(), F/residual.cpp:300-372: the residual of macroblock CurrMbAddr from the level globals, appended to
+// ferhip_legacy_bits; the TotalCoeff of every block it codes goes into totalcoeff_array_* (F/residual.cpp:530-541)
+extern "C" void residual_write(void)
+{
+    ferhip_res_job *J = new ferhip_res_job();
+    ferhip_res_result *R = new ferhip_res_result();
+    int rc = residual_job(*J, FERHIP_RES_WRITE) ? 0 : FERHIP_E_ARG;
+    if (!rc) {
+        memcpy(J->lumaLevel, LumaLevel, sizeof LumaLevel);
+        memcpy(J->dc16, Intra16x16DCLevel, sizeof Intra16x16DCLevel);
+        memcpy(J->ac16, Intra16x16ACLevel, sizeof Intra16x16ACLevel);
+        memcpy(J->cdc, ChromaDCLevel, sizeof ChromaDCLevel);
+        memcpy(J->cac, ChromaACLevel, sizeof ChromaACLevel);
+        rc = ferhip_residual_mbs(J, R, 1);
+    }
+    if (!rc && (R->nbits < 0 || (size_t)ferhip_legacy_nbits + (size_t)R->nbits > sizeof(ferhip_legacy_bits) * 8)) rc = FERHIP_E_DEVICE;
+    legacy_block("residual_write", rc);
+    if (!rc) {
+        for (int b = 0; b < R->nbits; b++) {
+            const unsigned bit = (R->bits[b >> 3] >> (7 - (b & 7))) & 1u;
+            const unsigned pos = ferhip_legacy_nbits++;
+            if ((pos & 7) == 0) ferhip_legacy_bits[pos >> 3] = 0;
+            ferhip_legacy_bits[pos >> 3] |= (unsigned char)(bit << (7 - (pos & 7)));
+        }
+        for (int b = 0; b < 16; b++)
+            if ((J->cbp_luma & (1 << (b >> 2))) || (b == 0 && J->cls == 1)) totalcoeff_array_luma[CurrMbAddr][b] = R->tc_luma[b];
+        for (int b = 0; b < 8 && (J->cbp_chroma & 2); b++) totalcoeff_array_chroma[b >> 2][CurrMbAddr][b & 3] = R->tc_chroma[b >> 2][b & 3];
+    }
+    delete J;
+    delete R;
+}
+
+// residual(startIdx, endIdx), F/residual.cpp:959-1067, for (0, 15) -- the only pair the reference calls it with: the
+// residual of macroblock CurrMbAddr read at ferhip_legacy_bitpos into the level globals and totalcoeff_array_*, the blocks
+// the CBP leaves out zeroed.  A malformed macroblock leaves globals and cursor alone.
+extern "C" void residual(int startIdx, int endIdx)
+{
+    if (startIdx != 0 || endIdx != 15) {
+        legacy_block("residual", FERHIP_E_UNSUP);
+        return;
+    }
+    ferhip_res_job *J = new ferhip_res_job();
+    ferhip_res_result *R = new ferhip_res_result();
+    const unsigned nbits = ferhip_legacy_nbits < sizeof(ferhip_legacy_bits) * 8 ? ferhip_legacy_nbits : (unsigned)sizeof(ferhip_legacy_bits) * 8;
+    int rc = residual_job(*J, FERHIP_RES_PARSE) && ferhip_legacy_bitpos < nbits ? 0 : FERHIP_E_ARG;
+    if (!rc) {  // the job takes a window of the stream that starts on a 32-bit boundary
+        const unsigned first = (ferhip_legacy_bitpos >> 5) * 4, total = (nbits + 7) / 8;
+        J->nbytes = total - first < FERHIP_RES_BITS_MAX ? total - first : FERHIP_RES_BITS_MAX;
+        J->bit_pos = ferhip_legacy_bitpos - first * 8;
+        memcpy(J->bits, ferhip_legacy_bits + first, J->nbytes);
+        rc = ferhip_residual_mbs(J, R, 1);
+    }
+    if (!rc && (R->nbits < 0 || ferhip_legacy_bitpos + (unsigned)R->nbits > nbits)) rc = FERHIP_E_DEVICE;
+    legacy_block("residual", rc);
+    if (!rc) {
+        if (J->cls == 1) {
+            memcpy(Intra16x16DCLevel, R->dc16, sizeof Intra16x16DCLevel);
+            memcpy(Intra16x16ACLevel, R->ac16, sizeof Intra16x16ACLevel);
+        } else {
+            memcpy(LumaLevel, R->lumaLevel, sizeof LumaLevel);
+        }
+        memcpy(ChromaDCLevel, R->cdc, sizeof ChromaDCLevel);
+        memcpy(ChromaACLevel, R->cac, sizeof ChromaACLevel);
+        for (int b = 0; b < 16; b++) totalcoeff_array_luma[CurrMbAddr][b] = R->tc_luma[b];
+        for (int b = 0; b < 8; b++) totalcoeff_array_chroma[b >> 2][CurrMbAddr][b & 3] = R->tc_chroma[b >> 2][b & 3];
+        ferhip_legacy_bitpos += (unsigned)R->nbits;
+    }
+    delete J;
+    delete R;
+}
+
+// AllocateMemory() of F/mode_pred.cpp:22-39: the vector arrays [macroblock][subMbIdx][subMbPartIdx]; with them the
+// CodedBlockPattern arrays that init_h264_structures sizes from the picture (F/h264_globals.cpp:245-246)
 extern "C" void AllocateMemory(void)
 {
     const int nmb = (frame.Lwidth >> 4) * (frame.Lheight >> 4);
+    if (!CodedBlockPatternLumaArray || g_mv_nmb != nmb) {  // (like the vector arrays, never freed)
+        CodedBlockPatternLumaArray = new int[nmb > 0 ? nmb : 1]();
+        CodedBlockPatternChromaArray = new int[nmb > 0 ? nmb : 1]();
+    }
     if (mvL0x && g_mv_nmb == nmb) return;
     auto alloc3 = [&](int ***&p) {
         p = new int **[nmb];
@@ -451,6 +590,10 @@ static void mc_parts(const char *name, int predL[16][16], int predCr[8][8], int 
                      const int *parts)
 {
     if (!refPic || !refPic->L || !mvL0x) return;
+    if (!fer_seam_mb_addr_ok(mb, g_mv_nmb)) {  // mb indexes the vector arrays AllocateMemory sized
+        legacy_block(name, FERHIP_E_ARG);
+        return;
+    }
     std::vector<unsigned char> pic;
     pack_i420(refPic, pic);
     std::vector<int32_t> desc(nparts * 5), pl(nparts * 16), pb(nparts * 4), pr(nparts * 4);

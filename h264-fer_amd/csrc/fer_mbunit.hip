@@ -1,17 +1,24 @@
 // fer_mbunit.hip -- the per-macroblock unit-parity surface of SURVEY.md 8b: the reference's macroblock-level functions
 // as batched device calls over the SAME device functions the encode / decode kernels are built from (fer_dev.h,
-// fer_cavlc_dev.h), so that a known-answer test pins them one function at a time:
+// fer_cavlc_dev.h, fer_decode_dev.h), so that a known-answer test pins them one function at a time:
 //   quantizationTransform                       F/quantizationTransform.cpp:349-486   k_mb_unit, MBU_QT
 //   transformDecoding4x4LumaResidual            F/inttransform.cpp:133-155            MBU_DEC4
 //   transformDecodingIntra_16x16Luma            F/inttransform.cpp:157-213            MBU_DEC16
 //   transformDecodingChroma                     F/inttransform.cpp:237-320            MBU_DECC
 //   transformDecodingP_Skip                     F/inttransform.cpp:215-231            MBU_SKIP
 //   residual_block_cavlc_write / _size          F/residual.cpp:374-666 / :673-957     k_cavlc_blocks
+//   residual_block_cavlc                        F/residual.cpp:1069-1386              k_cavlc_parse_blocks
+//   residual_write / residual(0, 15)            F/residual.cpp:300-372 / :959-1067    k_residual_write, k_residual_parse
 //   MotionCompensateSubMBPart                   F/mocomp.cpp:152-195                  k_mc_parts
 //   forward / inverse residual, DC, scan        F/quantizationTransform.h, scaleTransform.h  k_block_kat
-// Not a fast path: one wavefront per job, records of plain int32.  The legacy-name shims are in fer_legacy.hip.
+// Not a fast path: one wavefront (or thread) per job, records of plain int32.  Every entry point checks its arguments
+// (fer_seam_host.h) before its first HIP call.  The legacy-name shims are in fer_legacy.hip.
 #include "fer_cavlc_dev.h"
 #include "fer_ctx.h"
+#include "fer_decode_dev.h"
+#include "fer_seam_host.h"
+
+#include <algorithm>
 
 // list[k] = c[zig-zag k] (transformScan, F/quantizationTransform.cpp:310-325); the Intra16x16AC / chroma AC form drops the DC
 __device__ __forceinline__ void mbu_scan(const int c[16], int32_t *list, bool ac)
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(64) void k_mb_unit(const ferhip_mb_job *jobs, ferhi
 
 extern "C" int ferhip_mb_unit(const ferhip_mb_job *jobs, ferhip_mb_result *results, size_t n)
 {
-    if (!jobs || !results || n == 0) return FERHIP_E_ARG;
+    if (fer_seam_check_mb_unit(jobs, results, n)) return FERHIP_E_ARG;
     ferhip_mb_job *dj = nullptr;
     ferhip_mb_result *dr = nullptr;
     auto body = [&]() -> int {
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(64) void k_cavlc_blocks(const int32_t *coef, const 
 extern "C" int ferhip_cavlc_blocks(const int32_t *coef, const int32_t *nC, const int32_t *max_num_coeff, size_t n, uint8_t *bits,
                                    uint32_t *nbits, int32_t *total_coeff)
 {
-    if (!coef || !nC || !max_num_coeff || !bits || !nbits || !total_coeff || n == 0) return FERHIP_E_ARG;
+    if (fer_seam_check_cavlc_blocks(coef, nC, max_num_coeff, n, bits, nbits, total_coeff)) return FERHIP_E_ARG;
     int32_t *dc = nullptr, *dn = nullptr, *dm = nullptr, *dt = nullptr;
     uint32_t *db = nullptr, *dl = nullptr, *ds = nullptr;
     std::vector<uint32_t> sz(n);
@@ -272,6 +279,296 @@ extern "C" int ferhip_cavlc_blocks(const int32_t *coef, const int32_t *nC, const
     return rc;
 }
 
+// ---- the parse direction.  dec_block is wave-uniform (fer_decode_dev.h), so the unit of work is a wavefront; the SEAM_PW
+// wavefronts of a workgroup share the decode tables in LDS, filled once, and the grid is capped so that the fill is
+// amortised over the blocks / macroblocks a wavefront walks.
+#define SEAM_PW 4
+#define SEAM_GRID_MAX 64  // 256 wavefronts
+__device__ __forceinline__ void mbu_wsync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ void mbu_fill_luts(DecLutsLds &lut, const DecLuts *__restrict__ luts)
+{
+    const uint32_t *src = (const uint32_t *)&luts->ct1[0][0];
+    uint32_t *dst = (uint32_t *)&lut;
+    for (int i = threadIdx.x; i < (int)(sizeof(DecLutsLds) / 4); i += 64 * SEAM_PW) dst[i] = src[i];
+    __syncthreads();
+}
+
+// residual_block_cavlc for n blocks of one stream (4-byte aligned, padded by 16 bytes): block i starts at bit_pos[i]
+__global__ __launch_bounds__(64 * SEAM_PW) void k_cavlc_parse_blocks(const uint8_t *bits, unsigned nbytes, const uint64_t *bit_pos,
+                                                                    const int32_t *nC, const int32_t *maxn, int n, int32_t *coef, int32_t *tc,
+                                                                    uint32_t *used, const DecLuts *__restrict__ luts)
+{
+    __shared__ uint32_t ring_w[SEAM_PW][128];
+    __shared__ __attribute__((aligned(4))) int16_t cf_w[SEAM_PW][16];
+    __shared__ DecLutsLds lut;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int16_t *cf = cf_w[wv];
+    mbu_fill_luts(lut, luts);
+    for (int i = blockIdx.x * SEAM_PW + wv; i < n; i += gridDim.x * SEAM_PW) {
+        const unsigned pos0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)bit_pos[i]);  // < 8 * nbytes <= 2^31
+        const int m = __builtin_amdgcn_readfirstlane(maxn[i]), c = __builtin_amdgcn_readfirstlane(nC[i]);
+        if (lane < 16) cf[lane] = 0;
+        mbu_wsync();
+        DecBits b;
+        db_open(b, bits, nbytes, pos0, ring_w[wv]);
+        int t = dec_block(b, &lut, cf, m, c);
+        mbu_wsync();
+        if (t >= 0 && b.pos > nbytes * 8u) t = -1;  // the reader zero-extends the stream: a block that ran out of it
+        if (lane < 16) coef[(size_t)i * 16 + lane] = t < 0 ? 0 : cf[lane];
+        if (lane == 0) {
+            tc[i] = t;
+            used[i] = b.pos - pos0;
+        }
+        mbu_wsync();  // cf and the ring are the next block's
+    }
+}
+
+extern "C" int ferhip_cavlc_parse_blocks(const uint8_t *bits, size_t nbytes, const uint64_t *bit_pos, const int32_t *nC,
+                                         const int32_t *max_num_coeff, size_t n, int32_t *coef, int32_t *total_coeff, uint32_t *bits_used)
+{
+    if (fer_seam_check_parse_blocks(bits, nbytes, bit_pos, nC, max_num_coeff, n, coef, total_coeff, bits_used)) return FERHIP_E_ARG;
+    DevBuf<uint8_t> dbits;
+    DevBuf<uint64_t> dpos;
+    DevBuf<int32_t> dn, dm, dc, dt;
+    DevBuf<uint32_t> du;
+    const size_t padded = ((nbytes + 3) & ~(size_t)3) + 16;  // what DecBits asks for: hipMalloc aligns, the tail is zero
+    if (dbits.reserve(padded) || dpos.reserve(n) || dn.reserve(n) || dm.reserve(n) || dc.reserve(n * 16) || dt.reserve(n) || du.reserve(n))
+        return FERHIP_E_HIP;
+    const DecLuts *luts = dec_luts(0);
+    if (!luts) return FERHIP_E_HIP;
+    CK(hipMemset(dbits, 0, padded));
+    CK(hipMemcpy(dbits, bits, nbytes, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dpos, bit_pos, n * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dn, nC, n * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dm, max_num_coeff, n * 4, hipMemcpyHostToDevice));
+    const unsigned grid = (unsigned)std::min<size_t>((n + SEAM_PW - 1) / SEAM_PW, SEAM_GRID_MAX);
+    hipLaunchKernelGGL(k_cavlc_parse_blocks, dim3(grid), dim3(64 * SEAM_PW), 0, 0, dbits.p, (unsigned)nbytes, dpos.p, dn.p, dm.p, (int)n, dc.p,
+                       dt.p, du.p, luts);
+    CK(hipGetLastError());
+    CK(hipMemcpy(coef, dc, n * 64, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(total_coeff, dt, n * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(bits_used, du, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- residual_write() / residual(0, 15) of one macroblock with nC derived from its neighbours.
+// WRITE: the encoder's block order and cavlc_nC (cavlc_residual_mb of fer_cavlc_dev.h, the body of k_cavlc), one thread
+// per job as in k_cavlc.  cavlc_nC reads the FerDev side information, so job j is stream j of a context of 2x2-macroblock
+// pictures (mbw = 2) and its macroblock sits at address cur[j], where exactly the neighbours it states exist.
+__global__ __launch_bounds__(64) void k_residual_write(FerDev d, const ferhip_res_job *jobs, const uint8_t *cur, int n, ferhip_res_result *res)
+{
+    __shared__ int16_t stage[16 * 64];
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= n || jobs[s].op != FERHIP_RES_WRITE) return;
+    const int mb = cur[s];
+    const size_t mbi = (size_t)s * d.nmb + mb;
+    const int16_t *lv = d.levels + mbi * FER_LEVELS;
+    ferhip_res_result &R = res[s];
+    BitW w;
+    bw_init<true>(w, (uint32_t *)R.bits, FERHIP_RES_BITS_MAX / 4, 0);  // (zeroed by the host: the writer merges words with atomicOr)
+    cavlc_residual_mb<true, 64>(w, d, s, mb, lv, d.cbp[mbi * 2], d.cbp[mbi * 2 + 1], jobs[s].cls == 1, stage + threadIdx.x);
+    bw_flush<true>(w);
+    R.nbits = w.bits > FERHIP_RES_BITS_MAX * 8u ? -1 : (int)w.bits;  // (words behind the buffer are dropped by the writer)
+    for (int k = 0; k < 16; k++) R.tc_luma[k] = d.tc[mbi * 24 + k];
+    for (int k = 0; k < 8; k++) R.tc_chroma[k >> 2][k & 3] = d.tc[mbi * 24 + 16 + k];
+}
+
+// PARSE: the decoder's dec_block with dec_nC over a two-entry DecNb row (the residual part of k_dec_parse's macroblock
+// loop), one wavefront per job.  dec_nC takes entry x - 1 of the row for A and entry x for B: with A the macroblock is at
+// x = 1, without at x = 0, and y says whether B exists.
+__global__ __launch_bounds__(64 * SEAM_PW) void k_residual_parse(const ferhip_res_job *jobs, ferhip_res_result *res, int n,
+                                                                const DecLuts *__restrict__ luts)
+{
+    __shared__ uint8_t tcur_w[SEAM_PW][24];
+    __shared__ uint32_t ring_w[SEAM_PW][128];
+    __shared__ int16_t cac_w[SEAM_PW][2][4][16];
+    __shared__ __attribute__((aligned(16))) int16_t mblv_w[SEAM_PW][FER_LEVELS];
+    __shared__ DecNb row_w[SEAM_PW][2];
+    __shared__ DecLutsLds lut;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint8_t *tcur = tcur_w[wv];
+    int16_t(*cac)[4][16] = cac_w[wv];
+    int16_t *lv = mblv_w[wv];
+    DecNb *row = row_w[wv];
+    mbu_fill_luts(lut, luts);
+    for (int j = blockIdx.x * SEAM_PW + wv; j < n; j += gridDim.x * SEAM_PW) {
+        const ferhip_res_job &J = jobs[j];
+        if (__builtin_amdgcn_readfirstlane(J.op) != FERHIP_RES_PARSE) continue;
+        ferhip_res_result &R = res[j];
+        const bool i16 = __builtin_amdgcn_readfirstlane(J.cls) == 1;
+        const int cbpL = __builtin_amdgcn_readfirstlane(J.cbp_luma), cbpC = __builtin_amdgcn_readfirstlane(J.cbp_chroma);
+        const int avail = __builtin_amdgcn_readfirstlane(J.avail);
+        const unsigned pos0 = (unsigned)__builtin_amdgcn_readfirstlane((int)J.bit_pos), nbytes = (unsigned)__builtin_amdgcn_readfirstlane((int)J.nbytes);
+        const int mbx = avail & 1, mby = (avail >> 1) & 1;
+        for (int k = 0; k < 2; k++) {  // A into entry 0, B into entry mbx
+            if (!(avail & (1 << k))) continue;
+            const ferhip_res_nb &N = J.nb[k];
+            DecNb &e = row[k ? mbx : 0];
+            if (lane < 24) e.tc[lane] = (uint8_t)(lane < 16 ? N.tc_luma[lane] : N.tc_chroma[(lane - 16) >> 2][lane & 3]);
+            if (lane == 0) {
+                e.cbpL = (uint8_t)N.cbp_luma;
+                e.cbpC = (uint8_t)N.cbp_chroma;
+                e.skip = N.p_skip ? 1 : 0;
+                e.i4 = 0;
+            }
+        }
+        for (int i = lane; i < FER_LEVELS / 2; i += 64) ((uint32_t *)lv)[i] = 0;
+        for (int i = lane; i < 2 * 4 * 16; i += 64) (&cac[0][0][0])[i] = 0;
+        if (lane < 24) tcur[lane] = 0;
+        mbu_wsync();
+        DecBits b;
+        db_open(b, J.bits, nbytes, pos0, ring_w[wv]);
+        bool bad = false;
+        // residual(0,15), F/residual.cpp:959-1067, as in k_dec_parse; the blocks the CBP leaves out stay zero
+        if (i16) {
+            int t = dec_block(b, &lut, lv + FER_LV_DC16, 16, dec_nC(row, mbx, mby, true, 0, 0, tcur, cbpL, cbpC));
+            bad |= t < 0;
+            if (t >= 0) tcur[0] = (uint8_t)t;
+            mbu_wsync();
+        }
+        for (int i8 = 0; i8 < 4 && !bad; i8++)
+            if (cbpL & (1 << i8)) {
+                for (int i4x = 0; i4x < 4 && !bad; i4x++) {
+                    int blk = i8 * 4 + i4x;
+                    int t = dec_block(b, &lut, lv + blk * 16, i16 ? 15 : 16, dec_nC(row, mbx, mby, true, blk, 0, tcur, cbpL, cbpC));
+                    bad |= t < 0;
+                    if (t >= 0) tcur[blk] = (uint8_t)t;
+                    mbu_wsync();
+                }
+            } else {  // F/residual.cpp:1051,1059: also entry 0 of an Intra16x16 macroblock, where the DC block's count stood
+                if (lane < 4) tcur[i8 * 4 + lane] = 0;
+                mbu_wsync();
+            }
+        for (int pl = 0; pl < 2 && !bad; pl++)
+            if (cbpC & 3) bad |= dec_block(b, &lut, lv + FER_LV_CDC + pl * 4, 4, -1) < 0;
+        for (int pl = 0; pl < 2 && !bad; pl++)
+            for (int cb = 0; cb < 4 && !bad; cb++)
+                if (cbpC & 2) {
+                    int t = dec_block(b, &lut, &cac[pl][cb][0], 15, dec_nC(row, mbx, mby, false, cb, pl, tcur, cbpL, cbpC));
+                    bad |= t < 0;
+                    if (t >= 0) tcur[16 + pl * 4 + cb] = (uint8_t)t;
+                    mbu_wsync();
+                }
+        mbu_wsync();
+        bad |= b.pos > nbytes * 8u;  // ran out of the stream (the reader zero-extends it)
+        if (lane == 0) R.nbits = bad ? -1 : (int)(b.pos - pos0);
+        if (!bad) {  // (the results start out zero)
+            if (lane < 16) R.tc_luma[lane] = tcur[lane];
+            if (lane >= 16 && lane < 24) R.tc_chroma[(lane - 16) >> 2][lane & 3] = tcur[lane];
+            int32_t *ll = i16 ? &R.ac16[0][0] : &R.lumaLevel[0][0];
+            for (int i = lane; i < 256; i += 64) ll[i] = lv[i];
+            if (i16 && lane < 16) R.dc16[lane] = lv[FER_LV_DC16 + lane];
+            if (lane < 8) R.cdc[lane >> 2][lane & 3] = lv[FER_LV_CDC + lane];
+            for (int i = lane; i < 2 * 4 * 16; i += 64) (&R.cac[0][0][0])[i] = (&cac[0][0][0])[i];
+        }
+        mbu_wsync();  // the LDS of this wavefront is the next job's
+    }
+}
+
+static int count_nz(const int32_t *v, int n)
+{
+    int c = 0;
+    for (int i = 0; i < n; i++) c += v[i] != 0;
+    return c;
+}
+
+extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result *results, size_t n)
+{
+    if (fer_seam_check_residual_mbs(jobs, results, n)) return FERHIP_E_ARG;
+    bool any_write = false, any_parse = false;
+    for (size_t j = 0; j < n; j++) (jobs[j].op == FERHIP_RES_WRITE ? any_write : any_parse) = true;
+    // the FerDev side information cavlc_nC and the block loop read: mb_type, cbp, tc, levels of [n streams][4 macroblocks]
+    std::vector<int> mbt;
+    std::vector<uint8_t> cbp, tc, cur(n, 0);
+    std::vector<int16_t> lev;
+    if (any_write) {
+        mbt.assign(n * 4, 0);
+        cbp.assign(n * 8, 0);
+        tc.assign(n * 96, 0);
+        lev.assign(n * 4 * FER_LEVELS, 0);
+    }
+    for (size_t j = 0; j < n && any_write; j++) {
+        const ferhip_res_job &J = jobs[j];
+        if (J.op != FERHIP_RES_WRITE) continue;
+        const int c = J.avail;  // both neighbours: address 3 (A = 2, B = 1); A only: 1 (A = 0); B only: 2 (B = 0); neither: 0
+        cur[j] = (uint8_t)c;
+        for (int k = 0; k < 2; k++) {
+            if (!(J.avail & (1 << k))) continue;
+            const ferhip_res_nb &N = J.nb[k];
+            const size_t m = j * 4 + (size_t)(k == 0 ? c - 1 : c - 2);
+            mbt[m] = N.p_skip ? FER_P_SKIP : 0;
+            cbp[m * 2] = (uint8_t)N.cbp_luma;
+            cbp[m * 2 + 1] = (uint8_t)N.cbp_chroma;
+            for (int b = 0; b < 16; b++) tc[m * 24 + b] = (uint8_t)N.tc_luma[b];
+            for (int b = 0; b < 8; b++) tc[m * 24 + 16 + b] = (uint8_t)N.tc_chroma[b >> 2][b & 3];
+        }
+        // the macroblock itself: its levels, and its own cbp and tc, which the blocks inside it read -- tc by the rule of
+        // k_p_resid / k_intra_mb: the non-zero levels of each block's list (15 entries for Intra16x16 AC and chroma AC)
+        const size_t m = j * 4 + (size_t)c;
+        int16_t *lv = lev.data() + m * FER_LEVELS;
+        const bool i16 = J.cls == 1;
+        cbp[m * 2] = (uint8_t)J.cbp_luma;
+        cbp[m * 2 + 1] = (uint8_t)J.cbp_chroma;
+        for (int b = 0; b < 16; b++) {
+            const int32_t *src = i16 ? J.ac16[b] : J.lumaLevel[b];
+            for (int k = 0; k < (i16 ? 15 : 16); k++) lv[b * 16 + k] = (int16_t)src[k];
+            if (J.cbp_luma & (1 << (b >> 2))) tc[m * 24 + b] = (uint8_t)count_nz(src, i16 ? 15 : 16);  // (0 for a block the CBP leaves out)
+            lv[FER_LV_DC16 + b] = (int16_t)J.dc16[b];
+        }
+        for (int b = 0; b < 8; b++) {
+            lv[FER_LV_CDC + b] = (int16_t)J.cdc[b >> 2][b & 3];
+            for (int k = 0; k < 15; k++) lv[FER_LV_CAC + b * 15 + k] = (int16_t)J.cac[b >> 2][b & 3][k];
+            if (J.cbp_chroma & 2) tc[m * 24 + 16 + b] = (uint8_t)count_nz(J.cac[b >> 2][b & 3], 15);
+        }
+    }
+    DevBuf<uint8_t> dj, dr, dcbp, dtc, dcur;
+    DevBuf<int> dmbt;
+    DevBuf<int16_t> dlev;
+    const size_t jbytes = n * sizeof(ferhip_res_job) + 16;  // DecBits reads a padded stream: behind the last job's bits
+    if (dj.reserve(jbytes) || dr.reserve(n * sizeof(ferhip_res_result))) return FERHIP_E_HIP;
+    if (any_write && (dcbp.reserve(cbp.size()) || dtc.reserve(tc.size()) || dcur.reserve(n) || dmbt.reserve(mbt.size()) || dlev.reserve(lev.size())))
+        return FERHIP_E_HIP;
+    const DecLuts *luts = any_parse ? dec_luts(0) : nullptr;
+    if (any_parse && !luts) return FERHIP_E_HIP;
+    CK(hipMemset(dj, 0, jbytes));
+    CK(hipMemcpy(dj, jobs, n * sizeof(ferhip_res_job), hipMemcpyHostToDevice));
+    CK(hipMemset(dr, 0, n * sizeof(ferhip_res_result)));
+    const ferhip_res_job *djobs = (const ferhip_res_job *)dj.p;
+    ferhip_res_result *dres = (ferhip_res_result *)dr.p;
+    if (any_write) {
+        CK(hipMemcpy(dmbt, mbt.data(), mbt.size() * sizeof(int), hipMemcpyHostToDevice));
+        CK(hipMemcpy(dcbp, cbp.data(), cbp.size(), hipMemcpyHostToDevice));
+        CK(hipMemcpy(dtc, tc.data(), tc.size(), hipMemcpyHostToDevice));
+        CK(hipMemcpy(dlev, lev.data(), lev.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        CK(hipMemcpy(dcur, cur.data(), n, hipMemcpyHostToDevice));
+        FerDev d = {};
+        d.mbw = d.mbh = 2;
+        d.nmb = 4;
+        d.S = (int)n;
+        d.mb_type = dmbt;
+        d.cbp = dcbp;
+        d.tc = dtc;
+        d.levels = dlev;
+        hipLaunchKernelGGL(k_residual_write, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, d, djobs, dcur.p, (int)n, dres);
+        CK(hipGetLastError());
+    }
+    if (any_parse) {
+        const unsigned grid = (unsigned)std::min<size_t>((n + SEAM_PW - 1) / SEAM_PW, SEAM_GRID_MAX);
+        hipLaunchKernelGGL(k_residual_parse, dim3(grid), dim3(64 * SEAM_PW), 0, 0, djobs, dres, (int)n, luts);
+        CK(hipGetLastError());
+    }
+    CK(hipMemcpy(results, dr, n * sizeof(ferhip_res_result), hipMemcpyDeviceToHost));
+    // TotalCoeff_luma_array[CurrMbAddr][0] of an Intra16x16 macroblock without AC blocks is what its DC block left there
+    // (F/residual.cpp:530-541); no neighbour can read it (the CBP gates it), the encoder's side information keeps the AC count
+    for (size_t j = 0; j < n; j++)
+        if (jobs[j].op == FERHIP_RES_WRITE && jobs[j].cls == 1 && !(jobs[j].cbp_luma & 1)) results[j].tc_luma[0] = count_nz(jobs[j].dc16, 16);
+    return 0;
+}
+
 // ---- MotionCompensateSubMBPart for n (macroblock, 4x4 sub-block, vector) triples on one reference picture:
 // thread = one luma sample of the 4x4 block (lanes 0..15), one chroma sample of either plane's 2x2 block (16..23),
 // and the four-sample row form the residual kernel uses for the same chroma samples (24..27: Cb rows, 28..31: Cr rows)
@@ -309,8 +606,7 @@ __global__ __launch_bounds__(64) void k_mc_parts(const uint8_t *ref, int W, int 
 extern "C" int ferhip_mc_sub_mb_parts(const uint8_t *ref_i420, int width, int height, const int32_t *desc, size_t n, int32_t *predL,
                                       int32_t *predCb, int32_t *predCr)
 {
-    if (!ref_i420 || !desc || !predL || !predCb || !predCr || n == 0 || width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return FERHIP_E_ARG;
+    if (fer_seam_check_mc_parts(ref_i420, width, height, desc, n, predL, predCb, predCr)) return FERHIP_E_ARG;
     const size_t fsz = (size_t)width * height * 3 / 2;
     uint8_t *dref = nullptr;
     int32_t *dd = nullptr, *dl = nullptr, *db = nullptr, *dr = nullptr, *rb = nullptr, *rr = nullptr;

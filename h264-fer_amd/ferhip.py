@@ -664,6 +664,91 @@ def cavlc_blocks(coef, nC, max_num_coeff):
     return bits, nb, tc
 
 
+def cavlc_parse_blocks(bits, bit_pos, nC, max_num_coeff):
+    """ferhip_cavlc_parse_blocks: block i read at bit position bit_pos[i] of the stream `bits` (bytes or uint8 array)
+    -> (coef [n][16], total_coeff [n] (-1 = malformed), bits_used [n])"""
+    lib = load_library()
+    b = np.ascontiguousarray(np.frombuffer(bits, np.uint8) if isinstance(bits, (bytes, bytearray)) else bits, np.uint8).reshape(-1)
+    pos = np.ascontiguousarray(bit_pos, np.uint64).reshape(-1)
+    n = pos.shape[0]
+    nc = np.ascontiguousarray(np.broadcast_to(np.asarray(nC, np.int32), (n,)))
+    mx = np.ascontiguousarray(np.broadcast_to(np.asarray(max_num_coeff, np.int32), (n,)))
+    coef = np.zeros((n, 16), np.int32)
+    tc = np.zeros(n, np.int32)
+    used = np.zeros(n, np.uint32)
+    lib.ferhip_cavlc_parse_blocks.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 3
+    _chk(lib.ferhip_cavlc_parse_blocks(b.ctypes.data, b.size, pos.ctypes.data, nc.ctypes.data, mx.ctypes.data, n, coef.ctypes.data, tc.ctypes.data,
+                                       used.ctypes.data), "ferhip_cavlc_parse_blocks")
+    return coef, tc, used
+
+
+RES_WRITE, RES_PARSE = 0, 1
+RES_BITS_MAX = 2048
+_RES_LEVELS = [("lumaLevel", C.c_int32 * 256), ("dc16", C.c_int32 * 16), ("ac16", C.c_int32 * 256), ("cdc", C.c_int32 * 8), ("cac", C.c_int32 * 128)]
+
+
+class ResNb(C.Structure):
+    """ferhip_res_nb of include/ferhip.h: what nC needs from a neighbouring macroblock"""
+    _fields_ = [("p_skip", C.c_int32), ("cbp_luma", C.c_int32), ("cbp_chroma", C.c_int32), ("tc_luma", C.c_int32 * 16), ("tc_chroma", C.c_int32 * 8)]
+
+
+class ResJob(C.Structure):
+    """ferhip_res_job of include/ferhip.h"""
+    _fields_ = [("op", C.c_int32), ("cls", C.c_int32), ("cbp_luma", C.c_int32), ("cbp_chroma", C.c_int32), ("avail", C.c_int32),
+                ("nb", ResNb * 2)] + _RES_LEVELS + [("bit_pos", C.c_uint32), ("nbytes", C.c_uint32), ("bits", C.c_uint8 * RES_BITS_MAX)]
+
+
+class ResResult(C.Structure):
+    _fields_ = [("nbits", C.c_int32), ("tc_luma", C.c_int32 * 16), ("tc_chroma", C.c_int32 * 8)] + _RES_LEVELS + [("bits", C.c_uint8 * RES_BITS_MAX)]
+
+
+def residual_jobs(jobs):
+    """a list of dicts -> a ferhip_res_job array.  Scalars and arrays by field name; nb = (A, B), each None or a dict of
+    the fields of ferhip_res_nb; bits = the stream of a PARSE job (bytes or uint8 array; nbytes defaults to its length)"""
+    J = (ResJob * len(jobs))()
+    for k, j in enumerate(jobs):
+        for name, val in j.items():
+            if name == "nb":
+                for i, nb in enumerate(val):
+                    for f, v in (nb or {}).items():
+                        if isinstance(v, (int, np.integer, bool)):
+                            setattr(J[k].nb[i], f, int(v))
+                        else:
+                            a = np.ascontiguousarray(v, np.int32).reshape(-1)
+                            C.memmove(getattr(J[k].nb[i], f), a.ctypes.data, a.nbytes)
+            elif name == "bits":
+                a = np.ascontiguousarray(np.frombuffer(val, np.uint8) if isinstance(val, (bytes, bytearray)) else val, np.uint8).reshape(-1)
+                if a.size > RES_BITS_MAX:
+                    raise FerHipError(f"a PARSE job takes at most {RES_BITS_MAX} bytes")
+                C.memmove(J[k].bits, a.ctypes.data, a.size)
+                if "nbytes" not in j:
+                    J[k].nbytes = a.size
+            elif isinstance(val, (int, np.integer)):
+                setattr(J[k], name, int(val))
+            else:
+                a = np.ascontiguousarray(val, np.int32).reshape(-1)
+                C.memmove(getattr(J[k], name), a.ctypes.data, a.nbytes)
+    return J
+
+
+def residual_mbs(jobs):
+    """ferhip_residual_mbs: jobs = list of dicts (see residual_jobs) -> list of dicts: nbits, tc_luma [16], tc_chroma [8],
+    the level arrays (PARSE), bits (uint8 [RES_BITS_MAX], WRITE)"""
+    lib = load_library()
+    n = len(jobs)
+    J = residual_jobs(jobs)
+    R = (ResResult * n)()
+    lib.ferhip_residual_mbs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    _chk(lib.ferhip_residual_mbs(J, R, n), "ferhip_residual_mbs")
+    out = []
+    for k in range(n):
+        r = {f: np.frombuffer(getattr(R[k], f), np.int32).copy() for f, _ in ResResult._fields_ if f not in ("nbits", "bits")}
+        r["nbits"] = int(R[k].nbits)
+        r["bits"] = np.frombuffer(R[k].bits, np.uint8).copy()
+        out.append(r)
+    return out
+
+
 def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5, flags=None):
     """ferhip_frame_nal_blocks on a list of payloads (bytes or uint8 arrays) -> (return code, out [cap] pre-filled with
     `fill`, index [n + 1] of dtype AU).  cap None = room for every payload with every second byte escaped.

@@ -705,6 +705,48 @@ int ferhip_mb_unit(const ferhip_mb_job *jobs, ferhip_mb_result *results, size_t 
  * total_coeff[n] the TotalCoeff the block leaves for its neighbours */
 int ferhip_cavlc_blocks(const int32_t *coef, const int32_t *nC, const int32_t *max_num_coeff, size_t nblocks, uint8_t *bits,
                         uint32_t *nbits, int32_t *total_coeff);
+/* residual_block_cavlc(coeffLevel, 0, maxNumCoeff - 1, maxNumCoeff) (F/residual.cpp:1069) for n blocks with nC given
+ * (-1 = chroma DC).  Block i is read from bit position bit_pos[i] (MSB first) of the nbytes bytes at `bits`.
+ * coef[n][16] receives the levels (zero behind maxNumCoeff).
+ * total_coeff[n] receives TotalCoeff, or -1 for a malformed block (its coef row is then all zero); a block that runs
+ * past the end of the stream is malformed.
+ * bits_used[n] receives the bits consumed (undefined where total_coeff is -1).
+ * nbytes is at most 2^28 (the device reader keeps bit positions in 32 bits). */
+int ferhip_cavlc_parse_blocks(const uint8_t *bits, size_t nbytes, const uint64_t *bit_pos, const int32_t *nC,
+                              const int32_t *max_num_coeff, size_t nblocks, int32_t *coef, int32_t *total_coeff,
+                              uint32_t *bits_used);
+/* The residual of one macroblock with nC derived from its neighbours, both directions: residual_write() through the
+ * encoder's block order and cavlc_nC, residual(0, 15) through the decoder's dec_block and dec_nC.  A job is one macroblock
+ * and the state of its left (A) and upper (B) neighbours; levels use the layouts of ferhip_mb_job and must fit 16 bits.
+ * cbp_luma is 0..15 (0 or 15 for cls 1), cbp_chroma 0..2; a neighbour's tc entries are 0..16.
+ * WRITE reports 0 in the tc entries of the blocks the CBP leaves out (the reference leaves those entries as they were);
+ * PARSE zeroes their levels and counts, as residual() does.  Of the level arrays PARSE fills lumaLevel (cls 0, 2) or dc16
+ * and ac16 (cls 1), cdc and cac; the others come back zero. */
+#define FERHIP_RES_WRITE 0 /* residual_write(), F/residual.cpp:300-372 */
+#define FERHIP_RES_PARSE 1 /* residual(0, 15),  F/residual.cpp:959-1067 */
+#define FERHIP_RES_BITS_MAX 2048
+typedef struct {
+    int32_t p_skip, cbp_luma, cbp_chroma, tc_luma[16], tc_chroma[2][4];
+} ferhip_res_nb;
+typedef struct {
+    int32_t op, cls /* MbPartPredMode(mb_type, 0) as in ferhip_mb_job */, cbp_luma, cbp_chroma;
+    int32_t avail;                                                                /* bit 0: mbAddrA exists, bit 1: mbAddrB exists */
+    ferhip_res_nb nb[2];                                                          /* A, B (ignored where not available) */
+    int32_t lumaLevel[16][16], dc16[16], ac16[16][16], cdc[2][4], cac[2][4][16]; /* WRITE: in (layouts of ferhip_mb_job) */
+    uint32_t bit_pos, nbytes;                                                     /* PARSE: in */
+    uint8_t bits[FERHIP_RES_BITS_MAX];                                            /* PARSE: in */
+} ferhip_res_job;
+typedef struct {
+    int32_t nbits;                        /* bits written / consumed; -1: malformed (PARSE) or longer than the buffer (WRITE) */
+    int32_t tc_luma[16], tc_chroma[2][4]; /* what the macroblock leaves for its neighbours (the reference's TotalCoeff arrays) */
+    int32_t lumaLevel[16][16], dc16[16], ac16[16][16], cdc[2][4], cac[2][4][16]; /* PARSE: out */
+    uint8_t bits[FERHIP_RES_BITS_MAX];    /* WRITE: out, MSB first */
+} ferhip_res_result;
+int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result *results, size_t njobs);
+/* All five entry points of this surface check their arguments before the first HIP call and return FERHIP_E_ARG for a null
+ * pointer, n == 0, max_num_coeff outside {4, 15, 16}, nC < -1, nC == -1 with max_num_coeff != 4, an op, cls, blk, qp, qpc,
+ * cbp, avail, sub / part index or macroblock address out of range, a bit_pos at or behind 8 * nbytes, nbytes == 0 or above
+ * its limit. */
 /* MotionCompensateSubMBPart(predL, predCr, predCb, refPic, mbPartIdx, subMbIdx, subMbPartIdx) (F/mocomp.cpp:152) for n
  * sub-blocks of one reference picture (host I420, width x height): desc[n][5] = macroblock address, subMbIdx, subMbPartIdx,
  * mvx, mvy (quarter samples); predL[n][16] = the 4x4 luma block, predCb / predCr[n][4] = the 2x2 chroma blocks (raster).

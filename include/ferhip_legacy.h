@@ -109,9 +109,35 @@ unsigned int residual_block_cavlc_size(int coeffLevel[16], int startIdx, int end
 void MotionCompensateSubMBPart(int predL[16][16], int predCr[8][8], int predCb[8][8], frame_type *refPic, int mbPartIdx, int subMbIdx,
                                int subMbPartIdx);                                                                         /* F/mocomp.cpp:152 */
 void Decode(int predL[16][16], int predCr[8][8], int predCb[8][8]);                                                        /* :200 */
-/* coded_mb_size (F/rbsp_encoding.cpp:330) and intraPrediction / intraPredictionEncoding (F/intra.cpp:770,949) have no
- * stand-alone shim: their device form is the body of k_intra_mb, which needs the reconstructed neighbourhood of a whole
- * picture.  Their unit parity is checked on every macroblock of a picture through ferhip_read_buffer(FERHIP_BUF_MBSIZE). */
+/* ---- the CAVLC seam in both directions, macroblock layer included (ferhip_cavlc_parse_blocks, ferhip_residual_mbs of
+ * ferhip.h).  The block parser reads the ferhip_legacy_nbits bits of ferhip_legacy_bits at the cursor ferhip_legacy_bitpos
+ * and advances it, with nC stated in ferhip_legacy_nC like the writer's; a malformed block (one that runs past the written
+ * bits included) leaves the cursor alone, zeroes the block and prints the message.
+ * residual_write() and residual(0, 15) derive nC themselves, from where the reference keeps the neighbours' state:
+ * mb_type_array, CodedBlockPatternLumaArray / ChromaArray, totalcoeff_array_luma / _chroma (F/h264_globals.h:102-109,
+ * 187-188), for macroblock CurrMbAddr of a picture `frame`.Lwidth wide, with CodedBlockPatternLuma / Chroma as its own
+ * pattern.  As in the reference, the caller (setCodedBlockPattern, the macroblock-layer parser) stores mb_type and the
+ * pattern of the macroblock in the arrays as well; the shims store its TotalCoeff.  AllocateMemory sizes the pattern
+ * arrays from `frame`; the fixed-size arrays hold FERHIP_LEGACY_MAX_MBS macroblocks, as the reference's do.
+ * TotalCoeff_luma_array / TotalCoeff_chroma_array of F/residual.h are not exported: the reference reads them in get_nC
+ * (F/residual.cpp:111) alone, by sample position, and nothing calls that; what residual_write() and residual() read and
+ * write is totalcoeff_array_*.  Only (0, 15) is supported by residual(); anything else prints the message and returns. */
+#define FERHIP_LEGACY_MAX_MBS 10000
+extern unsigned int ferhip_legacy_bitpos;
+extern int CodedBlockPatternLuma, CodedBlockPatternChroma;                  /* F/h264_globals.cpp:171-172 */
+extern int *CodedBlockPatternLumaArray, *CodedBlockPatternChromaArray;      /* [macroblock] */
+extern int mb_type_array[FERHIP_LEGACY_MAX_MBS];
+extern int totalcoeff_array_luma[FERHIP_LEGACY_MAX_MBS][16], totalcoeff_array_chroma[2][FERHIP_LEGACY_MAX_MBS][4];
+void residual_block_cavlc(int coeffLevel[16], int startIdx, int endIdx, int maxNumCoeff); /* F/residual.cpp:1069 */
+void residual_write(void);                                                                 /* :300 */
+void residual(int startIdx, int endIdx);                                                   /* :959 */
+/* Every shim above that takes CurrMbAddr checks it first: against the macroblocks of `frame`, or, where it indexes what
+ * AllocateMemory sized, against the macroblock count of the last AllocateMemory.
+ * What has no stand-alone shim: DeriveMVs / ClearMVD (F/mode_pred.cpp), per-macroblock interEncoding, coded_mb_size
+ * (F/rbsp_encoding.cpp:330) and intraPrediction / intraPredictionEncoding (F/intra.cpp:770,949).  The device form of the
+ * last three is the body of k_intra_mb or a whole-picture search, which needs the reconstructed neighbourhood of a whole
+ * picture; their unit parity is checked on every macroblock of a picture through ferhip_read_buffer(FERHIP_BUF_MBSIZE) and
+ * the motion-search lists. */
 
 #ifdef __cplusplus
 }
