@@ -168,6 +168,8 @@ typedef struct fo_ctx {
     int (*dbg_mbsize)[2];
     /* test hook: the candidate lists of interEncoding, one record per 8x8 partition; NULL (default) = not recorded */
     struct fo_me_rec *me_rec;
+    /* test hook: the largest |level| fo_encode_slice handed to the CAVLC writer in the last picture (fo_dbg_max_level) */
+    int dbg_max_level;
 } fo_ctx;
 
 /* What fo_interEncoding searched for one 8x8 partition (fo_dbg_me_record).  List 0 = stage 1 (17 entries around the
@@ -186,6 +188,8 @@ _Static_assert(sizeof(fo_me_rec) == FO_ME_REC_INTS * sizeof(int), "fo_py.Oracle.
 #endif
 int *fo_dbg_me_record(struct fo_ctx *c, int on); /* fo_debug.c: start (records zeroed) / stop recording */
 int *fo_dbg_me_lists(struct fo_ctx *c);          /* [nmb][4] fo_me_rec, NULL when recording is off */
+int fo_dbg_max_level(struct fo_ctx *c);          /* fo_debug.c: largest |level| written in the last picture */
+void fo_dbg_note_levels(struct fo_ctx *c);       /* fo_debug.c: called by fo_encode_slice before residual_write */
 
 fo_ctx *fo_create(int W, int H);
 void fo_destroy(fo_ctx *c);

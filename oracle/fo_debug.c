@@ -77,3 +77,33 @@ int *fo_dbg_me_record(fo_ctx *c, int on)
     return (int *)c->me_rec;
 }
 int *fo_dbg_me_lists(fo_ctx *c) { return (int *)c->me_rec; }
+
+/* The largest |level| fo_encode_slice produced in the last picture, over the level arrays that the macroblock's
+ * mb_type and CBP cause to be written (the block list of residual_blocks, fo_cavlc.c).  Above 2063 a level does not fit
+ * the 12-bit escape suffix at suffixLength 0 and the reference's writer is not pinned.  Changes no output. */
+int fo_pred_class(const fo_ctx *c, int mb_type);
+static void note(fo_ctx *c, const int *lv, int n)
+{
+    for (int i = 0; i < n; i++) {
+        int a = lv[i] < 0 ? -lv[i] : lv[i];
+        if (a > c->dbg_max_level) c->dbg_max_level = a;
+    }
+}
+void fo_dbg_note_levels(fo_ctx *c)
+{
+    int i16 = fo_pred_class(c, c->cur_mb_type) == 1;
+    if (i16) note(c, c->lv.DC16, 16);
+    for (int blk = 0; blk < 16; blk++)
+        if (c->cbpL & (1 << (blk >> 2))) {
+            if (i16)
+                note(c, c->lv.AC16[blk], 15);
+            else
+                note(c, c->lv.Lumalevel[blk], 16);
+        }
+    for (int k = 0; k < 2; k++) {
+        if (c->cbpC & 3) note(c, c->lv.CDC[k], 4);
+        if (c->cbpC & 2)
+            for (int b = 0; b < 4; b++) note(c, c->lv.CAC[k][b], 15);
+    }
+}
+int fo_dbg_max_level(fo_ctx *c) { return c->dbg_max_level; }

@@ -223,6 +223,7 @@ size_t fo_encode_slice(fo_ctx *c, int nal_type, uint8_t *rbsp, size_t cap)
         c->frame_num++;
     }
     slice_header(c, &w, nal_type);
+    c->dbg_max_level = 0;
 
     int predL[16][16], predCb[8][8], predCr[8][8];
     int mb_skip_run = 0;
@@ -283,6 +284,7 @@ size_t fo_encode_slice(fo_ctx *c, int nal_type, uint8_t *rbsp, size_t cap)
         }
         if (c->cbpL > 0 || c->cbpC > 0 || pc == 1) {
             fo_bw_se(&w, 0); /* mb_qp_delta */
+            fo_dbg_note_levels(c);
             fo_residual_write(c, &w);
         } else {
             /* clear_residual_structures(), F/residual.cpp:28-49: luma levels and chroma DC only */

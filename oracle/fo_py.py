@@ -62,6 +62,8 @@ def lib():
         L.fo_dbg_me_record.argtypes = [vp, i]
         L.fo_dbg_me_lists.restype = vp
         L.fo_dbg_me_lists.argtypes = [vp]
+        L.fo_dbg_max_level.restype = i
+        L.fo_dbg_max_level.argtypes = [vp]
         L.fo_dbg_set_mb.argtypes = [vp, i, i, i, i]
         L.fo_dbg_set_mv.argtypes = [vp, i, i, i, i, i]
         L.fo_mc_sub.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i]
@@ -212,6 +214,21 @@ class Oracle:
 
     def cbp(self):
         return np.stack([_arr(self.L.fo_dbg_cbp(self.c, k), self.nmb, np.int32) for k in range(2)], -1).copy()
+
+    def tc(self):
+        """TotalCoeff as the CAVLC writer left it, [nmb][24]: 16 luma blocks, 4 Cb, 4 Cr (the layout of FERHIP_BUF_TC).
+        Only the blocks that the macroblock's CBP sends through the writer are those of the coded macroblock."""
+        l = _arr(self.L.fo_dbg_tc_l(self.c), self.nmb * 16, np.int32).reshape(self.nmb, 16)
+        ch = _arr(self.L.fo_dbg_tc_c(self.c), self.nmb * 8, np.int32).reshape(self.nmb, 8)
+        return np.concatenate([l, ch], 1)
+
+    def i4mode(self):
+        """Intra4x4PredMode [nmb][16]; defined on the Intra4x4 macroblocks of the last I picture"""
+        return _arr(self.L.fo_dbg_i4mode(self.c), self.nmb * 16, np.int32).reshape(self.nmb, 16).copy()
+
+    def max_level(self):
+        """largest |level| encode_slice handed to the CAVLC writer in the last picture"""
+        return int(self.L.fo_dbg_max_level(self.c))
 
 
 class _BW(C.Structure):
