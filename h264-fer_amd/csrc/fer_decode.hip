@@ -131,8 +131,10 @@ __global__ void k_dec_build_luts(DecLuts *L)
     }
 }
 
-// P macroblock vectors: PredictMV + DeriveMVs (F/mode_pred.cpp:381-482), quadrant storage
-__device__ void dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int mb, int type, const int mvd[4][2], const int sub[4])
+// P macroblock vectors: PredictMV + DeriveMVs (F/mode_pred.cpp:381-482), quadrant storage.  The vectors are kept as 16-bit
+// quarter samples (a level allows +-8192); false when a component does not fit: the caller refuses the picture instead of
+// predicting from a wrapped vector (the reference keeps ints)
+__device__ bool dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int mb, int type, const int mvd[4][2], const int sub[4])
 {
     MvCtx c;
     c.mv = mvs;
@@ -155,8 +157,9 @@ __device__ void dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int 
             o[q * 2] = (short)mx;
             o[q * 2 + 1] = (short)my;
         }
-        return;
+        return true;  // (zero, or the median of vectors that fit)
     }
+    bool fits = true;
     int np = type == 0 ? 1 : (type <= 2 ? 2 : 4);
     for (int i = 0; i < np; i++) {
         int px, py;
@@ -166,6 +169,7 @@ __device__ void dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int 
             predict_luma(c, i, px, py);
         px += mvd[i][0];
         py += mvd[i][1];
+        fits &= px == (short)px && py == (short)py;
         // quadrants covered by partition i
         int q0, q1, q2 = -1, q3 = -1;
         if (np == 1) {
@@ -189,6 +193,7 @@ __device__ void dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int 
                 o[qs[k] * 2 + 1] = (short)py;
             }
     }
+    return fits;
 }
 
 // One wavefront per (stream, picture of the window).  What a picture inherits from its predecessor -- the
@@ -320,6 +325,25 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
                     cur++;
                 }
                 if (cur != 0 || run > 0) more = db_more(b);
+                if (more && cur >= d.nmb) {
+                    // data behind a skip run that ends the picture: the reference goes on to parse a macroblock past the picture
+                    // (F/rbsp_decoding.cpp:121 tests moreDataFlag alone).  It is followed as far as it only reads the stream --
+                    // mb_type and an intra type's prediction modes, with the fatal errors the reference has there -- not into
+                    // what it then decodes behind its pictures: short of those errors the picture is complete.
+                    const int t = (int)db_ue(b);
+                    bool past = t > 31;
+                    if (!past && t >= 5 && t <= 29) {
+                        if (t == 5)
+                            for (int blk = 0; blk < 16; blk++)
+                                if (!db_bit(b)) db_bits(b, 3);
+                        past = db_ue(b) > 3;
+                    }
+                    if (past) {
+                        atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                        perr = FER_ERR_DEC_SYNTAX;
+                    }
+                    break;
+                }
             }
             if (!(more && cur < d.nmb)) break;
             const size_t mbi = (size_t)s * d.nmb + cur;
@@ -490,7 +514,11 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
             n_inherit += delta_known ? 0 : 1;
             p_dec_qp[mbi] = (uint8_t)QPy;
             if (inter) {
-                dec_derive_mvs(d, mvs, mbt, cur, t, mvd, sub);
+                if (!dec_derive_mvs(d, mvs, mbt, cur, t, mvd, sub)) {  // a vector past 16 bits
+                    atomicOr(&d.status[s], FER_ERR_DEC_SYNTAX);
+                    perr = FER_ERR_DEC_SYNTAX;
+                    break;
+                }
             } else if (i4) {
                 // getIntra4x4PredMode, F/intra.cpp:77-136
                 unsigned long long cm = 0;  // this macroblock's modes, 4 bits per block
@@ -613,8 +641,10 @@ __device__ __forceinline__ int dec_qpc(const FerDev &d, int s, int QPy)
     return qpc[iclamp(QPy + (int)d.hdr[s * 4], 0, 51)];
 }
 
-// chroma residual of lanes 16..23 (dc Hadamard shared through shuffles), F/inttransform.cpp:237-320
-__device__ __forceinline__ void recon_chroma(const FerDev &d, const int16_t *lv, int lane, int qpc_, const uint8_t *pred,
+// chroma residual of lanes 16..23 (dc Hadamard shared through shuffles), F/inttransform.cpp:237-320.  pred: uint8_t samples
+// (motion compensation) or int16_t (intra prediction, which may hold the -1 of a neighbour that does not exist)
+template <typename PredT>
+__device__ __forceinline__ void recon_chroma(const FerDev &d, const int16_t *lv, int lane, int qpc_, const PredT *pred,
                                              uint8_t *C0, uint8_t *C1, int Wc, int xp, int yp)
 {
     const bool isC = lane >= 16 && lane < 24;
@@ -686,6 +716,9 @@ __global__ __launch_bounds__(64) void k_dec_inter(FerDev d)
 __global__ __launch_bounds__(64) void k_dec_intra(FerDev d, int diag)
 {
     __shared__ IntraLds L;
+    // chroma prediction as the reference's ints: a stream may name the horizontal / vertical mode where the left / upper
+    // macroblock does not exist, and the prediction is then the -1 marker itself (IntraLds.predC, 8 bits, is the encoder's)
+    __shared__ int16_t predC[2][8][8];
     const int lane = threadIdx.x;
     const int s = blockIdx.y;
     int y_lo = diag - (d.mbw - 1);
@@ -721,10 +754,10 @@ __global__ __launch_bounds__(64) void k_dec_intra(FerDev d, int diag)
     const int16_t *lv = d.levels + mbi * FER_LEVELS;
     const int QPy = d.dec_qp[mbi];
     const int chroma_mode = d.chroma_mode[mbi];
-    // chroma prediction -> L.predC (same code path as the encoder's phase 2a)
+    // chroma prediction (pred_chroma_px: the code of the encoder's phase 2a)
     {
         int cx = lane & 7, cy = lane >> 3;
-        for (int pl = 0; pl < 2; pl++) L.predC[pl][cy][cx] = (uint8_t)pred_chroma_px(L.cfr[pl], chroma_mode, cx, cy, availL, availT);
+        for (int pl = 0; pl < 2; pl++) predC[pl][cy][cx] = (int16_t)pred_chroma_px(L.cfr[pl], chroma_mode, cx, cy, availL, availT);
     }
     if (i16) {
         P16 q16;
@@ -785,7 +818,7 @@ __global__ __launch_bounds__(64) void k_dec_intra(FerDev d, int diag)
         }
     }
     __syncthreads();
-    recon_chroma(d, lv, lane, dec_qpc(d, s, QPy), &L.predC[0][0][0], Cp[0], Cp[1], Wc, xp, yp);
+    recon_chroma(d, lv, lane, dec_qpc(d, s, QPy), &predC[0][0][0], Cp[0], Cp[1], Wc, xp, yp);
 }
 
 // the decode tables of the current device; null if they cannot be allocated

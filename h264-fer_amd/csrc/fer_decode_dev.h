@@ -155,9 +155,12 @@ __device__ int dec_block(DecBits &b, const DecLutsLds *L, int16_t *coef, int max
     if (TotalCoeff > maxNumCoeff) return -1;
     const int lane = (int)(threadIdx.x & 63);
     int lvv = 0;
-    if (TrailingOnes) {  // the sign bits of the trailing ones, first coefficient first
-        const unsigned sg = db_bits(b, TrailingOnes);
-        lvv = 1 - 2 * (int)((sg >> ((TrailingOnes - 1 - lane) & 31)) & 1u);
+    // the sign bits of the trailing ones, first coefficient first.  The 6-bit coeff_token of nC >= 8 can name more trailing
+    // ones than coefficients; the reference reads one sign per coefficient then (F/residual.cpp:1249-1254), so does this
+    const int nsign = min(TrailingOnes, TotalCoeff);
+    if (nsign) {
+        const unsigned sg = db_bits(b, nsign);
+        lvv = 1 - 2 * (int)((sg >> ((nsign - 1 - lane) & 31)) & 1u);
     }
     int suffixLength = (TotalCoeff > 10 && TrailingOnes < 3) ? 1 : 0;
     int st = TrailingOnes < 3 ? 7 + suffixLength : suffixLength;
@@ -193,6 +196,8 @@ __device__ int dec_block(DecBits &b, const DecLutsLds *L, int16_t *coef, int max
         if (e == 0) return -1;
         db_skip(b, e >> 8);
         zerosLeft = (int)(e & 0xff);
+        // (the 4x4 total_zeros tables serve the 15-coefficient blocks too and can name one zero too many for them)
+        if (TotalCoeff + zerosLeft > maxNumCoeff) return -1;
     }
     unsigned long long runs = 0;  // run_before of coefficient j in bits 4j..4j+3 (scalar registers, no LDS round trips)
     int j = 0;
@@ -213,6 +218,10 @@ __device__ int dec_block(DecBits &b, const DecLutsLds *L, int16_t *coef, int max
             db_skip(b, e >> 8);
             rb = (int)(e & 0xff);
         }
+        // a run_before above zerosLeft (only the escape above can code one): the reference lets zerosLeft go negative and
+        // stores the levels in front of the block, into a neighbouring block of its level array or outside it.  Refused, like
+        // the other blocks whose coefficients do not fit them (TotalCoeff or total_zeros too large, above).
+        if (rb > zerosLeft) return -1;
         runs |= (unsigned long long)(rb & 15) << (4 * j);
         zerosLeft -= rb;
     }

@@ -491,7 +491,32 @@ int ferhip_set_reference(ferhip_ctx *c, const void *src);
  * every stream at once, reconstruction one wavefront per macroblock, picture by picture.  out (host, may be NULL): [max_pictures][S][W*H*3/2], picture t of
  * stream s at (t*S + s)*W*H*3/2; pictures[s] = number decoded.  Sub-8x8 partitions, ref_idx_l0 and
  * reference list modification are handled the way the reference handles them; syntax the
- * GPU path does not implement (I_PCM, CABAC, High profiles, field coding, slice groups) returns FERHIP_E_UNSUP. */
+ * GPU path does not implement (I_PCM, CABAC, High profiles, field coding, slice groups) returns FERHIP_E_UNSUP.
+ *
+ * Illegal and damaged streams (all three decode paths).  The rule is no silent divergence from the reference decoder: a
+ * stream it decodes gives its pictures, bit for bit, or a fault for that stream at that picture.  Meaning that no
+ * conformant encoder produces is decoded like the reference decodes it: an intra prediction mode that reads a neighbour
+ * which does not exist predicts from the reference's -1 "unavailable" samples, a motion vector may point anywhere (every
+ * sample coordinate is clamped to the picture).  Where the reference stops with one of its fatal errors (mb_type,
+ * intra_chroma_pred_mode, coded_block_pattern or mb_qp_delta out of range, TotalCoeff above 16), the picture is a fault:
+ * FERHIP_E_DEVICE.  One limit: with data left behind a skip run that ends a picture the reference parses one more
+ * macroblock, past the picture.  That macroblock is followed only through mb_type (above 31 is its fatal error) and, for
+ * an intra type, the prediction modes and intra_chroma_pred_mode (above 3); short of these the picture is complete and
+ * is delivered.  An inter type's fields, the coded_block_pattern, mb_qp_delta and residual of that macroblock, and
+ * whatever the reference parses after it, are not followed: a fatal error the reference meets there goes unreported.
+ * What the decoders refuse although the reference decodes on -- the complete list:
+ *   - I_PCM (mb_type 25 in an I slice, 30 in a P slice): FERHIP_E_UNSUP;
+ *   - any other mb_type above 25 in an I slice written with slice_type 7 (the reference tests slice_type == 2 only),
+ *     bits that no entry of a CAVLC table matches (the reference settles on the nearest lower code): FERHIP_E_DEVICE;
+ *   - a motion vector component outside [-32768, 32767] quarter samples (vectors are kept in 16 bits; a level allows
+ *     +-8192): FERHIP_E_DEVICE;
+ *   - a residual block whose coefficients do not fit it -- TotalCoeff or total_zeros too large for a 15-coefficient
+ *     block, a run_before above the zeros that are left -- which the reference stores into the neighbouring block of
+ *     its level array or outside it: FERHIP_E_DEVICE.
+ * Where the reference itself divides by zero or indexes outside its arrays (a sub_mb_type above 3, a level_prefix above
+ * 15, a level stored outside its level array, a macroblock type without partitions in motion prediction) there is
+ * nothing to follow; such a stream decodes or faults (a sub_mb_type above 3 and a level_prefix of more than 31 zeros
+ * always fault, FERHIP_E_DEVICE), and never disturbs another stream or a later call. */
 int ferhip_decode_streams(const uint8_t *const *streams, const size_t *lens, int nstreams, uint8_t *out,
                           int max_pictures, int *pictures, int *width, int *height);
 /* frees the window buffers ferhip_decode_streams keeps between calls (tens of GB of HBM for large batches) and the

@@ -170,7 +170,20 @@ typedef struct fo_ctx {
     struct fo_me_rec *me_rec;
     /* test hook: the largest |level| fo_encode_slice handed to the CAVLC writer in the last picture (fo_dbg_max_level) */
     int dbg_max_level;
+    /* decoder trace: intra_chroma_pred_mode of every intra macroblock of the last picture (fo_dbg_chroma_mode) */
+    int *chroma_pred_mode;
+    /* decoder: set where the reference itself would divide by zero or index past one of its tables (its behaviour is
+     * undefined there); fo_decode_stream_status then ends with FO_DEC_UNDEFINED instead of following it */
+    int undefined;
+    /* decoder trace: residual blocks so far with a level stored outside the block (TotalCoeff or total_zeros too large for
+     * it, a run_before above zerosLeft) */
+    int block_overrun;
+    /* decoder trace: FO_REFUSE_* of what the stream held so far that the device refuses although the reference decodes on */
+    int refusals;
 } fo_ctx;
+#define FO_REFUSE_I_MB_TYPE 1 /* mb_type above 24 in an I slice of slice_type 7 (the reference tests slice_type == 2 only) */
+#define FO_REFUSE_NO_CODE 2   /* bits no entry of a CAVLC table matches: the reference's binary search (cavlc_table_decode) settles on
+                               * the nearest lower code and decodes on; the oracle does not follow it and ends like a fatal error */
 
 /* What fo_interEncoding searched for one 8x8 partition (fo_dbg_me_record).  List 0 = stage 1 (17 entries around the
  * predictor), 1 = stage 2 (33 of the bucket walk), 2 = stage 3 (33, centre 0, wide pass then local pass).  Entries are
@@ -238,6 +251,13 @@ unsigned fo_cavlc_encode_block(fo_bw *w, const int *coef, int maxNumCoeff, int n
 typedef void (*fo_frame_cb)(fo_ctx *c, void *user);
 /* Annex-B stream in, calls cb after every decoded picture. Returns pictures decoded. */
 int fo_decode_stream(const uint8_t *stream, size_t n, fo_frame_cb cb, void *user, fo_ctx **ctx_out);
+/* The same, and how the decode ended in *status: FO_DEC_END the stream ran out (the reference exits 0), FO_DEC_FATAL at one
+ * of the reference's own "Fatal error" exits (the picture it was in is not delivered), FO_DEC_UNDEFINED where the
+ * reference's behaviour is undefined (a division by zero, an index past a table): the pictures in front were delivered. */
+#define FO_DEC_END 0
+#define FO_DEC_FATAL 1
+#define FO_DEC_UNDEFINED 2
+int fo_decode_stream_status(const uint8_t *stream, size_t n, fo_frame_cb cb, void *user, fo_ctx **ctx_out, int *status);
 int fo_decode_slice(fo_ctx *c, int nal_type, int nal_ref_idc, const uint8_t *rbsp, size_t n);
 
 /* ---- synthetic input (fo_gen.c) ---- */

@@ -359,7 +359,10 @@ static int parse_block(fo_ctx *c, fo_br *r, int *coef, int maxNumCoeff, int kind
     int nC = fo_cavlc_nC(c, kind, blk, iCbCr);
     int cls = (nC == -1) ? 4 : (nC <= 1 ? 0 : (nC <= 3 ? 1 : (nC < 8 ? 2 : 3)));
     int TotalCoeff, TrailingOnes;
-    if (!read_coeff_token(r, cls, &TotalCoeff, &TrailingOnes)) return 0;
+    if (!read_coeff_token(r, cls, &TotalCoeff, &TrailingOnes)) {
+        c->refusals |= FO_REFUSE_NO_CODE;
+        return 0;
+    }
     if (kind <= 2)
         c->tc_l[c->cur][kind == 0 ? 0 : blk] = TotalCoeff;
     else if (kind == 4)
@@ -374,7 +377,11 @@ static int parse_block(fo_ctx *c, fo_br *r, int *coef, int maxNumCoeff, int kind
             int level_prefix = 0;
             while (fo_br_bit(r) == 0) {
                 level_prefix++;
-                if (level_prefix > 32) return 0;
+                if (level_prefix > 32) break;
+            }
+            if (level_prefix > 15) { /* inputstream_to_levelcode[16][7][4096] is indexed by level_prefix: past the table */
+                c->undefined = 1;
+                return 0;
             }
             int size;
             if (level_prefix == 14 && suffixLength == 0)
@@ -411,7 +418,10 @@ static int parse_block(fo_ctx *c, fo_br *r, int *coef, int maxNumCoeff, int kind
                 found = 1;
             }
         }
-        if (!found) return 0;
+        if (!found) {
+            c->refusals |= FO_REFUSE_NO_CODE;
+            return 0;
+        }
     }
     for (int j = 0; j < TotalCoeff - 1; j++) {
         if (zerosLeft > 0) {
@@ -421,7 +431,10 @@ static int parse_block(fo_ctx *c, fo_br *r, int *coef, int maxNumCoeff, int kind
                 if (rb == 7)
                     while (fo_br_bit(r) == 0) {
                         rb++;
-                        if (rb > 64) return 0;
+                        if (rb > 64) { /* (the reference reads on for its 1 bit: not followed) */
+                            c->undefined = 1;
+                            return 0;
+                        }
                     }
             } else {
                 int found = 0;
@@ -432,7 +445,10 @@ static int parse_block(fo_ctx *c, fo_br *r, int *coef, int maxNumCoeff, int kind
                         found = 1;
                     }
                 }
-                if (!found) return 0;
+                if (!found) {
+                    c->refusals |= FO_REFUSE_NO_CODE;
+                    return 0;
+                }
             }
             run[j] = rb;
         } else {
@@ -441,12 +457,23 @@ static int parse_block(fo_ctx *c, fo_br *r, int *coef, int maxNumCoeff, int kind
         zerosLeft -= run[j];
     }
     run[TotalCoeff - 1] = zerosLeft;
-    int coeffNum = -1;
+    /* QUIRK: a run_before above zerosLeft (only the escape of zerosLeft > 6 can code one) makes zerosLeft negative and
+     * coeffNum run backwards, and the reference stores coeffLevel[coeffNum] unchecked (F/residual.cpp:1380-1385).  Inside
+     * the array the block is a row of -- level[16][16], i16x16AClevel[16][16], ChromaDCLevel[2][4], ChromaACLevel[2][4][16],
+     * laid out like fo_levels' -- the level lands in a neighbouring block, which is kept; outside it, in other memory. */
+    int row = kind == 0 ? 0 : (kind == 3 ? iCbCr : (kind == 4 ? iCbCr * 4 + blk : blk));
+    int width = kind == 3 ? 4 : 16, rows = kind == 0 ? 1 : (kind == 3 ? 2 : (kind == 4 ? 8 : 16));
+    int coeffNum = -1, outside = 0;
     for (int i = TotalCoeff - 1; i >= 0; i--) {
         coeffNum += run[i] + 1;
-        if (coeffNum >= 0 && coeffNum < 16) coef[coeffNum] = level[i];
+        if (coeffNum < 0 || coeffNum >= maxNumCoeff) outside = 1;
+        if (row * width + coeffNum >= 0 && row * width + coeffNum < rows * width)
+            coef[coeffNum] = level[i];
+        else
+            c->undefined = 1;
     }
-    return 1;
+    c->block_overrun += outside;
+    return !c->undefined;
 }
 
 /* residual(0,15): F/residual.cpp:959-1067 */

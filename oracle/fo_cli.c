@@ -89,14 +89,33 @@ int main(int argc, char **argv)
         fclose(f);
         y4m_out o = {fopen(argv[3], "wb"), 1};
         double t0 = now();
-        int n = fo_decode_stream(s, (size_t)sz, y4m_cb, &o, NULL);
+        int how = 0;
+        int n = fo_decode_stream_status(s, (size_t)sz, y4m_cb, &o, NULL, &how);
         double t1 = now();
         fclose(o.f);
-        printf("{\"pictures\": %d, \"seconds\": %.6f}\n", n, t1 - t0);
+        free(s);
+        printf("{\"pictures\": %d, \"seconds\": %.6f, \"status\": %d}\n", n, t1 - t0, how);
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[1], "decn")) { /* decode every stream listed, one result line each, no pictures kept */
+        for (int k = 2; k < argc; k++) {
+            FILE *f = fopen(argv[k], "rb");
+            if (!f) return 1;
+            fseek(f, 0, SEEK_END);
+            long sz = ftell(f);
+            fseek(f, 0, SEEK_SET);
+            uint8_t *s = malloc((size_t)sz + 1);
+            if (fread(s, 1, (size_t)sz, f) != (size_t)sz) return 1;
+            fclose(f);
+            int how = 0;
+            int n = fo_decode_stream_status(s, (size_t)sz, NULL, NULL, NULL, &how);
+            free(s);
+            printf("{\"pictures\": %d, \"status\": %d}\n", n, how);
+        }
         return 0;
     }
     fprintf(stderr,
             "usage: fo_cli gen W H n seed noise out.yuv | enc W H n qp window maxdiff intraEvery basic in.yuv out.264 "
-            "[recon.yuv] | dec in.264 out.y4m\n");
+            "[recon.yuv] | dec in.264 out.y4m | decn in.264 ...\n");
     return 2;
 }

@@ -25,6 +25,12 @@ int *fo_dbg_koliko(fo_ctx *c) { return c->koliko; }
 int *fo_dbg_mb_type(fo_ctx *c) { return c->mb_type; }
 int *fo_dbg_cbp(fo_ctx *c, int chroma) { return chroma ? c->cbp_c : c->cbp_l; }
 int *fo_dbg_mv(fo_ctx *c, int y) { return y ? &c->dbg_mvy[0][0][0] : &c->dbg_mvx[0][0][0]; }
+/* the decoder's (and encoder's) live vector field mvx / mvy [nmb][4][4]; entries of macroblocks that are not inter are stale */
+int *fo_dbg_dec_mv(fo_ctx *c, int y) { return y ? &c->mvy[0][0][0] : &c->mvx[0][0][0]; }
+int *fo_dbg_chroma_mode(fo_ctx *c) { return c->chroma_pred_mode; }
+int fo_dbg_block_overrun(fo_ctx *c) { return c->block_overrun; } /* blocks so far whose coefficients did not fit them */
+int fo_dbg_refusals(fo_ctx *c) { return c->refusals; }           /* FO_REFUSE_* met so far */
+int fo_dbg_slice_type(fo_ctx *c) { return c->slice_type; } /* of the last slice: 0 = P, 2 = I */
 int *fo_dbg_tc_l(fo_ctx *c) { return &c->tc_l[0][0]; }
 int *fo_dbg_tc_c(fo_ctx *c) { return &c->tc_c[0][0][0]; }
 int *fo_dbg_i4mode(fo_ctx *c) { return c->i4mode; }

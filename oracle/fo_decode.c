@@ -161,16 +161,37 @@ static int decode_slice(fo_ctx *c, dec_hdr *h, int nal_type, int nal_ref_idc, co
                 c->cur++;
             }
             if (c->cur != 0 || run > 0) more = fo_br_more(r);
+            if (more && c->cur >= MbCount) {
+                /* QUIRK: F/rbsp_decoding.cpp:121 tests moreDataFlag alone, so with data left behind a skip run that ends
+                 * the picture the reference parses a macroblock past the picture.  It is followed as far as it only reads
+                 * the stream -- mb_type and, for an intra type, the prediction modes, with the fatal errors the reference has
+                 * there -- and not into what it then decodes into the memory behind its pictures: the picture is complete. */
+                int t = (int)fo_br_ue(r);
+                if (t > 31) return -1;
+                int pc = fo_pred_class(c, t);
+                if (pc == 0 || pc == 1) {
+                    if (pc == 0)
+                        for (int b = 0; b < 16; b++)
+                            if (!fo_br_bit(r)) fo_br_bits(r, 3);
+                    if (fo_br_ue(r) > 3) return -1;
+                }
+                more = 0;
+            }
         }
         if (more && c->cur < MbCount) {
             int t = (int)fo_br_ue(r);
             c->cur_mb_type = t;
             c->mb_type[c->cur] = t;
-            if (t > 31 || (s5 == 2 && t > 24)) return -1;
+            if (t > 31 || (st == 2 && t > 24)) return -1; /* QUIRK: slice_type itself, not % 5 (F/rbsp_decoding.cpp:128) */
+            if (s5 == 2 && t > 24) c->refusals |= FO_REFUSE_I_MB_TYPE;
             int pc = fo_pred_class(c, t);
             int np = (s5 == 2) ? 0 : p_num_part(t);
             if (pc == 2 && np == 4) {
-                for (int i = 0; i < 4; i++) c->sub_mb_type[i] = (int)fo_br_ue(r);
+                for (int i = 0; i < 4; i++) {
+                    c->sub_mb_type[i] = (int)fo_br_ue(r);
+                    if (c->sub_mb_type[i] > 3) c->undefined = 1; /* NumSubMbPart indexes past P_sub_macroblock_modes[5][6] */
+                }
+                if (c->undefined) return -2;
                 for (int i = 0; i < 4; i++)
                     if (c->num_ref_idx_override > 0 && t != FO_P_8x8ref0) c->ref_idx_l0[c->cur][i] = (int)fo_br_te(r);
                 for (int i = 0; i < 4; i++)
@@ -186,6 +207,7 @@ static int decode_slice(fo_ctx *c, dec_hdr *h, int nal_type, int nal_ref_idc, co
                     }
                 c->chroma_mode = (int)fo_br_ue(r);
                 if (c->chroma_mode > 3) return -1;
+                c->chroma_pred_mode[c->cur] = c->chroma_mode;
             } else {
                 if (np == 0xff) np = 0;
                 for (int i = 0; i < np; i++)
@@ -211,7 +233,7 @@ static int decode_slice(fo_ctx *c, dec_hdr *h, int nal_type, int nal_ref_idc, co
             if (c->cbpL > 0 || c->cbpC > 0 || pc == 1) {
                 c->mb_qp_delta = fo_br_se(r);
                 if (c->mb_qp_delta < -26 || c->mb_qp_delta > 25) return -1;
-                if (!fo_residual_parse(c, r)) return -1;
+                if (!fo_residual_parse(c, r)) return c->undefined ? -2 : -1;
             } else {
                 clear_residual(c);
             }
@@ -220,6 +242,7 @@ static int decode_slice(fo_ctx *c, dec_hdr *h, int nal_type, int nal_ref_idc, co
                 fo_intraPrediction_dec(c, predL, predCr, predCb);
             } else {
                 fo_DeriveMVs(c);
+                if (c->undefined) return -2;
                 fo_Decode(c, predL, predCr, predCb);
             }
             if (pc == 1)
@@ -245,6 +268,12 @@ static int decode_slice(fo_ctx *c, dec_hdr *h, int nal_type, int nal_ref_idc, co
 /* findNALstart / findNALend / parseNAL, F/nal.cpp:68-223 (4-byte start codes only) */
 int fo_decode_stream(const uint8_t *s, size_t n, fo_frame_cb cb, void *user, fo_ctx **ctx_out)
 {
+    return fo_decode_stream_status(s, n, cb, user, ctx_out, NULL);
+}
+
+int fo_decode_stream_status(const uint8_t *s, size_t n, fo_frame_cb cb, void *user, fo_ctx **ctx_out, int *status)
+{
+    int how = FO_DEC_END;
     dec_hdr h;
     memset(&h, 0, sizeof h);
     fo_ctx *c = NULL;
@@ -287,12 +316,17 @@ int fo_decode_stream(const uint8_t *s, size_t n, fo_frame_cb cb, void *user, fo_
         } else if (type == FO_NAL_PPS) {
             parse_pps(&h, &r);
         } else if ((type == FO_NAL_IDR || type == FO_NAL_SLICE) && c) {
-            if (decode_slice(c, &h, type, ref_idc, rbsp, m) < 0) break;
+            int e = decode_slice(c, &h, type, ref_idc, rbsp, m);
+            if (e < 0) {
+                how = e == -2 ? FO_DEC_UNDEFINED : FO_DEC_FATAL;
+                break;
+            }
             pictures++;
             if (cb) cb(c, user);
         }
     }
     free(rbsp);
+    if (status) *status = how;
     if (ctx_out)
         *ctx_out = c;
     else

@@ -41,6 +41,7 @@ fo_ctx *fo_create(int W, int H)
     c->dbg_mvx = calloc((size_t)c->nmb, sizeof *c->dbg_mvx);
     c->dbg_mbsize = calloc((size_t)c->nmb, sizeof *c->dbg_mbsize);
     c->dbg_mvy = calloc((size_t)c->nmb, sizeof *c->dbg_mvy);
+    c->chroma_pred_mode = (int *)calloc((size_t)c->nmb, sizeof(int));
     /* defaults of F/h264_globals.cpp:217,301-306 and the GUI */
     c->qp = 12;
     c->basic = 0;
@@ -74,6 +75,7 @@ void fo_destroy(fo_ctx *c)
     free(c->dbg_mvx);
     free(c->dbg_mbsize);
     free(c->dbg_mvy);
+    free(c->chroma_pred_mode);
     free(c->me_rec);
     for (int i = 0; i < 16; i++) {
         free(c->interp[i]);

@@ -103,6 +103,11 @@ static void nbr_parts(const fo_ctx *c, int mbPartIdx, int subIdx, nbrs *n)
 {
     int t = c->cur_mb_type;
     int pw = part_w(t), ph = part_h(t);
+    if (pw <= 0 || pw > 16) { /* a macroblock type without partitions (F/mode_pred.cpp:117 divides 16 / 255, then by that 0) */
+        ((fo_ctx *)c)->undefined = 1;
+        for (int k = 0; k < 4; k++) n->mb[k] = n->part[k] = n->valid[k] = 0;
+        return;
+    }
     int x = (mbPartIdx % (16 / pw)) * pw, y = (mbPartIdx / (16 / pw)) * ph;
     int xS = 0, yS = 0, ppw = 16;
     if (t == FO_P_8x8 || t == FO_P_8x8ref0) {

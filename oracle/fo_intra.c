@@ -49,18 +49,18 @@ void fo_intra4x4_pred(int mode, const int p[14], int pred[4][4])
                 if (x == 3 && y == 3)
                     pred[y][x] = (P4(6, -1) + 3 * P4(7, -1) + 2) >> 2;
                 else
-                    pred[y][x] = (P4(x + y, -1) + (P4(x + y + 1, -1) << 1) + P4(x + y + 2, -1) + 2) >> 2;
+                    pred[y][x] = (P4(x + y, -1) + (P4(x + y + 1, -1) * 2) + P4(x + y + 2, -1) + 2) >> 2;
             }
         break;
     case 4:
         for (y = 0; y < 4; y++)
             for (x = 0; x < 4; x++) {
                 if (x > y)
-                    pred[y][x] = (P4(x - y - 2, -1) + (P4(x - y - 1, -1) << 1) + P4(x - y, -1) + 2) >> 2;
+                    pred[y][x] = (P4(x - y - 2, -1) + (P4(x - y - 1, -1) * 2) + P4(x - y, -1) + 2) >> 2;
                 else if (x < y)
-                    pred[y][x] = (P4(-1, y - x - 2) + (P4(-1, y - x - 1) << 1) + P4(-1, y - x) + 2) >> 2;
+                    pred[y][x] = (P4(-1, y - x - 2) + (P4(-1, y - x - 1) * 2) + P4(-1, y - x) + 2) >> 2;
                 else
-                    pred[y][x] = (P4(0, -1) + (P4(-1, -1) << 1) + P4(-1, 0) + 2) >> 2;
+                    pred[y][x] = (P4(0, -1) + (P4(-1, -1) * 2) + P4(-1, 0) + 2) >> 2;
             }
         break;
     case 5:
@@ -71,11 +71,11 @@ void fo_intra4x4_pred(int mode, const int p[14], int pred[4][4])
                     pred[y][x] = (P4(x - (y >> 1) - 1, -1) + P4(x - (y >> 1), -1) + 1) >> 1;
                 else if (z == 1 || z == 3 || z == 5)
                     pred[y][x] =
-                        (P4(x - (y >> 1) - 2, -1) + (P4(x - (y >> 1) - 1, -1) << 1) + P4(x - (y >> 1), -1) + 2) >> 2;
+                        (P4(x - (y >> 1) - 2, -1) + (P4(x - (y >> 1) - 1, -1) * 2) + P4(x - (y >> 1), -1) + 2) >> 2;
                 else if (z == -1)
-                    pred[y][x] = (P4(-1, 0) + (P4(-1, -1) << 1) + P4(0, -1) + 2) >> 2;
+                    pred[y][x] = (P4(-1, 0) + (P4(-1, -1) * 2) + P4(0, -1) + 2) >> 2;
                 else
-                    pred[y][x] = (P4(-1, y - 1) + (P4(-1, y - 2) << 1) + P4(-1, y - 3) + 2) >> 2;
+                    pred[y][x] = (P4(-1, y - 1) + (P4(-1, y - 2) * 2) + P4(-1, y - 3) + 2) >> 2;
             }
         break;
     case 6:
@@ -86,11 +86,11 @@ void fo_intra4x4_pred(int mode, const int p[14], int pred[4][4])
                     pred[y][x] = (P4(-1, y - (x >> 1) - 1) + P4(-1, y - (x >> 1)) + 1) >> 1;
                 else if (z == 1 || z == 3 || z == 5)
                     pred[y][x] =
-                        (P4(-1, y - (x >> 1) - 2) + (P4(-1, y - (x >> 1) - 1) << 1) + P4(-1, y - (x >> 1)) + 2) >> 2;
+                        (P4(-1, y - (x >> 1) - 2) + (P4(-1, y - (x >> 1) - 1) * 2) + P4(-1, y - (x >> 1)) + 2) >> 2;
                 else if (z == -1)
-                    pred[y][x] = (P4(-1, 0) + (P4(-1, -1) << 1) + P4(0, -1) + 2) >> 2;
+                    pred[y][x] = (P4(-1, 0) + (P4(-1, -1) * 2) + P4(0, -1) + 2) >> 2;
                 else
-                    pred[y][x] = (P4(x - 1, -1) + (P4(x - 2, -1) << 1) + P4(x - 3, -1) + 2) >> 2;
+                    pred[y][x] = (P4(x - 1, -1) + (P4(x - 2, -1) * 2) + P4(x - 3, -1) + 2) >> 2;
             }
         break;
     case 7:
@@ -100,7 +100,7 @@ void fo_intra4x4_pred(int mode, const int p[14], int pred[4][4])
                     pred[y][x] = (P4(x + (y >> 1), -1) + P4(x + (y >> 1) + 1, -1) + 1) >> 1;
                 else
                     pred[y][x] =
-                        (P4(x + (y >> 1), -1) + (P4(x + (y >> 1) + 1, -1) << 1) + P4(x + (y >> 1) + 2, -1) + 2) >> 2;
+                        (P4(x + (y >> 1), -1) + (P4(x + (y >> 1) + 1, -1) * 2) + P4(x + (y >> 1) + 2, -1) + 2) >> 2;
             }
         break;
     case 8:
@@ -111,7 +111,7 @@ void fo_intra4x4_pred(int mode, const int p[14], int pred[4][4])
                     pred[y][x] = (P4(-1, y + (x >> 1)) + P4(-1, y + (x >> 1) + 1) + 1) >> 1;
                 else if (z == 1 || z == 3)
                     pred[y][x] =
-                        (P4(-1, y + (x >> 1)) + (P4(-1, y + (x >> 1) + 1) << 1) + P4(-1, y + (x >> 1) + 2) + 2) >> 2;
+                        (P4(-1, y + (x >> 1)) + (P4(-1, y + (x >> 1) + 1) * 2) + P4(-1, y + (x >> 1) + 2) + 2) >> 2;
                 else if (z == 5)
                     pred[y][x] = (P4(-1, 2) + 3 * P4(-1, 3) + 2) >> 2;
                 else
@@ -183,7 +183,7 @@ void fo_intra16_pred(int mode, const int p[33], int pred[16][16])
             Hh += (i + 1) * (P16(8 + i, -1) - P16(6 - i, -1));
             V += (i + 1) * (P16(-1, 8 + i) - P16(-1, 6 - i));
         }
-        int a = (P16(-1, 15) + P16(15, -1)) << 4;
+        int a = (P16(-1, 15) + P16(15, -1)) * 16; /* (a product, not a shift: the samples may be the -1 marker) */
         int b = (5 * Hh + 32) >> 6;
         int cc = (5 * V + 32) >> 6;
         for (y = 0; y < 16; y++)
@@ -256,7 +256,7 @@ static void chroma_pred(int mode, const int p[17], int pred[8][8])
         int Hh = 0, V = 0;
         for (int i = 0; i <= 3; i++) Hh += (i + 1) * (PC(4 + i, -1) - PC(2 - i, -1));
         for (int i = 0; i <= 3; i++) V += (i + 1) * (PC(-1, 4 + i) - PC(-1, 2 - i));
-        int a = (PC(-1, 7) + PC(7, -1)) << 4;
+        int a = (PC(-1, 7) + PC(7, -1)) * 16;
         int b = (34 * Hh + 32) >> 6;
         int cc = (34 * V + 32) >> 6;
         for (y = 0; y < 8; y++)

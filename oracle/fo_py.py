@@ -35,7 +35,13 @@ def lib():
         L.fo_fill_interpolated.argtypes = [vp]
         L.fo_gen_frame.argtypes = [i, i, i, C.c_uint64, i, vp, vp, vp]
         L.fo_decode_stream.argtypes = [vp, sz, vp, vp, vp]
-        for n in ("fo_dbg_plane", "fo_dbg_interp", "fo_dbg_sorted", "fo_dbg_mv", "fo_dbg_cbp"):
+        L.fo_decode_stream_status.argtypes = [vp, sz, vp, vp, vp, vp]
+        L.fo_dbg_chroma_mode.restype = vp
+        L.fo_dbg_chroma_mode.argtypes = [vp]
+        L.fo_dbg_slice_type.argtypes = [vp]
+        L.fo_dbg_block_overrun.argtypes = [vp]
+        L.fo_dbg_refusals.argtypes = [vp]
+        for n in ("fo_dbg_plane", "fo_dbg_interp", "fo_dbg_sorted", "fo_dbg_mv", "fo_dbg_dec_mv", "fo_dbg_cbp"):
             getattr(L, n).restype = vp
             getattr(L, n).argtypes = [vp, i]
         L.fo_dbg_kar.restype = vp
@@ -311,6 +317,48 @@ def decode_stream_trace(stream):
     a = np.frombuffer(stream, np.uint8)
     n = L.fo_decode_stream(a.ctypes.data, a.size, CB(cb), None, None)
     return n, frames, types
+
+
+DEC_END, DEC_FATAL, DEC_UNDEFINED = 0, 1, 2  # FO_DEC_*: how fo_decode_stream_status ended
+REFUSE_I_MB_TYPE, REFUSE_NO_CODE = 1, 2  # FO_REFUSE_*
+
+
+def decode_stream_verdict(stream):
+    """Decode an Annex-B stream and say how the decode ended -> dict: status (DEC_END the stream ran out, DEC_FATAL one of
+    the reference's own fatal errors, DEC_UNDEFINED a point where the reference's behaviour is undefined), frames (the
+    I420 pictures delivered in front of that point), and the trace of every picture as it stood when it was delivered:
+    slice_type (0 P, 2 I), mb_type [nmb], i4mode [nmb][16], chroma_mode [nmb], mv [nmb][4][2] (x, y of the four 8x8
+    quadrants; stale where the macroblock is not inter), block_overrun (residual blocks of the stream so far whose
+    coefficients did not fit them: TotalCoeff or total_zeros too large for the block, a run_before above zerosLeft),
+    refusals (the FO_REFUSE_* bits of fo.h met so far); end_refusals: those bits when the decode ended, which may be in a
+    picture that was not delivered."""
+    L = lib()
+    out = dict(frames=[], slice_type=[], block_overrun=[], refusals=[], mb_type=[], i4mode=[], chroma_mode=[], mv=[])
+    CB = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)
+
+    def cb(cptr, user):
+        W, H = (int(v) for v in _arr(cptr, 2, np.int32))
+        ys, nmb = W * H, (W // 16) * (H // 16)
+        c = C.c_void_p(cptr)
+        out["frames"].append(np.concatenate([_arr(L.fo_dbg_plane(c, k), ys if k == 0 else ys // 4, np.uint8).copy() for k in range(3)]))
+        out["slice_type"].append(int(L.fo_dbg_slice_type(c)))
+        out["block_overrun"].append(int(L.fo_dbg_block_overrun(c)))
+        out["refusals"].append(int(L.fo_dbg_refusals(c)))
+        out["mb_type"].append(_arr(L.fo_dbg_mb_type(c), nmb, np.int32).copy())
+        out["i4mode"].append(_arr(L.fo_dbg_i4mode(c), nmb * 16, np.int32).reshape(nmb, 16).copy())
+        out["chroma_mode"].append(_arr(L.fo_dbg_chroma_mode(c), nmb, np.int32).copy())
+        out["mv"].append(np.stack([_arr(L.fo_dbg_dec_mv(c, k), nmb * 16, np.int32).reshape(nmb, 4, 4)[:, :, 0] for k in range(2)], -1).copy())
+
+    a = np.frombuffer(stream, np.uint8)
+    status = C.c_int(-1)
+    ctx = C.c_void_p()
+    n = L.fo_decode_stream_status(a.ctypes.data, a.size, CB(cb), None, C.byref(ctx), C.byref(status))
+    assert n == len(out["frames"])
+    out["status"] = status.value
+    out["end_refusals"] = int(L.fo_dbg_refusals(ctx)) if ctx else 0
+    if ctx:
+        L.fo_destroy(ctx)
+    return out
 
 
 def block_op(name, blocks, qp=0, flag=None):

@@ -3,7 +3,7 @@
 Test infrastructure (plain Python + numpy, seeded, no GPU).  make_stream() writes SPS, PPS, IDR I slices and P slices
 of any size in macroblocks: every macroblock type the decoder supports (I4x4 with all prev / rem combinations, the 24
 I16x16 types, P_Skip runs, the five P types with all four sub types, types 5..29 = intra in P), intra modes that only
-use neighbours that exist (the reference's decoder does not check), slice_qp_delta / mb_qp_delta over the whole QP
+use neighbours that exist (the reference's decoder does not check; ILLEGAL_PLANS draw the others too), slice_qp_delta / mb_qp_delta over the whole QP
 range, and the parameter-set fields dec_parse_sps / dec_parse_pps accept at other values than the encoder's.  The
 header pieces (Bits, nal_unit, te_bits, the P slice header) are those of pslice_synth.py.
 
@@ -362,12 +362,19 @@ class Synth:
         rng = self.rng
         mbx, mby = mb % self.mbw, mb // self.mbw
         left, top = mbx > 0, mby > 0
-        chroma = int(rng.choice([0] + ([1] if left else []) + ([2] if top else []) + ([3] if left and top else [])))
+        any_mode = p.get("any_mode", False)  # modes drawn without regard to the neighbours they need (ILLEGAL_PLANS)
+        if any_mode:
+            chroma = int(rng.integers(0, 4))
+        else:
+            chroma = int(rng.choice([0] + ([1] if left else []) + ([2] if top else []) + ([3] if left and top else [])))
         self.cov["chroma_modes"].add(chroma)
         base = 5 if slice_type == "P" else 0
         self.kind[mb] = kind
         if kind == "i16":
-            mode = int(rng.choice([2] + ([1] if left else []) + ([0] if top else []) + ([3] if left and top else [])))
+            if any_mode:
+                mode = int(rng.integers(0, 4))
+            else:
+                mode = int(rng.choice([2] + ([1] if left else []) + ([0] if top else []) + ([3] if left and top else [])))
             cbpC = 2 if p.get("nonzero") else int(rng.integers(0, 3))
             cbpL = 15 if p.get("nonzero") or rng.random() < 0.5 else 0
             t = base + 1 + mode + 4 * cbpC + (12 if cbpL else 0)
@@ -388,7 +395,7 @@ class Synth:
                     mB = self.modes[mb][BLK_AT[(x0, y0 - 4)]] if y0 else (
                         self.modes[mb - self.mbw][BLK_AT[(x0, 12)]] if self.kind[mb - self.mbw] == "i4" else 2)
                     pm = min(mA, mB)
-                legal = [2] + ([0, 3, 7] if okB else []) + ([1, 8] if okA else []) + ([4, 5, 6] if okA and okB else [])
+                legal = list(range(9)) if any_mode else [2] + ([0, 3, 7] if okB else []) + ([1, 8] if okA else []) + ([4, 5, 6] if okA and okB else [])
                 assert pm in legal
                 m = pm if rng.random() < 0.3 else int(rng.choice(legal))
                 if m == pm:
@@ -549,7 +556,8 @@ def make_stream(seed, cfg, pictures):
     qp (SliceQPy), levels (the level modes its macroblocks draw from), p_i16, p_intra, p_skip, p_cbp0, delta_range, p_delta,
     qp_targets (QPy of the coded macroblocks, in order), nonzero (every macroblock codes luma, chroma DC and chroma AC),
     head (kinds of the first macroblocks: "skip" / "cbp0"), tail_chroma_ac (mb_qp_delta of a last macroblock with chroma
-    AC), steer_pairs, deblocking (idc, alpha, beta), bad_mb (index of an I_PCM macroblock) and the P header options of
+    AC), steer_pairs, deblocking (idc, alpha, beta), bad_mb (index of an I_PCM macroblock), any_mode (Intra4x4, Intra16x16
+    and chroma prediction modes drawn from all of them, whether or not the neighbours they read exist) and the P header options of
     pslice_synth (override, active, modification, mvd_range, early_end).
     -> (Annex-B bytes, coverage report, [mb_type of every macroblock written, per picture])"""
     s = Synth(seed, cfg)
@@ -635,6 +643,30 @@ def plan_streams(name):
     """-> [(stream, coverage, mb_types)] * 2: the two different streams the plan's batch is made of"""
     cfg, pictures, short, _ = PLANS[name]
     return [make_stream(SEEDS[0], cfg, pictures), make_stream(SEEDS[1], cfg, pictures[:short] if short else pictures)]
+
+
+# Legal syntax, illegal meaning: streams no conformant encoder writes but whose every field parses.  The reference
+# decodes them all (it predicts from its -1 "unavailable" markers and keeps vectors of any size), so the decode twin
+# is held to its pictures here too.  Kept apart from PLANS: those streams, their bytes and their recorded md5s stay.
+#   any_mode   Intra4x4, Intra16x16 and chroma prediction modes drawn without regard to which neighbours exist
+#   mvd_*      vector differences far past what a level allows; mvd_40000 leaves 16 bits, the others stay inside
+_ANY = [_i(qp=22, levels=_SM, any_mode=True), _p(qp=20, levels=_SM, p_intra=0.5, any_mode=True),
+        _p(qp=18, levels=_SM, p_intra=0.5, p_skip=0.05, any_mode=True), _i(qp=24, levels=_SM, any_mode=True)]
+# name -> (cfg, pictures, seeds: one stream each)
+ILLEGAL_PLANS = {
+    **{f"any_mode_{w}x{h}": (dict(mbw=w, mbh=h), _ANY, (1, 2, 3)) for w, h in ((1, 1), (2, 1), (1, 2), (3, 2), (5, 4))},
+    "any_mode_constrained_5x4": (dict(mbw=5, mbh=4, constrained_intra_pred=1), _ANY, (1, 2)),
+    **{f"mvd_{r}": (dict(mbw=5, mbh=4), [_i(qp=22, levels=_SM)] + [_p(qp=22, levels=_SM, mvd_range=r, p_skip=0.1)] * 3, (1, 2))
+       for r in (300, 3000, 40000)},
+}
+VECTORS_INSIDE_INT16 = ("mvd_300", "mvd_3000")
+VECTORS_PAST_INT16 = ("mvd_40000",)
+
+
+def illegal_streams(name):
+    """-> [(stream, coverage, mb_types)]: one stream per seed of the plan"""
+    cfg, pictures, seeds = ILLEGAL_PLANS[name]
+    return [make_stream(seed, cfg, pictures) for seed in seeds]
 
 
 def unsupported_stream(slice_type, seed=5):

@@ -406,28 +406,35 @@ def test_gpu_decoder_1080p(pkg, fo):
 
 
 def test_gpu_decoder_survives_damaged_slice_data(pkg, fo):
-    """Bytes of the slice data overwritten at random: the parse either reaches the end of the picture or reports a syntax /
-    unsupported error through the return code -- it never hangs or leaves the library unusable (every loop of k_dec_parse is
-    bounded by the picture or the block, every table index by construction) -- and the undamaged stream still decodes bit-exactly
-    right after."""
+    """Bytes of the slice data overwritten (the first 24 streams of tests/damage_corpus.py: this golden, 1..5 bytes set to
+    2..255, so no start code is minted): the parse either reaches the end of the stream or reports a syntax / unsupported
+    error through the return code -- it never hangs or leaves the library unusable (every loop of k_dec_parse is bounded by
+    the picture or the block, every table index by construction) -- and the undamaged stream still decodes bit-exactly
+    right after.  Both outcomes occur; a stream the reference decodes (tests/golden/illegal_decode_record.json) gives the
+    oracle's pictures, one it stops at with a fatal error fails here too, with the device or the unsupported code."""
+    import illegal_cases as ic
     clean = (GOLD / "qcif_ippp_4f_qp12_w16.264").read_bytes()
     ref = _oracle_decode(fo, clean)
-    rng = np.random.default_rng(5)
     outcomes = {"ok": 0, "error": 0}
-    for trial in range(24):
-        bad = bytearray(clean)
-        lo = 64 + int(rng.integers(0, len(bad) - 200))  # behind the parameter sets and the first slice header
-        for k in range(int(rng.integers(1, 6))):
-            bad[min(lo + int(rng.integers(0, 64)), len(bad) - 1)] = int(rng.integers(1, 256))  # (no new start codes: never 0)
+    for i, name, golden, bad, entry in ic.tier2()[:24]:
+        assert golden == "qcif_ippp_4f_qp12_w16" and "/bytes" in name
+        v = ic.verdict(fo, i, bad)
+        x = ic.expectation(entry, v, i in ic.OPEN)
         try:
-            out, pics, w, h = pkg.decode_streams([bytes(bad), clean], ref.shape[0])
+            out, pics, w, h = pkg.decode_streams([bad, clean], ref.shape[0])
             outcomes["ok"] += 1
-            assert np.array_equal(out[:, 1], ref)  # the damaged neighbour does not disturb the other stream of the batch
-        except pkg.FerHipError:
+            assert pics[1] == ref.shape[0] and np.array_equal(out[:ref.shape[0], 1], ref)  # the damaged neighbour does not disturb the other stream of the batch
+            assert x["kind"] in ("complete", "undefined"), f"corpus {i}: decoded, but the reference stops ({x})"
+            if x["kind"] == "complete":
+                assert pics[0] == x["good"] and all(np.array_equal(out[t, 0], v["frames"][t]) for t in range(x["good"])), f"corpus {i}"
+        except pkg.FerHipError as err:
             outcomes["error"] += 1
+            assert "code -5" in str(err) or "code -4" in str(err), f"corpus {i}: {err}"  # FERHIP_E_DEVICE, FERHIP_E_UNSUP
+            assert x["kind"] != "complete", f"corpus {i}: {err} on a stream the reference decodes"
     out, pics, w, h = pkg.decode_streams([clean], ref.shape[0])
     assert pics == [ref.shape[0]] and np.array_equal(out[:, 0], ref)
     assert outcomes["ok"] + outcomes["error"] == 24
+    assert outcomes["ok"] >= 1 and outcomes["error"] >= 1, outcomes
 
 
 @pytest.mark.parametrize("W,H,S", [(3840, 64, 3), (6400, 32, 2), (12800, 16, 1)])
