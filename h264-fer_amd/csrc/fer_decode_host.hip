@@ -766,8 +766,27 @@ static int dec_session_window(DecSession &ss, const std::vector<std::vector<cons
             else
                 fer_launch_pic_emit_slots(d, set, map, iso->nmap[t], to, iso->fmt, py, pc, slot, iso->win, c->st);
         } else if (!iso && out) {
-            int rc = ferhip_get_recon(c, out + (t0 + t) * S * ss.fsz, 1);
-            if (rc) return rc;
+            uint8_t *row = out + (t0 + t) * S * ss.fsz;
+            bool all = true;
+            for (int s = 0; s < S; s++) all &= ss.pres[t * S + s] != 0;
+            if (all) {
+                int rc = ferhip_get_recon(c, row, 1);
+                if (rc) return rc;
+            } else {
+                // a stream that has ended has no picture at this step: its slot of `out` keeps what the caller put there
+                const uint8_t *set = c->planes[c->cur_set ^ 1];
+                for (int s = 0; s < S; s++) {
+                    if (!ss.pres[t * S + s]) continue;
+                    const size_t off[3] = {(size_t)s * d.ysz, (size_t)S * d.ysz + (size_t)s * d.csz,
+                                           (size_t)S * (d.ysz + d.csz) + (size_t)s * d.csz};
+                    uint8_t *f = row + (size_t)s * ss.fsz;
+                    if (hipMemcpyAsync(f, set + off[0], d.ysz, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
+                        hipMemcpyAsync(f + d.ysz, set + off[1], d.csz, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
+                        hipMemcpyAsync(f + d.ysz + d.csz, set + off[2], d.csz, hipMemcpyDeviceToHost, c->st) != hipSuccess)
+                        return FERHIP_E_HIP;
+                }
+                if (hipStreamSynchronize(c->st) != hipSuccess) return FERHIP_E_HIP;
+            }
         }
         for (int s = 0; s < S; s++) {
             if (!ss.pres[t * S + s]) continue;

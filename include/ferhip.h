@@ -214,7 +214,12 @@ int ferhip_set_csc(ferhip_ctx *c, int matrix);
  * nal_type[s]: FERHIP_NAL_IDR / FERHIP_NAL_SLICE / FERHIP_NAL_AUTO / FERHIP_NAL_NONE per stream on input, the
  * type actually used on output (NULL = AUTO for all).  After the call the picture buffers
  * hold the reconstruction (like the reference's `frame`) and become the reference picture.
- * rbsp (host): nstreams * rbsp_stride bytes; rbsp_len[s] receives NumBytesInRBSP. */
+ * rbsp (host): nstreams * rbsp_stride bytes; rbsp_len[s] receives NumBytesInRBSP.
+ * frame_num and pic_order_cnt_lsb wrap modulo 512 / 1024 (the field widths of the SPS): the 513th picture of a run
+ * without an IDR picture carries frame_num 0 again.  This is the one place where the encoder does not follow the reference:
+ * its bit writer adds a value into the buffer without masking it (writeRawBits, F/rbsp_IO.cpp:123-127), so past 512
+ * pictures without an IDR picture the reference's own writer corrupts the slice header.  An IDR picture takes
+ * idr_pic_id + 1 only directly behind an IDR picture; that test reads the counter before the wrap, as the reference's does. */
 int ferhip_encode_picture(ferhip_ctx *c, int *nal_type, uint8_t *rbsp, size_t rbsp_stride, uint32_t *rbsp_len);
 
 /* selectNALUnitType() (F/ref_frames.cpp:185-234) for the pictures set by ferhip_set_frames: IDR for the
@@ -489,7 +494,8 @@ int ferhip_set_reference(ferhip_ctx *c, const void *src);
  * S Annex-B streams (4-byte start codes, as the reference reads them) of equal picture size are
  * decoded side by side: slice_data parsing runs one wavefront per picture over a window of pictures of
  * every stream at once, reconstruction one wavefront per macroblock, picture by picture.  out (host, may be NULL): [max_pictures][S][W*H*3/2], picture t of
- * stream s at (t*S + s)*W*H*3/2; pictures[s] = number decoded.  Sub-8x8 partitions, ref_idx_l0 and
+ * stream s at (t*S + s)*W*H*3/2; pictures[s] = number decoded; the slots behind a stream's last picture are left as they
+ * were.  Sub-8x8 partitions, ref_idx_l0 and
  * reference list modification are handled the way the reference handles them; syntax the
  * GPU path does not implement (I_PCM, CABAC, High profiles, field coding, slice groups) returns FERHIP_E_UNSUP.
  *

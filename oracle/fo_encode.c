@@ -175,6 +175,10 @@ static void slice_header(fo_ctx *c, fo_bw *w, int nal_type)
     fo_bw_ue(w, 0);
     fo_bw_ue(w, (unsigned)c->slice_type);
     fo_bw_ue(w, 0);
+    /* frame_num and poc_lsb grow without bound; fo_bw_put keeps the low bits, so both wrap modulo 512 / 1024.  The one
+     * place where oracle and product knowingly leave the reference: its writeRawBits adds the value in unmasked
+     * (F/rbsp_IO.cpp:123-127), and past 512 pictures without an IDR the carry corrupts the header
+     * (tests/test_long_run_host.py states it as a test). */
     fo_bw_put(w, c->log2_max_frame_num, (uint32_t)c->frame_num);
     if (nal_type == FO_NAL_IDR) fo_bw_ue(w, (unsigned)c->idr_pic_id);
     fo_bw_put(w, c->log2_max_poc_lsb, (uint32_t)c->poc_lsb);
