@@ -131,71 +131,6 @@ __global__ void k_dec_build_luts(DecLuts *L)
     }
 }
 
-// P macroblock vectors: PredictMV + DeriveMVs (F/mode_pred.cpp:381-482), quadrant storage.  The vectors are kept as 16-bit
-// quarter samples (a level allows +-8192); false when a component does not fit: the caller refuses the picture instead of
-// predicting from a wrapped vector (the reference keeps ints)
-__device__ bool dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int mb, int type, const int mvd[4][2], const int sub[4])
-{
-    MvCtx c;
-    c.mv = mvs;
-    c.mb_type = mbt;
-    c.mbw = d.mbw;
-    c.cur = mb;
-    c.type = type;
-    c.coh = false;
-    short *o = mvs + (size_t)mb * 8;
-    if (type == FER_P_SKIP) {
-        int mx = 0, my = 0;
-        if (!(mb < d.mbw || mb % d.mbw == 0)) {
-            int up = mb - d.mbw, lf = mb - 1;
-            bool iu = mbt[up] >= 5 && mbt[up] <= 30, il = mbt[lf] >= 5 && mbt[lf] <= 30;
-            bool zu = !iu && (mvs[(up * 4 + 2) * 2] | mvs[(up * 4 + 2) * 2 + 1]) == 0;
-            bool zl = !il && (mvs[(lf * 4 + 1) * 2] | mvs[(lf * 4 + 1) * 2 + 1]) == 0;
-            if (!(zu || zl)) predict_luma(c, 0, mx, my);
-        }
-        for (int q = 0; q < 4; q++) {
-            o[q * 2] = (short)mx;
-            o[q * 2 + 1] = (short)my;
-        }
-        return true;  // (zero, or the median of vectors that fit)
-    }
-    bool fits = true;
-    int np = type == 0 ? 1 : (type <= 2 ? 2 : 4);
-    for (int i = 0; i < np; i++) {
-        int px, py;
-        if (np == 4)
-            predict_luma_quadrant(c, i, sub, px, py);
-        else
-            predict_luma(c, i, px, py);
-        px += mvd[i][0];
-        py += mvd[i][1];
-        fits &= px == (short)px && py == (short)py;
-        // quadrants covered by partition i
-        int q0, q1, q2 = -1, q3 = -1;
-        if (np == 1) {
-            q0 = 0;
-            q1 = 1;
-            q2 = 2;
-            q3 = 3;
-        } else if (type == FER_P_16x8) {
-            q0 = i * 2;
-            q1 = i * 2 + 1;
-        } else if (type == FER_P_8x16) {
-            q0 = i;
-            q1 = i + 2;
-        } else {
-            q0 = q1 = i;
-        }
-        int qs[4] = {q0, q1, q2, q3};
-        for (int k = 0; k < 4; k++)
-            if (qs[k] >= 0) {
-                o[qs[k] * 2] = (short)px;
-                o[qs[k] * 2 + 1] = (short)py;
-            }
-    }
-    return fits;
-}
-
 // One wavefront per (stream, picture of the window).  What a picture inherits from its predecessor -- the
 // mb_qp_delta that persists when absent and the ChromaACLevel block that persists into macroblocks without
 // residual (reference quirks) -- changes no bit position, so every picture is parsed as if it inherited zeros;
@@ -520,30 +455,8 @@ __global__ __launch_bounds__(64 * DEC_PW) void k_dec_parse(FerDev d, DecBatch B,
                     break;
                 }
             } else if (i4) {
-                // getIntra4x4PredMode, F/intra.cpp:77-136
-                unsigned long long cm = 0;  // this macroblock's modes, 4 bits per block
-                for (int blk = 0; blk < 16; blk++) {
-                    bool edgeA = blk == 0 || blk == 2 || blk == 8 || blk == 10;
-                    bool edgeB = blk == 0 || blk == 1 || blk == 4 || blk == 5;
-                    bool okA = !(edgeA && mbx == 0), okB = !(edgeB && mby == 0);
-                    int mA = 2, mB = 2;
-                    if (okA && okB && !constrained_intra) {
-                        // c_nbA / c_nbB (the neighbouring block to the left / above), 4 bits per block: no table load in the chain
-                        const int nA = (int)((0xebc9af8d63412705ull >> (4 * blk)) & 15), nB = (int)((0xdc76983254fe10baull >> (4 * blk)) & 15);
-                        if (edgeA)
-                            mA = left_i4 ? (int)((left_modes >> (4 * nA)) & 15) : 2;
-                        else
-                            mA = (int)((cm >> (4 * nA)) & 15);
-                        if (edgeB)
-                            mB = above_i4 ? (int)((above_modes >> (4 * ((nB & 1) | ((nB >> 1) & 2)))) & 15) : 2;  // 10, 11, 14, 15 -> 0 .. 3
-                        else
-                            mB = (int)((cm >> (4 * nB)) & 15);
-                    }
-                    int pm = mA <= mB ? mA : mB;
-                    int f = (int)((i4flags >> (4 * blk)) & 15);
-                    int mode = (f & 8) ? pm : ((f & 7) < pm ? (f & 7) : (f & 7) + 1);
-                    cm |= (unsigned long long)mode << (4 * blk);
-                }
+                // this macroblock's modes, 4 bits per block
+                const unsigned long long cm = dec_i4_modes(i4flags, mbx, mby, constrained_intra, left_i4, left_modes, above_i4, above_modes);
                 if (lane < 16) p_i4mode[mbi * 16 + lane] = (uint8_t)((cm >> (4 * lane)) & 15);
                 if (lane == 0) i4row[mbx] = (uint16_t)(((cm >> 40) & 0xff) | (((cm >> 56) & 0xff) << 8));  // blocks 10, 11 | 14, 15
                 left_modes = cm;
@@ -878,6 +791,12 @@ void fer_launch_decode_recon(const FerDev &d, bool anyP, bool anyIntra, hipStrea
         int maxk = min(d.mbh, (d.mbw + 1) / 2);
         for (int dg = 0; dg < ndiag; dg++) hipLaunchKernelGGL(k_dec_intra, dim3(maxk, d.S), dim3(64), 0, st, d, dg);
     }
+}
+
+// k_dec_intra of one anti-diagonal alone (the neighbourhood seam, ferhip_intra_mbs in fer_mbunit.hip)
+void fer_launch_decode_intra_diag(const FerDev &d, int diag, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_dec_intra, dim3(min(d.mbh, (d.mbw + 1) / 2), d.S), dim3(64), 0, st, d, diag);
 }
 
 // The decoded pictures of one step, whole and as tight I420, from the plane-major picture set `set` ([S] Y, [S] Cb, [S] Cr)

@@ -1,6 +1,7 @@
-// fer_decode_dev.h -- device bit reader, decode tables and CAVLC block parser shared by the decode twin (fer_decode.hip)
-// and the per-macroblock parse seam (k_cavlc_parse_blocks, k_residual_mbs in fer_mbunit.hip): residual_block_cavlc and the
-// decoder's form of nC (F/residual.cpp:1069-1386, :424-538).  The tables are built once per device by dec_luts()
+// fer_decode_dev.h -- device bit reader, decode tables, CAVLC block parser and Intra4x4 mode derivation shared by the decode
+// twin (fer_decode.hip) and the per-macroblock seams (k_cavlc_parse_blocks, k_residual_mbs, k_seam_i4_modes in
+// fer_mbunit.hip): residual_block_cavlc and the decoder's form of nC (F/residual.cpp:1069-1386, :424-538),
+// getIntra4x4PredMode (F/intra.cpp:77-136).  The tables are built once per device by dec_luts()
 // (fer_decode.hip, declared in fer_internal.h).
 #pragma once
 #include "fer_dev.h"
@@ -237,6 +238,40 @@ __device__ int dec_block(DecBits &b, const DecLutsLds *L, int16_t *coef, int max
         }
     }
     return TotalCoeff;
+}
+
+// getIntra4x4PredMode, F/intra.cpp:77-136, for the sixteen blocks of the Intra4x4 macroblock at (mbx, mby): the modes, 4
+// bits per block, from i4flags (prev_intra4x4_pred_mode_flag << 3 | rem_intra4x4_pred_mode, 4 bits per block) and the
+// neighbours' side: left_i4 / above_i4 = the macroblock to the left / above is Intra4x4, left_modes = its sixteen modes,
+// above_modes = the modes of its blocks 10, 11, 14, 15.  Everything is wave-uniform (scalar registers); shared by
+// k_dec_parse and the neighbourhood seam (k_seam_i4_modes, fer_mbunit.hip).
+__device__ __forceinline__ unsigned long long dec_i4_modes(unsigned long long i4flags, int mbx, int mby, bool constrained_intra, bool left_i4,
+                                                           unsigned long long left_modes, bool above_i4, unsigned above_modes)
+{
+    unsigned long long cm = 0;
+    for (int blk = 0; blk < 16; blk++) {
+        bool edgeA = blk == 0 || blk == 2 || blk == 8 || blk == 10;
+        bool edgeB = blk == 0 || blk == 1 || blk == 4 || blk == 5;
+        bool okA = !(edgeA && mbx == 0), okB = !(edgeB && mby == 0);
+        int mA = 2, mB = 2;
+        if (okA && okB && !constrained_intra) {
+            // c_nbA / c_nbB (the neighbouring block to the left / above), 4 bits per block: no table load in the chain
+            const int nA = (int)((0xebc9af8d63412705ull >> (4 * blk)) & 15), nB = (int)((0xdc76983254fe10baull >> (4 * blk)) & 15);
+            if (edgeA)
+                mA = left_i4 ? (int)((left_modes >> (4 * nA)) & 15) : 2;
+            else
+                mA = (int)((cm >> (4 * nA)) & 15);
+            if (edgeB)
+                mB = above_i4 ? (int)((above_modes >> (4 * ((nB & 1) | ((nB >> 1) & 2)))) & 15) : 2;  // 10, 11, 14, 15 -> 0 .. 3
+            else
+                mB = (int)((cm >> (4 * nB)) & 15);
+        }
+        int pm = mA <= mB ? mA : mB;
+        int f = (int)((i4flags >> (4 * blk)) & 15);
+        int mode = (f & 8) ? pm : ((f & 7) < pm ? (f & 7) : (f & 7) + 1);
+        cm |= (unsigned long long)mode << (4 * blk);
+    }
+    return cm;
 }
 
 // What the total-coefficient prediction needs from a decoded neighbour, kept in LDS: one entry per macroblock

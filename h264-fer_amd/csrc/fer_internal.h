@@ -30,6 +30,7 @@ void fer_launch_me_resolve(const FerDev &d, hipStream_t st);
 void fer_launch_basic_stat(const FerDev &d, hipStream_t st);
 void fer_launch_p_resid(const FerDev &d, hipStream_t st);
 void fer_launch_intra(const FerDev &d, hipStream_t st);
+void fer_launch_intra_diag(const FerDev &d, int diag, hipStream_t st);  // one anti-diagonal of k_intra_mb
 void fer_launch_cavlc(const FerDev &d, hipStream_t st);
 void fer_launch_rc_plan(const FerDev &d, hipStream_t st);
 int fer_quality_groups(const FerDev &d);
@@ -42,6 +43,7 @@ struct DecLuts;
 const DecLuts *dec_luts(hipStream_t st);
 void fer_launch_decode_parse(const FerDev &d, const DecBatch &B, hipStream_t st);
 void fer_launch_decode_recon(const FerDev &dslice, bool anyP, bool anyIntra, hipStream_t st);
+void fer_launch_decode_intra_diag(const FerDev &dslice, int diag, hipStream_t st);  // one anti-diagonal of k_dec_intra
 // map[j] = (stream, slot): picture of stream map[j].x in `set` -> dst + map[j].y * W*H*3/2 (I420), for j < n; dst is
 // 16-byte aligned (any other output of the live decoder goes through fer_launch_pic_emit_slots)
 void fer_launch_decode_out(const FerDev &d, const uint8_t *set, const int2 *map, int n, uint8_t *dst, hipStream_t st);

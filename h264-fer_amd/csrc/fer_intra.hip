@@ -456,3 +456,9 @@ void fer_launch_intra(const FerDev &d, hipStream_t st)
     int maxk = min(d.mbh, (d.mbw + 1) / 2);
     for (int dg = 0; dg < ndiag; dg++) hipLaunchKernelGGL(k_intra_mb, dim3(maxk, d.S), dim3(64), 0, st, d, dg);
 }
+
+// one anti-diagonal alone: the neighbourhood seam (ferhip_intra_mbs, fer_mbunit.hip) runs the macroblock of a job this way
+void fer_launch_intra_diag(const FerDev &d, int diag, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_intra_mb, dim3(min(d.mbh, (d.mbw + 1) / 2), d.S), dim3(64), 0, st, d, diag);
+}

@@ -558,12 +558,15 @@ extern "C" void residual(int startIdx, int endIdx)
 
 // AllocateMemory() of F/mode_pred.cpp:22-39: the vector arrays [macroblock][subMbIdx][subMbPartIdx]; with them the
 // CodedBlockPattern arrays that init_h264_structures sizes from the picture (F/h264_globals.cpp:245-246)
+extern "C" int *Intra4x4PredMode, *refIdxL0;
 extern "C" void AllocateMemory(void)
 {
     const int nmb = (frame.Lwidth >> 4) * (frame.Lheight >> 4);
     if (!CodedBlockPatternLumaArray || g_mv_nmb != nmb) {  // (like the vector arrays, never freed)
         CodedBlockPatternLumaArray = new int[nmb > 0 ? nmb : 1]();
         CodedBlockPatternChromaArray = new int[nmb > 0 ? nmb : 1]();
+        Intra4x4PredMode = new int[nmb > 0 ? nmb * 16 : 16]();  // F/h264_globals.cpp: [macroblock << 4 | luma4x4BlkIdx]
+        refIdxL0 = new int[nmb > 0 ? nmb : 1]();                // F/mode_pred.cpp:22-39
     }
     if (mvL0x && g_mv_nmb == nmb) return;
     auto alloc3 = [&](int ***&p) {
@@ -632,4 +635,204 @@ extern "C" void Decode(int predL[16][16], int predCr[8][8], int predCb[8][8])
         parts[k] = k & 3;
     }
     mc_parts("Decode", predL, predCr, predCb, &dpb, CurrMbAddr, 16, subs, parts);
+}
+
+// ---- the neighbourhood seam under the reference's names (ferhip_intra_mbs, ferhip_mv_mbs of fer_mbunit.hip): one
+// macroblock per call on the reference's globals.  The shim cuts the 3x2-macroblock neighbourhood of CurrMbAddr out of
+// `frame` and the state arrays, so that the macroblock sits at the pos that has exactly its neighbours.
+extern "C" {
+int *Intra4x4PredMode = nullptr, *refIdxL0 = nullptr;
+int intra_chroma_pred_mode = 0;
+unsigned char prev_intra4x4_pred_mode_flag[16];
+int rem_intra4x4_pred_mode[16];
+int mvd_l0[4][4][2];
+int sub_mb_type[4];
+int ferhip_legacy_constrained_intra_pred = 0;
+int ferhip_legacy_mbsize[2];
+}
+
+// pos of macroblock CurrMbAddr and the picture address of every macroblock of its neighbourhood (-1: outside the picture);
+// false, with the message, for a state the seam cannot take
+static bool nbhd_window(const char *name, int &pos, int win[FERHIP_NB_MBS])
+{
+    const int mbw = frame.Lwidth >> 4, mbh = frame.Lheight >> 4;
+    if (!frame.L || !mvL0x || !Intra4x4PredMode || !fer_seam_mb_addr_ok(CurrMbAddr, mbw * mbh) || !fer_seam_mb_addr_ok(CurrMbAddr, g_mv_nmb) ||
+        g_mv_nmb > FERHIP_LEGACY_MAX_MBS) {
+        legacy_block(name, FERHIP_E_ARG);
+        return false;
+    }
+    if (mbw < 2) {  // B without C and D, first and last column at once: no 3x2 neighbourhood has that macroblock
+        fprintf(stderr, "%s: a picture one macroblock wide is out of this seam's reach (%d)\n", name, FERHIP_E_UNSUP);
+        return false;
+    }
+    const int mbx = CurrMbAddr % mbw, mby = CurrMbAddr / mbw;
+    const bool A = mbx > 0, B = mby > 0, last = mbx == mbw - 1;
+    pos = B ? (!A ? 3 : (last ? 5 : 4)) : (!A ? 0 : (last ? 2 : 1));
+    const int ox = mbx - pos % 3, oy = mby - pos / 3;
+    for (int m = 0; m < FERHIP_NB_MBS; m++) {
+        const int rx = ox + m % 3, ry = oy + m / 3;
+        win[m] = (rx >= 0 && rx < mbw && ry >= 0 && ry < mbh) ? ry * mbw + rx : -1;
+    }
+    return true;
+}
+static void nbhd_side(ferhip_nb_mb *mb, int pos, const int win[FERHIP_NB_MBS])
+{
+    for (int m = 0; m < pos; m++) {
+        const int r = win[m];
+        if (r < 0) continue;  // (outside the picture: no neighbour of the macroblock, left zero)
+        ferhip_nb_mb &N = mb[m];
+        N.mb_type = mb_type_array[r];
+        N.cbp_luma = CodedBlockPatternLumaArray[r];
+        N.cbp_chroma = CodedBlockPatternChromaArray[r];
+        for (int b = 0; b < 16; b++) {
+            N.tc_luma[b] = totalcoeff_array_luma[r][b];
+            N.i4mode[b] = Intra4x4PredMode[r * 16 + b];
+        }
+        for (int b = 0; b < 8; b++) N.tc_chroma[b >> 2][b & 3] = totalcoeff_array_chroma[b >> 2][r][b & 3];
+        for (int q = 0; q < 4; q++) {
+            N.mv[q][0] = mvL0x[r][q][0];
+            N.mv[q][1] = mvL0y[r][q][0];
+        }
+    }
+}
+static void nbhd_picture(ferhip_intra_job &J, const int win[FERHIP_NB_MBS])
+{
+    for (int m = 0; m < FERHIP_NB_MBS; m++) {
+        if (win[m] < 0) continue;
+        const int mbw = frame.Lwidth >> 4, xP = (win[m] % mbw) << 4, yP = (win[m] / mbw) << 4, wx = (m % 3) << 4, wy = (m / 3) << 4;
+        for (int y = 0; y < 16; y++) memcpy(&J.Y[wy + y][wx], frame.L + (size_t)(yP + y) * frame.Lwidth + xP, 16);
+        for (int y = 0; y < 8; y++) {
+            memcpy(&J.Cb[wy / 2 + y][wx / 2], frame.C[0] + (size_t)(yP / 2 + y) * frame.Cwidth + xP / 2, 8);
+            memcpy(&J.Cr[wy / 2 + y][wx / 2], frame.C[1] + (size_t)(yP / 2 + y) * frame.Cwidth + xP / 2, 8);
+        }
+    }
+}
+static void nbhd_preds(const ferhip_intra_result &R, int predL[16][16], int predCr[8][8], int predCb[8][8])
+{
+    if (predL) memcpy(&predL[0][0], R.predL, sizeof R.predL);
+    if (predCb) memcpy(&predCb[0][0], R.predCb, sizeof R.predCb);
+    if (predCr) memcpy(&predCr[0][0], R.predCr, sizeof R.predCr);
+}
+static void nbhd_put_luma(const ferhip_intra_result &R)
+{
+    int xP, yP;
+    mb_origin(xP, yP);
+    for (int i = 0; i < 256; i++) frame.L[(size_t)(yP + (i >> 4)) * frame.Lwidth + xP + (i & 15)] = (unsigned char)R.recY[i];
+}
+
+// intraPredictionEncoding(predL, predCr, predCb), F/intra.cpp:949, in an I slice: the decision for macroblock CurrMbAddr of
+// `frame` (source at the macroblock, reconstruction around it) at QPy, with mb_type_array[CurrMbAddr] the stale entry the first
+// coded_mb_size reads.  As in the reference: returns the Intra16x16 mode or -1; Intra4x4PredMode, intra_chroma_pred_mode,
+// prev_intra4x4_pred_mode_flag, rem_intra4x4_pred_mode and the predictions are set; for -1 the luma of `frame` holds the
+// reconstruction and LumaLevel its levels, and mb_type_array[CurrMbAddr] is I_4x4 (0).  ferhip_legacy_mbsize = the two
+// coded_mb_size values.  Chroma levels, CBP and the final mb_type are the caller's quantizationTransform and
+// setCodedBlockPattern, as in RBSP_encode.  On an error: the message, 0 returned, nothing changed.
+extern "C" int intraPredictionEncoding(int predL[16][16], int predCr[8][8], int predCb[8][8])
+{
+    int pos, win[FERHIP_NB_MBS];
+    if (!nbhd_window("intraPredictionEncoding", pos, win)) return 0;
+    ferhip_intra_job *J = new ferhip_intra_job();
+    ferhip_intra_result *R = new ferhip_intra_result();
+    J->op = FERHIP_INTRA_ENCODE;
+    J->pos = pos;
+    J->slice_type = 2;
+    J->qp = QPy;
+    nbhd_side(J->mb, pos, win);
+    J->mb[pos].mb_type = mb_type_array[CurrMbAddr];
+    nbhd_picture(*J, win);
+    const int rc = ferhip_intra_mbs(J, R, 1);
+    legacy_block("intraPredictionEncoding", rc);
+    int ret = 0;
+    if (!rc) {
+        ret = R->ret;
+        for (int b = 0; b < 16; b++) {
+            Intra4x4PredMode[CurrMbAddr * 16 + b] = R->i4mode[b];
+            prev_intra4x4_pred_mode_flag[b] = (unsigned char)R->prev_flag[b];
+            if (!R->prev_flag[b]) rem_intra4x4_pred_mode[b] = R->rem_mode[b];
+        }
+        intra_chroma_pred_mode = R->chroma_mode;
+        ferhip_legacy_mbsize[0] = R->mbsize[0];
+        ferhip_legacy_mbsize[1] = R->mbsize[1];
+        nbhd_preds(*R, predL, predCr, predCb);
+        mb_type_array[CurrMbAddr] = 0;
+        if (ret == -1) {
+            memcpy(LumaLevel, R->lumaLevel, sizeof LumaLevel);
+            nbhd_put_luma(*R);
+        }
+    }
+    delete J;
+    delete R;
+    return ret;
+}
+
+// intraPrediction(predL, predCr, predCb), F/intra.cpp:770, with getIntra4x4PredMode: macroblock CurrMbAddr of type mb_type
+// (numbering of ferhip_legacy_slice_type) from prev_intra4x4_pred_mode_flag, rem_intra4x4_pred_mode, intra_chroma_pred_mode,
+// ferhip_legacy_constrained_intra_pred and, for Intra4x4, LumaLevel at QPy.  Sets the predictions; for Intra4x4 also
+// Intra4x4PredMode and the luma of `frame` (the reference reconstructs block by block inside the function).
+extern "C" void intraPrediction(int predL[16][16], int predCr[8][8], int predCb[8][8])
+{
+    int pos, win[FERHIP_NB_MBS];
+    if (!nbhd_window("intraPrediction", pos, win)) return;
+    ferhip_intra_job *J = new ferhip_intra_job();
+    ferhip_intra_result *R = new ferhip_intra_result();
+    J->op = FERHIP_INTRA_DECODE;
+    J->pos = pos;
+    J->slice_type = ferhip_legacy_slice_type % 5 == 0 ? 0 : 2;
+    J->qp = QPy;
+    J->constrained_intra = ferhip_legacy_constrained_intra_pred ? 1 : 0;
+    J->chroma_mode = intra_chroma_pred_mode;
+    nbhd_side(J->mb, pos, win);
+    J->mb[pos].mb_type = mb_type;
+    const bool i4 = pred_class_of(mb_type) == 0;
+    for (int b = 0; b < 16 && i4; b++) {
+        J->prev_flag[b] = prev_intra4x4_pred_mode_flag[b] ? 1 : 0;
+        J->rem_mode[b] = J->prev_flag[b] ? 0 : rem_intra4x4_pred_mode[b];
+    }
+    if (i4) memcpy(J->lumaLevel, LumaLevel, sizeof LumaLevel);
+    nbhd_picture(*J, win);
+    const int rc = ferhip_intra_mbs(J, R, 1);
+    legacy_block("intraPrediction", rc);
+    if (!rc) {
+        nbhd_preds(*R, predL, predCr, predCb);
+        if (i4) {
+            for (int b = 0; b < 16; b++) Intra4x4PredMode[CurrMbAddr * 16 + b] = R->i4mode[b];
+            nbhd_put_luma(*R);
+        }
+    }
+    delete J;
+    delete R;
+}
+
+// DeriveMVs(), F/mode_pred.cpp:428: the vectors of macroblock CurrMbAddr of type mb_type (P numbering) from mvd_l0,
+// sub_mb_type and the neighbours' mb_type_array and mvL0x / mvL0y entries into mvL0x / mvL0y [CurrMbAddr] (every
+// sub-partition of a quadrant takes its vector), refIdxL0[CurrMbAddr] = 0.  A vector that leaves 16 bits: the message,
+// nothing changed (the reference keeps ints).  ClearMVD(), F/mode_pred.cpp:41: mvd_l0 = 0.
+extern "C" void ClearMVD(void) { memset(mvd_l0, 0, sizeof mvd_l0); }
+extern "C" void DeriveMVs(void)
+{
+    int pos, win[FERHIP_NB_MBS];
+    if (!nbhd_window("DeriveMVs", pos, win)) return;
+    ferhip_mv_job *J = new ferhip_mv_job();
+    ferhip_mv_result R = {};
+    J->op = FERHIP_MV_DERIVE;
+    J->pos = pos;
+    J->mb_type = mb_type;
+    for (int i = 0; i < 4; i++) {
+        J->sub_mb_type[i] = (mb_type == 3 || mb_type == 4) ? sub_mb_type[i] : 0;
+        J->mvd[i][0] = mvd_l0[i][0][0];
+        J->mvd[i][1] = mvd_l0[i][0][1];
+    }
+    nbhd_side(J->mb, pos, win);
+    int rc = ferhip_mv_mbs(J, &R, 1);
+    if (!rc && !R.fits) rc = FERHIP_E_UNSUP;
+    legacy_block("DeriveMVs", rc);
+    if (!rc) {
+        for (int q = 0; q < 4; q++)
+            for (int j = 0; j < 4; j++) {
+                mvL0x[CurrMbAddr][q][j] = R.mv[q][0];
+                mvL0y[CurrMbAddr][q][j] = R.mv[q][1];
+            }
+        refIdxL0[CurrMbAddr] = 0;
+    }
+    delete J;
 }

@@ -10,15 +10,21 @@
 //   residual_block_cavlc                        F/residual.cpp:1069-1386              k_cavlc_parse_blocks
 //   residual_write / residual(0, 15)            F/residual.cpp:300-372 / :959-1067    k_residual_write, k_residual_parse
 //   MotionCompensateSubMBPart                   F/mocomp.cpp:152-195                  k_mc_parts
+//   intraPredictionEncoding + coded_mb_size     F/intra.cpp:949, F/rbsp_encoding.cpp:330   k_intra_mb over a 3x2 neighbourhood
+//   intraPrediction, getIntra4x4PredMode        F/intra.cpp:770, :77                  k_seam_i4_modes + k_dec_intra
+//   DeriveMVs and the encoder's mvd             F/mode_pred.cpp:428                   k_seam_mv
 //   forward / inverse residual, DC, scan        F/quantizationTransform.h, scaleTransform.h  k_block_kat
 // Not a fast path: one wavefront (or thread) per job, records of plain int32.  Every entry point checks its arguments
 // (fer_seam_host.h) before its first HIP call.  The legacy-name shims are in fer_legacy.hip.
 #include "fer_cavlc_dev.h"
 #include "fer_ctx.h"
 #include "fer_decode_dev.h"
+#include "fer_intra_dev.h"
+#include "fer_mvpred.h"
 #include "fer_seam_host.h"
 
 #include <algorithm>
+#include <string.h>
 
 // list[k] = c[zig-zag k] (transformScan, F/quantizationTransform.cpp:310-325); the Intra16x16AC / chroma AC form drops the DC
 __device__ __forceinline__ void mbu_scan(const int c[16], int32_t *list, bool ac)
@@ -566,6 +572,381 @@ extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result
     // (F/residual.cpp:530-541); no neighbour can read it (the CBP gates it), the encoder's side information keeps the AC count
     for (size_t j = 0; j < n; j++)
         if (jobs[j].op == FERHIP_RES_WRITE && jobs[j].cls == 1 && !(jobs[j].cbp_luma & 1)) results[j].tc_luma[0] = count_nz(jobs[j].dc16, 16);
+    return 0;
+}
+
+// ---- the neighbourhood seam: intraPredictionEncoding / intraPrediction and DeriveMVs of one macroblock among its
+// neighbours.  Job j is stream j of a context of 3x2-macroblock pictures (FERHIP_NB_W x FERHIP_NB_H) over a hand-built
+// FerDev, its macroblock sits at address pos, and the picture kernels run on it as they stand: k_intra_mb (ENCODE) and
+// k_dec_intra (DECODE) are launched for the one anti-diagonal of pos, over the streams of the jobs with that pos.  A
+// diagonal launch also visits the other macroblock of the diagonal (2 and 3 share one); nothing it reads or writes there
+// is a neighbour of the job's macroblock, and in DECODE its type is set to P_Skip so that k_dec_intra passes it by.
+#define SEAM_YSZ (FERHIP_NB_W * FERHIP_NB_H)
+#define SEAM_CSZ (SEAM_YSZ / 4)
+#define SEAM_MBW (FERHIP_NB_W / 16)
+
+// getIntra4x4PredMode of the DECODE jobs: dec_i4_modes (fer_decode_dev.h) fed from the FerDev side information the way
+// k_dec_parse feeds it from its neighbour rows.  One thread per stream (the function is scalar code).
+__global__ __launch_bounds__(64) void k_seam_i4_modes(FerDev d, const uint8_t *pos)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= d.S) return;
+    const int p = pos[s], mbx = p % d.mbw, mby = p / d.mbw;
+    const size_t mbi = (size_t)s * d.nmb + p;
+    const int i4t = d.hdr[s * 4 + 3] == 2 ? 0 : 5;
+    if (d.mb_type[mbi] != i4t) return;
+    unsigned long long i4flags = 0, left_modes = 0;
+    unsigned above_modes = 0;
+    for (int blk = 0; blk < 16; blk++) i4flags |= (unsigned long long)(d.i4flag[mbi * 16 + blk] & 15) << (4 * blk);
+    const bool left_i4 = mbx > 0 && d.mb_type[mbi - 1] == i4t, above_i4 = mby > 0 && d.mb_type[mbi - d.mbw] == i4t;
+    if (left_i4)
+        for (int blk = 0; blk < 16; blk++) left_modes |= (unsigned long long)(d.i4mode[(mbi - 1) * 16 + blk] & 15) << (4 * blk);
+    if (above_i4) {
+        const uint8_t *m = d.i4mode + (mbi - d.mbw) * 16;
+        above_modes = (unsigned)m[10] | ((unsigned)m[11] << 4) | ((unsigned)m[14] << 8) | ((unsigned)m[15] << 12);
+    }
+    const unsigned long long cm = dec_i4_modes(i4flags, mbx, mby, d.hdr[s * 4 + 1] != 0, left_i4, left_modes, above_i4, above_modes);
+    for (int blk = 0; blk < 16; blk++) d.i4mode[mbi * 16 + blk] = (uint8_t)((cm >> (4 * blk)) & 15);
+}
+
+// predL / predCb / predCr of the macroblock at pos, by the decode-side predictors (fetch4 + pred4x4, pred16_px,
+// pred_chroma_px of fer_intra_dev.h) on the reconstructed picture: every sample an Intra4x4 block predicts from belongs
+// to a neighbouring macroblock or to a block in front of it, so the sixteen blocks are evaluated side by side.
+// One wavefront per stream; pred[s] = 256 luma, 64 Cb, 64 Cr.
+__global__ __launch_bounds__(64) void k_seam_intra_pred(FerDev d, const uint8_t *pos, int32_t *pred)
+{
+    __shared__ IntraLds L;
+    const int lane = threadIdx.x, s = blockIdx.x;
+    const int p = pos[s], mbx = p % d.mbw, mby = p / d.mbw;
+    const size_t mbi = (size_t)s * d.nmb + p;
+    const int W = d.W, Wc = d.Wc, xp = mbx << 4, yp = mby << 4;
+    const uint8_t *Y = d.curY + (size_t)s * d.ysz;
+    const uint8_t *Cp[2] = {d.curCb + (size_t)s * d.csz, d.curCr + (size_t)s * d.csz};
+    const bool availL = mbx > 0, availT = mby > 0, lastcol = mbx == d.mbw - 1;
+    for (int i = lane; i < 17 * 21; i += 64) {  // the window of k_intra_mb: the macroblock, its left column, the row above with four more
+        const int r = i / 21, c = i % 21;
+        const int gx = xp + c - 1, gy = yp + r - 1;
+        int v = -1;
+        if (gx >= 0 && gy >= 0 && gx < W && (r == 0 || c <= 16)) v = Y[(size_t)gy * W + gx];
+        L.fr[r][c] = (int16_t)v;
+    }
+    for (int i = lane; i < 2 * 9 * 9; i += 64) {
+        const int pl = i / 81, r = (i % 81) / 9, c = i % 9;
+        const int gx = xp / 2 + c - 1, gy = yp / 2 + r - 1;
+        L.cfr[pl][r][c] = (int16_t)((gx >= 0 && gy >= 0) ? Cp[pl][(size_t)gy * Wc + gx] : -1);
+    }
+    __syncthreads();
+    int32_t *o = pred + (size_t)s * 384;
+    const int stype = (int)d.hdr[s * 4 + 3], t = d.mb_type[mbi], chroma_mode = d.chroma_mode[mbi];
+    {
+        const int cx = lane & 7, cy = lane >> 3;
+        for (int pl = 0; pl < 2; pl++) o[256 + pl * 64 + lane] = pred_chroma_px(L.cfr[pl], chroma_mode, cx, cy, availL, availT);
+    }
+    if (t == (stype == 2 ? 0 : 5)) {
+        if (lane < 16) {
+            int q[13], b[16];
+            fetch4(L, lane, lastcol, q);
+            pred4x4(d.i4mode[mbi * 16 + lane], q, b);
+            for (int i = 0; i < 16; i++) o[(c_by[lane] + (i >> 2)) * 16 + c_bx[lane] + (i & 3)] = b[i];
+        }
+    } else {
+        P16 q16;
+        pred16_params(L, availL, availT, q16);
+        const int mode = ((stype == 2 ? t : t - 5) - 1) & 3;
+        for (int i = lane; i < 256; i += 64) o[i] = pred16_px(L, q16, mode, i & 15, i >> 4);
+    }
+}
+
+static FerDev seam_streams(const FerDev &d, int s0, int cnt)  // the same context, streams s0 .. s0 + cnt - 1 only
+{
+    FerDev g = d;
+    g.S = cnt;
+    g.curY += (size_t)s0 * d.ysz;
+    g.curCb += (size_t)s0 * d.csz;
+    g.curCr += (size_t)s0 * d.csz;
+    g.qp += s0;
+    g.hdr += (size_t)s0 * 4;
+    g.mb_type += (size_t)s0 * d.nmb;
+    g.cbp += (size_t)s0 * d.nmb * 2;
+    g.tc += (size_t)s0 * d.nmb * 24;
+    g.i4mode += (size_t)s0 * d.nmb * 16;
+    g.i4flag += (size_t)s0 * d.nmb * 16;
+    g.chroma_mode += (size_t)s0 * d.nmb;
+    g.levels += (size_t)s0 * d.nmb * FER_LEVELS;
+    g.mbsize += (size_t)s0 * d.nmb * 2;
+    g.dec_qp += (size_t)s0 * d.nmb;
+    g.dec_state += (size_t)s0 * 4;
+    return g;
+}
+
+extern "C" int ferhip_chroma_qp(int qpy);  // fer_api.hip: qPiToQPc for chroma_qp_index_offset 0, the encoder's
+
+extern "C" int ferhip_intra_mbs(const ferhip_intra_job *jobs, ferhip_intra_result *results, size_t n)
+{
+    if (fer_seam_check_intra_mbs(jobs, results, n)) return FERHIP_E_ARG;
+    const int NM = FERHIP_NB_MBS;
+    // stream s = job order[s]: the jobs of one (op, pos) side by side, so that a launch covers a range of streams
+    std::vector<uint32_t> order(n);
+    for (size_t j = 0; j < n; j++) order[j] = (uint32_t)j;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].op * NM + jobs[a].pos < jobs[b].op * NM + jobs[b].pos; });
+    std::vector<uint8_t> Y(n * SEAM_YSZ), Cb(n * SEAM_CSZ), Cr(n * SEAM_CSZ), cbp(n * NM * 2, 0), tc(n * NM * 24, 0), i4m(n * NM * 16, 0),
+        i4f(n * NM * 16, 0), cmode(n * NM, 0), dqp(n * NM, 0), pos(n);
+    std::vector<int> mbt(n * NM, 0), qp(n), dst(n * 4, 0), mbsz(n * NM * 2, 0);
+    std::vector<uint32_t> hdr(n * 4, 0);
+    std::vector<int16_t> lev(n * NM * FER_LEVELS, 0);
+    for (size_t s = 0; s < n; s++) {
+        const ferhip_intra_job &J = jobs[order[s]];
+        const bool dec = J.op == FERHIP_INTRA_DECODE;
+        memcpy(&Y[s * SEAM_YSZ], J.Y, SEAM_YSZ);
+        memcpy(&Cb[s * SEAM_CSZ], J.Cb, SEAM_CSZ);
+        memcpy(&Cr[s * SEAM_CSZ], J.Cr, SEAM_CSZ);
+        pos[s] = (uint8_t)J.pos;
+        qp[s] = J.qp | (ferhip_chroma_qp(J.qp) << 8);
+        hdr[s * 4] = (uint32_t)J.chroma_qp_offset;
+        hdr[s * 4 + 1] = (uint32_t)J.constrained_intra;
+        hdr[s * 4 + 3] = (uint32_t)J.slice_type;
+        dst[s * 4 + 1] = NM;  // k_dec_intra: every macroblock was reached by the parser
+        for (int m = 0; m < NM; m++) {
+            const size_t mi = s * NM + m;
+            const ferhip_nb_mb &N = J.mb[m];
+            dqp[mi] = (uint8_t)J.qp;
+            if (m > J.pos) mbt[mi] = dec ? FER_P_SKIP : 0;
+            if (m >= J.pos) continue;
+            mbt[mi] = N.mb_type;
+            cbp[mi * 2] = (uint8_t)N.cbp_luma;
+            cbp[mi * 2 + 1] = (uint8_t)N.cbp_chroma;
+            for (int b = 0; b < 16; b++) {
+                tc[mi * 24 + b] = (uint8_t)N.tc_luma[b];
+                i4m[mi * 16 + b] = (uint8_t)N.i4mode[b];
+            }
+            for (int b = 0; b < 8; b++) tc[mi * 24 + 16 + b] = (uint8_t)N.tc_chroma[b >> 2][b & 3];
+        }
+        if (dec && J.pos == 3) mbt[s * NM + 2] = FER_P_SKIP;  // shares the diagonal of pos 3 and is none of its neighbours
+        const size_t mi = s * NM + J.pos;
+        mbt[mi] = J.mb[J.pos].mb_type;
+        if (!dec) continue;
+        cmode[mi] = (uint8_t)J.chroma_mode;
+        for (int b = 0; b < 16; b++) i4f[mi * 16 + b] = (uint8_t)((J.prev_flag[b] << 3) | J.rem_mode[b]);
+        int16_t *lv = &lev[mi * FER_LEVELS];
+        const bool i16 = fer_seam_is_i16(J.mb[J.pos].mb_type, J.slice_type);
+        for (int b = 0; b < 16; b++) {
+            for (int k = 0; k < (i16 ? 15 : 16); k++) lv[b * 16 + k] = (int16_t)(i16 ? J.ac16[b][k] : J.lumaLevel[b][k]);
+            if (i16) lv[FER_LV_DC16 + b] = (int16_t)J.dc16[b];
+        }
+        for (int b = 0; b < 8; b++) {
+            lv[FER_LV_CDC + b] = (int16_t)J.cdc[b >> 2][b & 3];
+            for (int k = 0; k < 15; k++) lv[FER_LV_CAC + b * 15 + k] = (int16_t)J.cac[b >> 2][b & 3][k];
+        }
+    }
+    DevBuf<uint8_t> dY, dCb, dCr, dcbp, dtc, di4m, di4f, dcm, ddqp, dpos;
+    DevBuf<int> dmbt, dqpw, ddst, dmbsz;
+    DevBuf<uint32_t> dhdr;
+    DevBuf<int16_t> dlev;
+    DevBuf<int32_t> dpred;
+    if (dY.reserve(Y.size()) || dCb.reserve(Cb.size()) || dCr.reserve(Cr.size()) || dcbp.reserve(cbp.size()) || dtc.reserve(tc.size()) ||
+        di4m.reserve(i4m.size()) || di4f.reserve(i4f.size()) || dcm.reserve(cmode.size()) || ddqp.reserve(dqp.size()) || dpos.reserve(n) ||
+        dmbt.reserve(mbt.size()) || dqpw.reserve(n) || ddst.reserve(dst.size()) || dmbsz.reserve(mbsz.size()) || dhdr.reserve(hdr.size()) ||
+        dlev.reserve(lev.size()) || dpred.reserve(n * 384))
+        return FERHIP_E_HIP;
+#define SEAM_UP(dv, hv) CK(hipMemcpy(dv, hv.data(), hv.size() * sizeof hv[0], hipMemcpyHostToDevice))
+#define SEAM_DOWN(hv, dv) CK(hipMemcpy(hv.data(), dv, hv.size() * sizeof hv[0], hipMemcpyDeviceToHost))
+    SEAM_UP(dY, Y);
+    SEAM_UP(dCb, Cb);
+    SEAM_UP(dCr, Cr);
+    SEAM_UP(dcbp, cbp);
+    SEAM_UP(dtc, tc);
+    SEAM_UP(di4m, i4m);
+    SEAM_UP(di4f, i4f);
+    SEAM_UP(dcm, cmode);
+    SEAM_UP(ddqp, dqp);
+    SEAM_UP(dpos, pos);
+    SEAM_UP(dmbt, mbt);
+    SEAM_UP(dqpw, qp);
+    SEAM_UP(ddst, dst);
+    SEAM_UP(dmbsz, mbsz);
+    SEAM_UP(dhdr, hdr);
+    SEAM_UP(dlev, lev);
+    FerDev d = {};
+    d.W = FERHIP_NB_W;
+    d.H = FERHIP_NB_H;
+    d.Wc = d.W / 2;
+    d.Hc = d.H / 2;
+    d.mbw = SEAM_MBW;
+    d.mbh = FERHIP_NB_H / 16;
+    d.nmb = NM;
+    d.S = (int)n;
+    d.ysz = SEAM_YSZ;
+    d.csz = SEAM_CSZ;
+    d.curY = dY;
+    d.curCb = dCb;
+    d.curCr = dCr;
+    d.qp = dqpw;
+    d.hdr = dhdr;
+    d.mb_type = dmbt;
+    d.cbp = dcbp;
+    d.tc = dtc;
+    d.i4mode = di4m;
+    d.i4flag = di4f;
+    d.chroma_mode = dcm;
+    d.levels = dlev;
+    d.mbsize = dmbsz;
+    d.dec_qp = ddqp;
+    d.dec_state = ddst;
+    for (size_t s0 = 0; s0 < n;) {  // one launch per (op, pos)
+        const ferhip_intra_job &J = jobs[order[s0]];
+        size_t s1 = s0 + 1;
+        while (s1 < n && jobs[order[s1]].op == J.op && jobs[order[s1]].pos == J.pos) s1++;
+        const FerDev g = seam_streams(d, (int)s0, (int)(s1 - s0));
+        const int diag = J.pos % SEAM_MBW + 2 * (J.pos / SEAM_MBW);
+        if (J.op == FERHIP_INTRA_ENCODE) {
+            fer_launch_intra_diag(g, diag, 0);
+        } else {
+            hipLaunchKernelGGL(k_seam_i4_modes, dim3((unsigned)((s1 - s0 + 63) / 64)), dim3(64), 0, 0, g, dpos.p + s0);
+            fer_launch_decode_intra_diag(g, diag, 0);
+        }
+        CK(hipGetLastError());
+        s0 = s1;
+    }
+    hipLaunchKernelGGL(k_seam_intra_pred, dim3((unsigned)n), dim3(64), 0, 0, d, dpos.p, dpred.p);
+    CK(hipGetLastError());
+    std::vector<int32_t> pred(n * 384);
+    SEAM_DOWN(Y, dY);
+    SEAM_DOWN(Cb, dCb);
+    SEAM_DOWN(Cr, dCr);
+    SEAM_DOWN(cbp, dcbp);
+    SEAM_DOWN(tc, dtc);
+    SEAM_DOWN(i4m, di4m);
+    SEAM_DOWN(i4f, di4f);
+    SEAM_DOWN(cmode, dcm);
+    SEAM_DOWN(mbt, dmbt);
+    SEAM_DOWN(mbsz, dmbsz);
+    SEAM_DOWN(lev, dlev);
+    SEAM_DOWN(pred, dpred);
+#undef SEAM_UP
+#undef SEAM_DOWN
+    for (size_t s = 0; s < n; s++) {
+        const ferhip_intra_job &J = jobs[order[s]];
+        ferhip_intra_result &R = results[order[s]];
+        memset(&R, 0, sizeof R);
+        const bool enc = J.op == FERHIP_INTRA_ENCODE;
+        const size_t mi = s * NM + J.pos;
+        const int t = mbt[mi];
+        const bool i4 = fer_seam_is_i4(t, J.slice_type);
+        R.mb_type = t;
+        R.ret = i4 ? -1 : ((J.slice_type == 2 ? t : t - 5) - 1) & 3;
+        R.chroma_mode = cmode[mi];
+        for (int b = 0; b < 16; b++) R.i4mode[b] = (enc || i4) ? i4m[mi * 16 + b] : 0;
+        const int xp = (J.pos % SEAM_MBW) << 4, yp = (J.pos / SEAM_MBW) << 4;
+        for (int i = 0; i < 256; i++) R.recY[i] = Y[s * SEAM_YSZ + (size_t)(yp + (i >> 4)) * FERHIP_NB_W + xp + (i & 15)];
+        for (int i = 0; i < 64; i++) {
+            const size_t o = s * SEAM_CSZ + (size_t)(yp / 2 + (i >> 3)) * (FERHIP_NB_W / 2) + xp / 2 + (i & 7);
+            R.recCb[i] = Cb[o];
+            R.recCr[i] = Cr[o];
+        }
+        memcpy(R.predL, &pred[s * 384], sizeof R.predL);
+        memcpy(R.predCb, &pred[s * 384 + 256], sizeof R.predCb);
+        memcpy(R.predCr, &pred[s * 384 + 320], sizeof R.predCr);
+        if (!enc) continue;
+        R.cbp_luma = cbp[mi * 2];
+        R.cbp_chroma = cbp[mi * 2 + 1];
+        R.mbsize[0] = mbsz[mi * 2];
+        R.mbsize[1] = mbsz[mi * 2 + 1];
+        for (int b = 0; b < 16; b++) {  // as the macroblock layer reads them (k_cavlc): bit 3 = the flag, bits 0..2 = rem
+            R.prev_flag[b] = (i4f[mi * 16 + b] >> 3) & 1;
+            R.rem_mode[b] = i4f[mi * 16 + b] & 7;
+            R.tc_luma[b] = tc[mi * 24 + b];
+        }
+        for (int b = 0; b < 8; b++) R.tc_chroma[b >> 2][b & 3] = tc[mi * 24 + 16 + b];
+        const int16_t *lv = &lev[mi * FER_LEVELS];
+        for (int b = 0; b < 16; b++) {
+            for (int k = 0; k < (i4 ? 16 : 15); k++) (i4 ? R.lumaLevel : R.ac16)[b][k] = lv[b * 16 + k];
+            if (!i4) R.dc16[b] = lv[FER_LV_DC16 + b];
+        }
+        for (int b = 0; b < 8; b++) {
+            R.cdc[b >> 2][b & 3] = lv[FER_LV_CDC + b];
+            for (int k = 0; k < 15; k++) R.cac[b >> 2][b & 3][k] = lv[FER_LV_CAC + b * 15 + k];
+        }
+    }
+    return 0;
+}
+
+// DeriveMVs and its inverse.  One wavefront per job: the job's neighbours go into the vector field and the type array of
+// stream j; DERIVE is dec_derive_mvs (fer_mvpred.h), scalar code run by lane 0 as k_dec_parse runs it; PREDICT is the
+// mvd step of k_p_resid -- lane i < 4 derives partition i through predict_luma_tbl from the vectors held one per lane.
+__global__ __launch_bounds__(64) void k_seam_mv(FerDev d, const ferhip_mv_job *jobs, ferhip_mv_result *res)
+{
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const ferhip_mv_job &J = jobs[j];
+    ferhip_mv_result &R = res[j];
+    const int p = J.pos, type = J.mb_type;
+    short *mvs = d.mv + (size_t)j * d.nmb * 8;
+    int *mbt = d.mb_type + (size_t)j * d.nmb;
+    if (lane < d.nmb * 8) {
+        const int m = lane >> 3;
+        short v = 0;
+        if (m < p) v = (short)J.mb[m].mv[(lane & 7) >> 1][lane & 1];
+        if (m == p && J.op == FERHIP_MV_PREDICT) v = (short)J.mv[(lane & 7) >> 1][lane & 1];
+        mvs[lane] = v;
+    }
+    if (lane < d.nmb) mbt[lane] = lane < p ? J.mb[lane].mb_type : 0;
+    __syncthreads();
+    if (J.op == FERHIP_MV_DERIVE) {
+        if (lane == 0) {
+            int mvd[4][2], sub[4];
+            for (int i = 0; i < 4; i++) {
+                mvd[i][0] = J.mvd[i][0];
+                mvd[i][1] = J.mvd[i][1];
+                sub[i] = J.sub_mb_type[i];
+            }
+            R.fits = dec_derive_mvs(d, mvs, mbt, p, type, mvd, sub) ? 1 : 0;
+            for (int k = 0; k < 8; k++) R.mv[k >> 1][k & 1] = mvs[p * 8 + k];
+        }
+        return;
+    }
+    const int mbx = p % d.mbw, mby = p / d.mbw;
+    int tbl;  // as in k_p_resid: the vectors of this macroblock and of its left / above / above-right / above-left neighbours
+    {
+        const int which = min(lane >> 2, 4), q = lane & 3;
+        const int off = which == 0 ? 0 : (which == 1 ? -1 : (which == 2 ? -d.mbw : (which == 3 ? 1 - d.mbw : -1 - d.mbw)));
+        tbl = ((const int *)mvs)[(size_t)iclamp(p + off, 0, d.nmb - 1) * 4 + q];
+    }
+    const int np = type == FER_P_L0_16x16 ? 1 : (type <= FER_P_8x16 ? 2 : 4);
+    const int i = lane & 3, pi = i < np ? i : 0;
+    const int q = (type == FER_P_16x8 && pi == 1) ? 2 : pi;  // quadrant that carries partition i's vector
+    int px, py;
+    predict_luma_tbl(tbl, d.mbw, mbx, mby, type, pi, px, py);
+    const int w = __shfl(tbl, q);
+    if (lane < 4) {
+        R.mvd[lane][0] = i < np ? (int)(short)(w & 0xffff) - px : 0;
+        R.mvd[lane][1] = i < np ? (w >> 16) - py : 0;
+        R.mv[lane][0] = J.mv[lane][0];
+        R.mv[lane][1] = J.mv[lane][1];
+    }
+    if (lane == 0) R.fits = 1;
+}
+
+extern "C" int ferhip_mv_mbs(const ferhip_mv_job *jobs, ferhip_mv_result *results, size_t n)
+{
+    if (fer_seam_check_mv_mbs(jobs, results, n)) return FERHIP_E_ARG;
+    DevBuf<ferhip_mv_job> dj;
+    DevBuf<ferhip_mv_result> dr;
+    DevBuf<short> dmv;
+    DevBuf<int> dmbt;
+    if (dj.reserve(n) || dr.reserve(n) || dmv.reserve(n * FERHIP_NB_MBS * 8) || dmbt.reserve(n * FERHIP_NB_MBS)) return FERHIP_E_HIP;
+    CK(hipMemcpy(dj, jobs, n * sizeof *jobs, hipMemcpyHostToDevice));
+    CK(hipMemset(dr, 0, n * sizeof *results));
+    FerDev d = {};
+    d.W = FERHIP_NB_W;
+    d.H = FERHIP_NB_H;
+    d.mbw = SEAM_MBW;
+    d.mbh = FERHIP_NB_H / 16;
+    d.nmb = FERHIP_NB_MBS;
+    d.S = (int)n;
+    d.mv = dmv;
+    d.mb_type = dmbt;
+    hipLaunchKernelGGL(k_seam_mv, dim3((unsigned)n), dim3(64), 0, 0, d, dj.p, dr.p);
+    CK(hipGetLastError());
+    CK(hipMemcpy(results, dr, n * sizeof *results, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -296,3 +296,69 @@ __device__ __forceinline__ void predict_luma_tbl(int tbl, int mbw, int mbx, int 
         oy = cy;
     }
 }
+
+// P macroblock vectors: PredictMV + DeriveMVs (F/mode_pred.cpp:381-482), quadrant storage; shared by k_dec_parse and the
+// neighbourhood seam (k_seam_mv, fer_mbunit.hip).  The vectors are kept as 16-bit quarter samples (a level allows +-8192);
+// false when a component does not fit: the caller refuses the picture instead of predicting from a wrapped vector (the
+// reference keeps ints)
+__device__ bool dec_derive_mvs(const FerDev &d, short *mvs, const int *mbt, int mb, int type, const int mvd[4][2], const int sub[4])
+{
+    MvCtx c;
+    c.mv = mvs;
+    c.mb_type = mbt;
+    c.mbw = d.mbw;
+    c.cur = mb;
+    c.type = type;
+    c.coh = false;
+    short *o = mvs + (size_t)mb * 8;
+    if (type == FER_P_SKIP) {
+        int mx = 0, my = 0;
+        if (!(mb < d.mbw || mb % d.mbw == 0)) {
+            int up = mb - d.mbw, lf = mb - 1;
+            bool iu = mbt[up] >= 5 && mbt[up] <= 30, il = mbt[lf] >= 5 && mbt[lf] <= 30;
+            bool zu = !iu && (mvs[(up * 4 + 2) * 2] | mvs[(up * 4 + 2) * 2 + 1]) == 0;
+            bool zl = !il && (mvs[(lf * 4 + 1) * 2] | mvs[(lf * 4 + 1) * 2 + 1]) == 0;
+            if (!(zu || zl)) predict_luma(c, 0, mx, my);
+        }
+        for (int q = 0; q < 4; q++) {
+            o[q * 2] = (short)mx;
+            o[q * 2 + 1] = (short)my;
+        }
+        return true;  // (zero, or the median of vectors that fit)
+    }
+    bool fits = true;
+    int np = type == 0 ? 1 : (type <= 2 ? 2 : 4);
+    for (int i = 0; i < np; i++) {
+        int px, py;
+        if (np == 4)
+            predict_luma_quadrant(c, i, sub, px, py);
+        else
+            predict_luma(c, i, px, py);
+        px += mvd[i][0];
+        py += mvd[i][1];
+        fits &= px == (short)px && py == (short)py;
+        // quadrants covered by partition i
+        int q0, q1, q2 = -1, q3 = -1;
+        if (np == 1) {
+            q0 = 0;
+            q1 = 1;
+            q2 = 2;
+            q3 = 3;
+        } else if (type == FER_P_16x8) {
+            q0 = i * 2;
+            q1 = i * 2 + 1;
+        } else if (type == FER_P_8x16) {
+            q0 = i;
+            q1 = i + 2;
+        } else {
+            q0 = q1 = i;
+        }
+        int qs[4] = {q0, q1, q2, q3};
+        for (int k = 0; k < 4; k++)
+            if (qs[k] >= 0) {
+                o[qs[k] * 2] = (short)px;
+                o[qs[k] * 2 + 1] = (short)py;
+            }
+    }
+    return fits;
+}

@@ -1,8 +1,9 @@
 // fer_seam_host.h -- argument checks of the per-macroblock unit-parity surface (ferhip_mb_unit, ferhip_cavlc_blocks,
-// ferhip_cavlc_parse_blocks, ferhip_residual_mbs, ferhip_mc_sub_mb_parts; fer_mbunit.hip).  The kernels behind these entry
-// points index device tables and LDS with what the caller states (QP, block and macroblock indices, nC, maxNumCoeff, bit
-// positions), so every call is checked here before its first HIP call.  Plain C++ without the HIP runtime, so that it
-// can be compiled into a stand-alone host program and run under a sanitizer (tools/seam_host_check.cpp).
+// ferhip_cavlc_parse_blocks, ferhip_residual_mbs, ferhip_mc_sub_mb_parts, ferhip_intra_mbs, ferhip_mv_mbs; fer_mbunit.hip).
+// The kernels behind these entry points index device tables and LDS with what the caller states (QP, block and macroblock
+// indices, nC, maxNumCoeff, bit positions, prediction modes), so every call is checked here before its first HIP call.
+// Plain C++ without the HIP runtime, so that it can be compiled into a stand-alone host program and run under a sanitizer
+// (tools/seam_host_check.cpp, tools/seam_nbhd_host_check.cpp).
 #pragma once
 #include "../../include/ferhip.h"
 #include <stddef.h>
@@ -100,6 +101,143 @@ static inline int fer_seam_check_residual_mbs(const ferhip_res_job *jobs, const 
         } else if (!fer_seam_levels16(&J.lumaLevel[0][0], 256) || !fer_seam_levels16(J.dc16, 16) || !fer_seam_levels16(&J.ac16[0][0], 256) ||
                    !fer_seam_levels16(&J.cdc[0][0], 8) || !fer_seam_levels16(&J.cac[0][0][0], 128)) {
             return FERHIP_E_ARG;
+        }
+    }
+    return 0;
+}
+
+// ---- the neighbourhood seam (ferhip_intra_mbs, ferhip_mv_mbs): a macroblock at pos of a 3 x 2-macroblock picture
+// neighbours that pos provides: bit 0 = A (pos - 1), 1 = B (pos - 3), 2 = C (pos - 2), 3 = D (pos - 4)
+static inline int fer_seam_pos_nb(int pos)
+{
+    static const int k[FERHIP_NB_MBS] = {0, 1, 1, 2 | 4, 1 | 2 | 4 | 8, 1 | 2 | 8};
+    return k[pos];
+}
+// mb_type in the numbering of slice_type (2 = I, 0 = P); 31 = P_Skip under either; no I_PCM
+static inline bool fer_seam_mb_type_ok(int32_t t, int32_t slice_type) { return t == 31 || fer_seam_in(t, 0, slice_type == 2 ? 24 : 29); }
+static inline bool fer_seam_is_i4(int32_t t, int32_t slice_type) { return t == (slice_type == 2 ? 0 : 5); }
+static inline bool fer_seam_is_i16(int32_t t, int32_t slice_type) { return slice_type == 2 ? fer_seam_in(t, 1, 24) : fer_seam_in(t, 6, 29); }
+static inline bool fer_seam_is_inter(int32_t t) { return fer_seam_in(t, 0, 4) || t == 31; }  // P numbering
+static inline bool fer_seam_mv16(const int32_t mv[4][2]) { return fer_seam_levels16(&mv[0][0], 8); }
+// the quadrants that one partition of an inter type covers carry one vector
+static inline bool fer_seam_mv_consistent(int32_t t, const int32_t mv[4][2])
+{
+    auto eq = [&](int a, int b) { return mv[a][0] == mv[b][0] && mv[a][1] == mv[b][1]; };
+    if (t == 0 || t == 31) return eq(0, 1) && eq(0, 2) && eq(0, 3);
+    if (t == 1) return eq(0, 1) && eq(2, 3);
+    if (t == 2) return eq(0, 2) && eq(1, 3);
+    return true;
+}
+static inline bool fer_seam_nb_ok(const ferhip_nb_mb &N, int32_t slice_type)
+{
+    if (!fer_seam_mb_type_ok(N.mb_type, slice_type) || !fer_seam_in(N.cbp_luma, 0, 15) || !fer_seam_in(N.cbp_chroma, 0, 2) || !fer_seam_mv16(N.mv))
+        return false;
+    for (int b = 0; b < 16; b++)
+        if (!fer_seam_in(N.tc_luma[b], 0, 16) || !fer_seam_in(N.i4mode[b], 0, 8)) return false;
+    for (int b = 0; b < 8; b++)
+        if (!fer_seam_in(N.tc_chroma[b >> 2][b & 3], 0, 16)) return false;
+    return true;
+}
+
+// getIntra4x4PredMode (F/intra.cpp:77-136) of a DECODE job, restated on the host only to tell whether the job is legal
+static inline void fer_seam_i4_modes(const ferhip_intra_job &J, int mode[16])
+{
+    static const int8_t nbA[16] = {5, 0, 7, 2, 1, 4, 3, 6, 13, 8, 15, 10, 9, 12, 11, 14}, nbB[16] = {10, 11, 0, 1, 14, 15, 4, 5, 2, 3, 8, 9, 6, 7, 12, 13};
+    const int nb = fer_seam_pos_nb(J.pos);
+    for (int blk = 0; blk < 16; blk++) {
+        const bool edgeA = blk == 0 || blk == 2 || blk == 8 || blk == 10, edgeB = blk == 0 || blk == 1 || blk == 4 || blk == 5;
+        int mA = 2, mB = 2;
+        if (!(edgeA && !(nb & 1)) && !(edgeB && !(nb & 2)) && !J.constrained_intra) {
+            if (edgeA) {
+                const ferhip_nb_mb &N = J.mb[J.pos - 1];
+                mA = fer_seam_is_i4(N.mb_type, J.slice_type) ? N.i4mode[nbA[blk]] : 2;
+            } else {
+                mA = mode[nbA[blk]];
+            }
+            if (edgeB) {
+                const ferhip_nb_mb &N = J.mb[J.pos - 3];
+                mB = fer_seam_is_i4(N.mb_type, J.slice_type) ? N.i4mode[nbB[blk]] : 2;
+            } else {
+                mB = mode[nbB[blk]];
+            }
+        }
+        const int pm = mA <= mB ? mA : mB, rem = J.rem_mode[blk];
+        mode[blk] = J.prev_flag[blk] ? pm : (rem < pm ? rem : rem + 1);
+    }
+}
+// a DECODE job whose prediction modes read only neighbours that pos provides (fields already in range)
+static inline bool fer_seam_intra_legal(const ferhip_intra_job &J)
+{
+    static const int8_t bx[16] = {0, 4, 0, 4, 8, 12, 8, 12, 0, 4, 0, 4, 8, 12, 8, 12}, by[16] = {0, 0, 4, 4, 0, 0, 4, 4, 8, 8, 12, 12, 8, 8, 12, 12};
+    const int nb = fer_seam_pos_nb(J.pos);
+    const bool A = (nb & 1) != 0, B = (nb & 2) != 0;
+    if ((J.chroma_mode == 1 && !A) || (J.chroma_mode == 2 && !B) || (J.chroma_mode == 3 && !(A && B))) return false;
+    const int32_t t = J.mb[J.pos].mb_type;
+    if (fer_seam_is_i16(t, J.slice_type)) {
+        const int m = ((J.slice_type == 2 ? t : t - 5) - 1) & 3;  // vertical, horizontal, DC, plane
+        return !((m == 0 && !B) || (m == 1 && !A) || (m == 3 && !(A && B)));
+    }
+    int mode[16];
+    fer_seam_i4_modes(J, mode);
+    for (int blk = 0; blk < 16; blk++) {
+        const bool left = bx[blk] > 0 || A, top = by[blk] > 0 || B;  // the corner sample exists where both do (D exists with A and B)
+        const int m = mode[blk];  // 0..8: a prediction is at most 8, and rem_mode 7 is below a prediction of 8
+        if ((m == 0 || m == 3 || m == 7) && !top) return false;
+        if ((m == 1 || m == 8) && !left) return false;
+        if ((m == 4 || m == 5 || m == 6) && !(left && top)) return false;
+    }
+    return true;
+}
+
+static inline int fer_seam_check_intra_mbs(const ferhip_intra_job *jobs, const ferhip_intra_result *results, size_t n)
+{
+    if (!jobs || !results || n == 0 || n > FER_SEAM_JOBS_MAX) return FERHIP_E_ARG;
+    for (size_t i = 0; i < n; i++) {
+        const ferhip_intra_job &J = jobs[i];
+        if (!fer_seam_in(J.op, FERHIP_INTRA_ENCODE, FERHIP_INTRA_DECODE) || !fer_seam_in(J.pos, 0, FERHIP_NB_MBS - 1) ||
+            (J.slice_type != 0 && J.slice_type != 2) || !fer_seam_in(J.qp, 0, 51) || !fer_seam_in(J.chroma_qp_offset, -12, 12) ||
+            !fer_seam_in(J.constrained_intra, 0, 1))
+            return FERHIP_E_ARG;
+        for (int m = 0; m < J.pos; m++)
+            if (!fer_seam_nb_ok(J.mb[m], J.slice_type)) return FERHIP_E_ARG;
+        const int32_t t = J.mb[J.pos].mb_type;
+        if (J.op == FERHIP_INTRA_ENCODE) {  // I slices only; mb[pos].mb_type is the stale entry of the previous picture
+            if (J.slice_type != 2 || !fer_seam_mb_type_ok(t, 2)) return FERHIP_E_ARG;
+            continue;
+        }
+        if (!fer_seam_is_i4(t, J.slice_type) && !fer_seam_is_i16(t, J.slice_type)) return FERHIP_E_ARG;
+        if (!fer_seam_in(J.chroma_mode, 0, 3)) return FERHIP_E_ARG;
+        for (int b = 0; b < 16; b++)
+            if (!fer_seam_in(J.prev_flag[b], 0, 1) || !fer_seam_in(J.rem_mode[b], 0, 7)) return FERHIP_E_ARG;
+        if (!fer_seam_levels16(&J.lumaLevel[0][0], 256) || !fer_seam_levels16(J.dc16, 16) || !fer_seam_levels16(&J.ac16[0][0], 256) ||
+            !fer_seam_levels16(&J.cdc[0][0], 8) || !fer_seam_levels16(&J.cac[0][0][0], 128))
+            return FERHIP_E_ARG;
+        if (!fer_seam_intra_legal(J)) return FERHIP_E_ARG;
+    }
+    return 0;
+}
+
+#define FER_SEAM_MVD_MAX 65536
+static inline int fer_seam_check_mv_mbs(const ferhip_mv_job *jobs, const ferhip_mv_result *results, size_t n)
+{
+    if (!jobs || !results || n == 0 || n > FER_SEAM_JOBS_MAX) return FERHIP_E_ARG;
+    for (size_t i = 0; i < n; i++) {
+        const ferhip_mv_job &J = jobs[i];
+        if (!fer_seam_in(J.op, FERHIP_MV_DERIVE, FERHIP_MV_PREDICT) || !fer_seam_in(J.pos, 0, FERHIP_NB_MBS - 1)) return FERHIP_E_ARG;
+        const bool predict = J.op == FERHIP_MV_PREDICT;
+        if (!(predict ? fer_seam_in(J.mb_type, 0, 4) : fer_seam_is_inter(J.mb_type))) return FERHIP_E_ARG;
+        for (int k = 0; k < 4; k++)
+            if (!fer_seam_in(J.sub_mb_type[k], 0, predict ? 0 : 3)) return FERHIP_E_ARG;
+        for (int m = 0; m < J.pos; m++) {  // of a neighbour, mb_type and mv are read (P numbering)
+            const ferhip_nb_mb &N = J.mb[m];
+            if (!fer_seam_mb_type_ok(N.mb_type, 0) || !fer_seam_mv16(N.mv)) return FERHIP_E_ARG;
+            if (fer_seam_is_inter(N.mb_type) ? !fer_seam_mv_consistent(N.mb_type, N.mv) : predict) return FERHIP_E_ARG;
+        }
+        if (predict) {
+            if (!fer_seam_mv16(J.mv) || !fer_seam_mv_consistent(J.mb_type, J.mv)) return FERHIP_E_ARG;
+        } else {
+            for (int k = 0; k < 8; k++)
+                if (!fer_seam_in(J.mvd[k >> 1][k & 1], -FER_SEAM_MVD_MAX, FER_SEAM_MVD_MAX)) return FERHIP_E_ARG;
         }
     }
     return 0;

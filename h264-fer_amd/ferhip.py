@@ -749,6 +749,100 @@ def residual_mbs(jobs):
     return out
 
 
+# ---- the neighbourhood seam (ferhip_intra_mbs, ferhip_mv_mbs): one macroblock at `pos` of a 3 x 2-macroblock picture
+INTRA_ENCODE, INTRA_DECODE = 0, 1
+MV_DERIVE, MV_PREDICT = 0, 1
+NB_W, NB_H, NB_MBS = 48, 32, 6
+
+
+class NbMb(C.Structure):
+    """ferhip_nb_mb of include/ferhip.h: the side information of one macroblock of the little picture"""
+    _fields_ = [("mb_type", C.c_int32), ("cbp_luma", C.c_int32), ("cbp_chroma", C.c_int32), ("tc_luma", C.c_int32 * 16), ("tc_chroma", C.c_int32 * 8),
+                ("i4mode", C.c_int32 * 16), ("mv", C.c_int32 * 8)]
+
+
+class IntraJob(C.Structure):
+    """ferhip_intra_job of include/ferhip.h"""
+    _fields_ = [("op", C.c_int32), ("pos", C.c_int32), ("slice_type", C.c_int32), ("qp", C.c_int32), ("chroma_qp_offset", C.c_int32),
+                ("constrained_intra", C.c_int32), ("chroma_mode", C.c_int32), ("prev_flag", C.c_int32 * 16), ("rem_mode", C.c_int32 * 16),
+                ("mb", NbMb * NB_MBS), ("Y", C.c_uint8 * (NB_W * NB_H)), ("Cb", C.c_uint8 * (NB_W * NB_H // 4)), ("Cr", C.c_uint8 * (NB_W * NB_H // 4))] + _RES_LEVELS
+
+
+class IntraResult(C.Structure):
+    _fields_ = [("ret", C.c_int32), ("mb_type", C.c_int32), ("cbp_luma", C.c_int32), ("cbp_chroma", C.c_int32), ("chroma_mode", C.c_int32),
+                ("mbsize", C.c_int32 * 2), ("i4mode", C.c_int32 * 16), ("prev_flag", C.c_int32 * 16), ("rem_mode", C.c_int32 * 16),
+                ("tc_luma", C.c_int32 * 16), ("tc_chroma", C.c_int32 * 8)] + _RES_LEVELS + [
+                    ("recY", C.c_int32 * 256), ("recCb", C.c_int32 * 64), ("recCr", C.c_int32 * 64),
+                    ("predL", C.c_int32 * 256), ("predCb", C.c_int32 * 64), ("predCr", C.c_int32 * 64)]
+
+
+class MvJob(C.Structure):
+    """ferhip_mv_job of include/ferhip.h"""
+    _fields_ = [("op", C.c_int32), ("pos", C.c_int32), ("mb_type", C.c_int32), ("sub_mb_type", C.c_int32 * 4), ("mvd", C.c_int32 * 8), ("mv", C.c_int32 * 8),
+                ("mb", NbMb * NB_MBS)]
+
+
+class MvResult(C.Structure):
+    _fields_ = [("mv", C.c_int32 * 8), ("mvd", C.c_int32 * 8), ("fits", C.c_int32)]
+
+
+def _set_fields(st, fields):
+    """a dict into a ctypes structure: scalars and arrays by field name; mb = a list of dicts (or None) per macroblock"""
+    for name, val in fields.items():
+        if name == "mb":
+            for m, nb in enumerate(val):
+                if nb:
+                    _set_fields(st.mb[m], nb)
+        elif isinstance(val, (int, np.integer, bool)):
+            setattr(st, name, int(val))
+        else:
+            fld = getattr(st, name)
+            a = np.ascontiguousarray(val, np.uint8 if fld._type_ is C.c_uint8 else np.int32).reshape(-1)
+            if a.nbytes != C.sizeof(fld):
+                raise FerHipError(f"{name}: {a.size} elements for a field of {len(fld)}")
+            C.memmove(fld, a.ctypes.data, a.nbytes)
+
+
+def _get_fields(st):
+    out = {}
+    for name, ct in st._fields_:
+        v = getattr(st, name)
+        out[name] = int(v) if ct is C.c_int32 else np.frombuffer(v, np.int32).copy()
+    return out
+
+
+def nbhd_jobs(jobs, mv=False):
+    """a list of dicts -> a ferhip_intra_job (or, mv = True, ferhip_mv_job) array"""
+    J = ((MvJob if mv else IntraJob) * len(jobs))()
+    for k, j in enumerate(jobs):
+        _set_fields(J[k], j)
+    return J
+
+
+def intra_mbs(jobs):
+    """ferhip_intra_mbs: jobs = list of dicts with the fields of ferhip_intra_job (Y [32][48], Cb, Cr [16][24] uint8; mb = a list
+    of up to six dicts of the fields of ferhip_nb_mb, or None) -> list of dicts of the fields of ferhip_intra_result"""
+    lib = load_library()
+    n = len(jobs)
+    J = nbhd_jobs(jobs)
+    R = (IntraResult * n)()
+    lib.ferhip_intra_mbs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    _chk(lib.ferhip_intra_mbs(J, R, n), "ferhip_intra_mbs")
+    return [_get_fields(R[k]) for k in range(n)]
+
+
+def mv_mbs(jobs):
+    """ferhip_mv_mbs: jobs = list of dicts with the fields of ferhip_mv_job -> list of dicts: mv [8], mvd [8] (x, y per
+    quadrant / partition), fits"""
+    lib = load_library()
+    n = len(jobs)
+    J = nbhd_jobs(jobs, mv=True)
+    R = (MvResult * n)()
+    lib.ferhip_mv_mbs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    _chk(lib.ferhip_mv_mbs(J, R, n), "ferhip_mv_mbs")
+    return [_get_fields(R[k]) for k in range(n)]
+
+
 def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5, flags=None):
     """ferhip_frame_nal_blocks on a list of payloads (bytes or uint8 arrays) -> (return code, out [cap] pre-filled with
     `fill`, index [n + 1] of dtype AU).  cap None = room for every payload with every second byte escaped.

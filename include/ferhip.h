@@ -774,10 +774,92 @@ typedef struct {
     uint8_t bits[FERHIP_RES_BITS_MAX];    /* WRITE: out, MSB first */
 } ferhip_res_result;
 int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result *results, size_t njobs);
-/* All five entry points of this surface check their arguments before the first HIP call and return FERHIP_E_ARG for a null
+/* ---- the neighbourhood seam: intra prediction and motion-vector derivation of one macroblock among its neighbours.
+ * A job carries a picture of 3 x 2 macroblocks (48 x 32 luma, two 24 x 16 chroma planes), the smallest in which a macroblock
+ * can have every neighbour the rules read -- A (left), B (above), C (above right), D (above left) --, and pos, the address
+ * of its macroblock in that picture.  Which neighbours exist follows from pos exactly as in a real picture:
+ *     pos 0: none    1: A    2: A (last column)    3: B, C    4: A, B, C, D    5: A, B, D (no C: last column)
+ * Job j is stream j of a context of such pictures over a hand-built FerDev, so the job runs the device code a real picture
+ * runs: k_intra_mb, k_dec_intra, dec_i4_modes, dec_derive_mvs, predict_luma_tbl.  mb[m] is the side information of
+ * macroblock m of the little picture; only the entries in front of pos (raster order) are read, plus mb[pos] where stated.
+ * mb_type is in the numbering of the job's slice_type (I: 0 I_4x4, 1..24 Intra16x16; P: 0..4 inter, 5 I_4x4, 6..29
+ * Intra16x16) or 31, P_Skip, under either; I_PCM is not part of the surface.  mv holds one vector per 8x8 quadrant in quarter
+ * samples, as the decoder and the encoder keep them: the quadrants that one partition of mb_type covers carry its vector.
+ * What this surface cannot reach: a picture ONE macroblock wide, where B exists without C and D and the macroblock is in
+ * the first and the last column at once; that stays with the whole pictures of tests/test_gpu_hard_content.py. */
+typedef struct {
+    int32_t mb_type;
+    int32_t cbp_luma, cbp_chroma;         /* 0..15, 0..2 */
+    int32_t tc_luma[16], tc_chroma[2][4]; /* TotalCoeff, 0..16 */
+    int32_t i4mode[16];                   /* Intra4x4PredMode, 0..8 (read where mb_type is I_4x4) */
+    int32_t mv[4][2];                     /* (x, y) of quadrant 0..3, each within 16 bits (read where mb_type is inter) */
+} ferhip_nb_mb;
+#define FERHIP_NB_W 48
+#define FERHIP_NB_H 32
+#define FERHIP_NB_MBS 6
+
+/* FERHIP_INTRA_ENCODE = intraPredictionEncoding (F/intra.cpp:949) and the tail of RBSP_encode for an I macroblock
+ * (F/rbsp_encoding.cpp:194-219): slice_type must be 2.  In: the picture with the source at pos and the reconstruction
+ * elsewhere, qp, mb[pos].mb_type = the stale mb_type_array entry the first coded_mb_size call reads (see
+ * FERHIP_BUF_MBSIZE: 31, a P_Skip left by the previous picture, changes the size estimate), the neighbours in front of pos.
+ * The body is k_intra_mb.  Out: ret = what the function returns (the Intra16x16 mode 0..3, or -1 for Intra4x4), i4mode,
+ * chroma_mode, mbsize = the two coded_mb_size values (F/rbsp_encoding.cpp:330; [0] the Intra16x16, [1] the Intra4x4
+ * alternative: the only two the reference ever asks for), the final mb_type, cbp, tc (the non-zero levels of every block's
+ * list; Intra16x16: of its AC list), the levels (lumaLevel for Intra4x4, dc16 and ac16 for Intra16x16, cdc, cac; the others
+ * zero), the reconstructed macroblock, predL / predCb / predCr as the function leaves them (evaluated by the decode-side
+ * predictors on the reconstruction), and prev_flag / rem_mode as the macroblock layer writes them.
+ * FERHIP_INTRA_DECODE = intraPrediction (F/intra.cpp:770) with getIntra4x4PredMode, in an I or a P slice (slice_type 2 or
+ * 0), and the reconstruction of the macroblock.  In: mb[pos].mb_type (intra), prev_flag, rem_mode, chroma_mode,
+ * constrained_intra, qp, chroma_qp_offset (-12..12), the levels (within 16 bits), the picture (the macroblock's own samples
+ * are ignored), the neighbours in front of pos.  The body is dec_i4_modes followed by k_dec_intra.  Out: i4mode (Intra4x4),
+ * predL / predCb / predCr, the reconstructed macroblock; ret, mb_type, chroma_mode repeat the input, the rest is zero.
+ * Jobs are legal only: a prediction mode that reads a neighbour pos does not provide is refused with FERHIP_E_ARG (what the
+ * decoder does with such modes is pinned on whole pictures, tests/test_gpu_decode_illegal.py). */
+#define FERHIP_INTRA_ENCODE 0
+#define FERHIP_INTRA_DECODE 1
+typedef struct {
+    int32_t op, pos, slice_type, qp, chroma_qp_offset, constrained_intra;
+    int32_t chroma_mode, prev_flag[16], rem_mode[16];                             /* DECODE: in */
+    ferhip_nb_mb mb[FERHIP_NB_MBS];
+    uint8_t Y[FERHIP_NB_H][FERHIP_NB_W], Cb[FERHIP_NB_H / 2][FERHIP_NB_W / 2], Cr[FERHIP_NB_H / 2][FERHIP_NB_W / 2];
+    int32_t lumaLevel[16][16], dc16[16], ac16[16][16], cdc[2][4], cac[2][4][16]; /* DECODE: in (layouts of ferhip_mb_job) */
+} ferhip_intra_job;
+typedef struct {
+    int32_t ret, mb_type, cbp_luma, cbp_chroma, chroma_mode, mbsize[2];
+    int32_t i4mode[16], prev_flag[16], rem_mode[16];
+    int32_t tc_luma[16], tc_chroma[2][4];
+    int32_t lumaLevel[16][16], dc16[16], ac16[16][16], cdc[2][4], cac[2][4][16];
+    int32_t recY[256], recCb[64], recCr[64];
+    int32_t predL[256], predCb[64], predCr[64];
+} ferhip_intra_result;
+int ferhip_intra_mbs(const ferhip_intra_job *jobs, ferhip_intra_result *results, size_t njobs);
+
+/* FERHIP_MV_DERIVE = DeriveMVs (F/mode_pred.cpp:428) in a P slice, through the decoder's dec_derive_mvs.  In: pos, mb_type
+ * (0..4, or 31 P_Skip), sub_mb_type (0..3, read for mb_type 3 and 4), mvd (the vector difference of partition i, for P_8x8
+ * of the first sub-partition of quadrant i; |mvd| <= 65536), the neighbours' mb_type and mv.  Out: mv, and fits = 0 when a
+ * component leaves 16 bits: the device keeps vectors in 16 bits and refuses the picture there, the reference keeps ints
+ * (mv is then undefined).
+ * FERHIP_MV_PREDICT = the encoder's direction: given the macroblock's final mv and mb_type (0..4; the quadrants of one
+ * partition equal, sub_mb_type 0, every neighbour inter, as in the encoder's P pictures), the mvd that k_p_resid writes,
+ * through its predictor predict_luma_tbl.  Out: mvd (zero behind the last partition).  DERIVE of it gives mv back. */
+#define FERHIP_MV_DERIVE 0
+#define FERHIP_MV_PREDICT 1
+typedef struct {
+    int32_t op, pos, mb_type, sub_mb_type[4];
+    int32_t mvd[4][2]; /* DERIVE: in */
+    int32_t mv[4][2];  /* PREDICT: in */
+    ferhip_nb_mb mb[FERHIP_NB_MBS];
+} ferhip_mv_job;
+typedef struct {
+    int32_t mv[4][2], mvd[4][2], fits;
+} ferhip_mv_result;
+int ferhip_mv_mbs(const ferhip_mv_job *jobs, ferhip_mv_result *results, size_t njobs);
+
+/* All seven entry points of this surface check their arguments before the first HIP call and return FERHIP_E_ARG for a null
  * pointer, n == 0, max_num_coeff outside {4, 15, 16}, nC < -1, nC == -1 with max_num_coeff != 4, an op, cls, blk, qp, qpc,
  * cbp, avail, sub / part index or macroblock address out of range, a bit_pos at or behind 8 * nbytes, nbytes == 0 or above
- * its limit. */
+ * its limit; the two calls of the neighbourhood seam also for a pos, slice_type, chroma_qp_offset, mb_type, tc, prediction
+ * mode, flag, sub type or vector out of range, for levels outside 16 bits and for a job that is not legal. */
 /* MotionCompensateSubMBPart(predL, predCr, predCb, refPic, mbPartIdx, subMbIdx, subMbPartIdx) (F/mocomp.cpp:152) for n
  * sub-blocks of one reference picture (host I420, width x height): desc[n][5] = macroblock address, subMbIdx, subMbPartIdx,
  * mvx, mvy (quarter samples); predL[n][16] = the 4x4 luma block, predCb / predCr[n][4] = the 2x2 chroma blocks (raster).

@@ -18,6 +18,8 @@
  *   LoadY4MHeader / ReadFromY4M / writeToY4M / writeToYUV, FILE *yuvinput, *yuvoutput        F/fileIO.h
  *   forwardResidual, transformScan, forwardDCLumaIntra, forwardDCChroma                      F/quantizationTransform.h
  *   transformInverseScan, inverseResidual, InverseDCLumaIntra, InverseDCChroma               F/scaleTransform.h
+ *   the per-macroblock functions (quantizationTransform ... residual_write, intraPredictionEncoding, intraPrediction,
+ *   DeriveMVs): see "per-macroblock entry points" below
  *
  * Contract kept from F/rbsp_encoding.cpp:119-326: nal_unit_type 7 / 8 write SPS / PPS (the SPS
  * call also sizes the encoder from frame.Lwidth x frame.Lheight); 5 / 1 encode the picture in
@@ -131,13 +133,46 @@ extern int totalcoeff_array_luma[FERHIP_LEGACY_MAX_MBS][16], totalcoeff_array_ch
 void residual_block_cavlc(int coeffLevel[16], int startIdx, int endIdx, int maxNumCoeff); /* F/residual.cpp:1069 */
 void residual_write(void);                                                                 /* :300 */
 void residual(int startIdx, int endIdx);                                                   /* :959 */
+/* ---- intra prediction and motion-vector derivation of one macroblock among its neighbours (ferhip_intra_mbs,
+ * ferhip_mv_mbs of ferhip.h).  The shims cut the 3 x 2-macroblock neighbourhood of CurrMbAddr out of `frame` and of the
+ * state arrays -- mb_type_array, CodedBlockPatternLumaArray / ChromaArray, totalcoeff_array_*, Intra4x4PredMode, mvL0x /
+ * mvL0y -- and place the macroblock where it has exactly the neighbours it has in `frame`.  AllocateMemory sizes
+ * Intra4x4PredMode ([macroblock << 4 | luma4x4BlkIdx]) and refIdxL0 ([macroblock]) from `frame` as well.
+ * `unsigned char` stands for the reference's bool; ferhip_legacy_constrained_intra_pred = pps.constrained_intra_pred_flag.
+ *   intraPredictionEncoding (F/intra.cpp:949), an I slice: `frame` holds the source at CurrMbAddr and the reconstruction
+ *     around it, QPy the QP, mb_type_array[CurrMbAddr] the entry of the previous picture (the first coded_mb_size reads it).
+ *     Returns the Intra16x16 mode or -1 (Intra4x4) and sets Intra4x4PredMode, intra_chroma_pred_mode, the flags and rem
+ *     modes, the predictions and mb_type_array[CurrMbAddr] = 0; for -1 the luma of `frame` is the reconstruction and LumaLevel
+ *     holds its levels.  ferhip_legacy_mbsize[2] = the two coded_mb_size values (F/rbsp_encoding.cpp:330) the function asked
+ *     for: of the Intra16x16 and of the Intra4x4 alternative.
+ *   intraPrediction (F/intra.cpp:770) with getIntra4x4PredMode, an I or P slice (ferhip_legacy_slice_type): mb_type, the
+ *     flags and rem modes, intra_chroma_pred_mode, for Intra4x4 LumaLevel and QPy in; the predictions and, for Intra4x4,
+ *     Intra4x4PredMode and the luma of `frame` out.  A mode that reads a neighbour the macroblock does not have is refused.
+ *   DeriveMVs (F/mode_pred.cpp:428): mb_type (0..4, 31), sub_mb_type, mvd_l0[mbPartIdx][0] in; mvL0x / mvL0y [CurrMbAddr]
+ *     and refIdxL0[CurrMbAddr] = 0 out.  A vector that leaves 16 bits is refused (the device keeps 16 bits).
+ *   ClearMVD (F/mode_pred.cpp:41): mvd_l0 = 0.
+ * For a `frame` one macroblock wide -- B without C and D, first and last column at once: no macroblock of a 3 x 2
+ * neighbourhood is like that -- the three shims print the message and return (intraPredictionEncoding: 0). */
+extern int *Intra4x4PredMode, *refIdxL0;
+extern int intra_chroma_pred_mode;
+extern unsigned char prev_intra4x4_pred_mode_flag[16];
+extern int rem_intra4x4_pred_mode[16];
+extern int mvd_l0[4][4][2];
+extern int sub_mb_type[4];
+extern int ferhip_legacy_constrained_intra_pred;
+extern int ferhip_legacy_mbsize[2];
+int intraPredictionEncoding(int predL[16][16], int predCr[8][8], int predCb[8][8]); /* F/intra.cpp:949 */
+void intraPrediction(int predL[16][16], int predCr[8][8], int predCb[8][8]);        /* :770 */
+void DeriveMVs(void);                                                               /* F/mode_pred.cpp:428 */
+void ClearMVD(void);                                                                /* :41 */
 /* Every shim above that takes CurrMbAddr checks it first: against the macroblocks of `frame`, or, where it indexes what
  * AllocateMemory sized, against the macroblock count of the last AllocateMemory.
- * What has no stand-alone shim: DeriveMVs / ClearMVD (F/mode_pred.cpp), per-macroblock interEncoding, coded_mb_size
- * (F/rbsp_encoding.cpp:330) and intraPrediction / intraPredictionEncoding (F/intra.cpp:770,949).  The device form of the
- * last three is the body of k_intra_mb or a whole-picture search, which needs the reconstructed neighbourhood of a whole
- * picture; their unit parity is checked on every macroblock of a picture through ferhip_read_buffer(FERHIP_BUF_MBSIZE) and
- * the motion-search lists. */
+ * What has no stand-alone shim, and why:
+ *   - coded_mb_size (F/rbsp_encoding.cpp:330) under its own name: its value for arbitrary caller-made predictions is not
+ *     something any kernel computes.  The two values the reference ever asks for -- inside intraPredictionEncoding -- are
+ *     ferhip_legacy_mbsize[2] (mbsize[2] of ferhip_intra_result).
+ *   - per-macroblock interEncoding: the serial chain k_me_resolve is not given a second entry; the lists it searches are
+ *     pinned against the reference's, one 8x8 partition at a time, by tests/test_gpu_me_lists.py. */
 
 #ifdef __cplusplus
 }
