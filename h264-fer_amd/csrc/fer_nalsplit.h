@@ -1,5 +1,5 @@
 // fer_nalsplit.h -- the NAL splitters on the device (fer_nalsplit.hip: Annex-B and length-prefixed ranges) as the live
-// decoder drives them (fer_decode_host.hip): byte ranges in device memory -> a table of NAL units and their RBSP in one
+// decoder drives them (fer_decode_live.hip): byte ranges in device memory -> a table of NAL units and their RBSP in one
 // device store.
 #pragma once
 #include "fer_ctx.h"
@@ -70,7 +70,7 @@ inline void fer_split_free(FerSplit &sp)
     new (&sp) FerSplit();
 }
 
-// The empty-payload cut of split_stream (fer_decode_host.hip), which the device leaves to the host: a unit with bytes == 0
+// The empty-payload cut of split_stream (fer_dec_syntax_host.h), which the device leaves to the host: a unit with bytes == 0
 // ends its range, and the later units of that range are skipped.  f(k, unit) for every entry k of the last job's table that
 // stays, in table order, until one returns non-zero; returns that value, or 0.
 template <typename F>

@@ -1,4 +1,4 @@
-"""NumPy model of the decoder's Annex-B splitter (split_stream, csrc/fer_decode_host.hip) as a set of local predicates, the
+"""NumPy model of the decoder's Annex-B splitter (split_stream, csrc/fer_dec_syntax_host.h) as a set of local predicates, the
 layout the device splitter (csrc/fer_nalsplit.hip) gives its output, and the corpus that pins both.
 
 For a range s[0..n):

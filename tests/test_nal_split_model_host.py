@@ -1,4 +1,4 @@
-"""tests/nal_split_model.py against a byte loop that restates split_stream (csrc/fer_decode_host.hip) line by line, on the
+"""tests/nal_split_model.py against a byte loop that restates split_stream (csrc/fer_dec_syntax_host.h) line by line, on the
 model's whole corpus, and against the framing model: a framed payload splits into exactly that payload."""
 import nal_model
 import nal_split_model as sm
