@@ -1,5 +1,6 @@
 // fer_ctx.h -- the context of libferhip and the owners of its resources, for the host translation units that drive it
-// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, fer_mbunit.hip).
+// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
+// fer_mbunit.hip, every buffer of which is a DevBuf).
 #pragma once
 #include "fer_internal.h"
 #include <stdio.h>

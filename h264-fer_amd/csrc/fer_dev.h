@@ -7,6 +7,7 @@
 // F/residual.cpp:10-17, F/moestimation.cpp:21-27).  F/ = fer_h264/fer_h264/ of the
 // reference tree.
 #pragma once
+#include "fer_levels.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,10 +35,6 @@
 #define FER_BRANGE_MIN 1024  // buckets with more positions than this get feature ranges (FerDev.brange)
 #define FER_ST2_CAP 384  // stage-2 candidates kept per 8x8 partition
 #define FER_BIG_SLICE 1024  // records of one bucket inside a partition's column range beyond which k_me_walk bounds instead of reading
-#define FER_LEVELS 400   // int16 per MB: luma 16x16, dc16 16, cdc 2x4, cac 2x4x15
-#define FER_LV_DC16 256
-#define FER_LV_CDC 272
-#define FER_LV_CAC 280
 
 // Rate control of one stream (ferhip_set_rate, k_rc_plan in fer_rate.hip).  FerRcPar is the host's setting, uploaded with the
 // picture's slice headers after every change; FerRcState lives on the device only.

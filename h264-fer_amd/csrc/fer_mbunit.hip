@@ -15,16 +15,16 @@
 //   DeriveMVs and the encoder's mvd             F/mode_pred.cpp:428                   k_seam_mv
 //   forward / inverse residual, DC, scan        F/quantizationTransform.h, scaleTransform.h  k_block_kat
 // Not a fast path: one wavefront (or thread) per job, records of plain int32.  Every entry point checks its arguments
-// (fer_seam_host.h) before its first HIP call.  The legacy-name shims are in fer_legacy.hip.
+// (fer_seam_host.h) before its first HIP call and keeps its device memory in DevBuf (fer_ctx.h); the hand-built FerDev of the
+// neighbour-aware ones is packed by fer_seam_pack_host.h and held by SeamDev.  The legacy-name shims are in fer_legacy.hip.
 #include "fer_cavlc_dev.h"
 #include "fer_ctx.h"
 #include "fer_decode_dev.h"
 #include "fer_intra_dev.h"
 #include "fer_mvpred.h"
-#include "fer_seam_host.h"
+#include "fer_seam_pack_host.h"
 
-#include <algorithm>
-#include <string.h>
+static_assert(SEAM_P_SKIP == FER_P_SKIP, "fer_seam_pack_host.h restates it");
 
 // list[k] = c[zig-zag k] (transformScan, F/quantizationTransform.cpp:310-325); the Intra16x16AC / chroma AC form drops the DC
 __device__ __forceinline__ void mbu_scan(const int c[16], int32_t *list, bool ac)
@@ -196,22 +196,15 @@ __global__ __launch_bounds__(64) void k_mb_unit(const ferhip_mb_job *jobs, ferhi
 extern "C" int ferhip_mb_unit(const ferhip_mb_job *jobs, ferhip_mb_result *results, size_t n)
 {
     if (fer_seam_check_mb_unit(jobs, results, n)) return FERHIP_E_ARG;
-    ferhip_mb_job *dj = nullptr;
-    ferhip_mb_result *dr = nullptr;
-    auto body = [&]() -> int {
-        CK(hipMalloc((void **)&dj, n * sizeof *dj));
-        CK(hipMalloc((void **)&dr, n * sizeof *dr));
-        CK(hipMemcpy(dj, jobs, n * sizeof *dj, hipMemcpyHostToDevice));
-        CK(hipMemset(dr, 0, n * sizeof *dr));
-        hipLaunchKernelGGL(k_mb_unit, dim3((unsigned)n), dim3(64), 0, 0, dj, dr, (int)n);
-        CK(hipGetLastError());
-        CK(hipMemcpy(results, dr, n * sizeof *dr, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    hipFree(dj);
-    hipFree(dr);
-    return rc;
+    DevBuf<ferhip_mb_job> dj;
+    DevBuf<ferhip_mb_result> dr;
+    if (dj.reserve(n) || dr.reserve(n)) return FERHIP_E_HIP;
+    CK(hipMemcpy(dj, jobs, n * sizeof *jobs, hipMemcpyHostToDevice));
+    CK(hipMemset(dr, 0, n * sizeof *results));
+    hipLaunchKernelGGL(k_mb_unit, dim3((unsigned)n), dim3(64), 0, 0, dj.p, dr.p, (int)n);
+    CK(hipGetLastError());
+    CK(hipMemcpy(results, dr, n * sizeof *results, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- residual_block_cavlc_write / _size for n blocks: the device block coder of the entropy pass and of coded_mb_size
@@ -246,43 +239,27 @@ extern "C" int ferhip_cavlc_blocks(const int32_t *coef, const int32_t *nC, const
                                    uint32_t *nbits, int32_t *total_coeff)
 {
     if (fer_seam_check_cavlc_blocks(coef, nC, max_num_coeff, n, bits, nbits, total_coeff)) return FERHIP_E_ARG;
-    int32_t *dc = nullptr, *dn = nullptr, *dm = nullptr, *dt = nullptr;
-    uint32_t *db = nullptr, *dl = nullptr, *ds = nullptr;
+    DevBuf<int32_t> dc, dn, dm, dt;
+    DevBuf<uint32_t> db, dl, ds;
     std::vector<uint32_t> sz(n);
-    auto body = [&]() -> int {
-        CK(hipMalloc((void **)&dc, n * 64));
-        CK(hipMalloc((void **)&dn, n * 4));
-        CK(hipMalloc((void **)&dm, n * 4));
-        CK(hipMalloc((void **)&dt, n * 4));
-        CK(hipMalloc((void **)&db, n * 64));
-        CK(hipMalloc((void **)&dl, n * 4));
-        CK(hipMalloc((void **)&ds, n * 4));
-        CK(hipMemcpy(dc, coef, n * 64, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dn, nC, n * 4, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dm, max_num_coeff, n * 4, hipMemcpyHostToDevice));
-        CK(hipMemset(db, 0, n * 64));
-        hipLaunchKernelGGL(k_cavlc_blocks, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, dc, dn, dm, (int)n, db, dl, dt, ds);
-        CK(hipGetLastError());
-        CK(hipMemcpy(bits, db, n * 64, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(nbits, dl, n * 4, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(total_coeff, dt, n * 4, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(sz.data(), ds, n * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; i++)
-            if (sz[i] != nbits[i]) {
-                fprintf(stderr, "ferhip_cavlc_blocks: block %zu: the counting form gives %u bits, the writer %u\n", i, sz[i], nbits[i]);
-                return FERHIP_E_DEVICE;
-            }
-        return 0;
-    };
-    const int rc = body();
-    hipFree(dc);
-    hipFree(dn);
-    hipFree(dm);
-    hipFree(dt);
-    hipFree(db);
-    hipFree(dl);
-    hipFree(ds);
-    return rc;
+    if (dc.reserve(n * 16) || dn.reserve(n) || dm.reserve(n) || dt.reserve(n) || db.reserve(n * 16) || dl.reserve(n) || ds.reserve(n))
+        return FERHIP_E_HIP;
+    CK(hipMemcpy(dc, coef, n * 64, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dn, nC, n * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dm, max_num_coeff, n * 4, hipMemcpyHostToDevice));
+    CK(hipMemset(db, 0, n * 64));
+    hipLaunchKernelGGL(k_cavlc_blocks, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, dc.p, dn.p, dm.p, (int)n, db.p, dl.p, dt.p, ds.p);
+    CK(hipGetLastError());
+    CK(hipMemcpy(bits, db, n * 64, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(nbits, dl, n * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(total_coeff, dt, n * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(sz.data(), ds, n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++)
+        if (sz[i] != nbits[i]) {
+            fprintf(stderr, "ferhip_cavlc_blocks: block %zu: the counting form gives %u bits, the writer %u\n", i, sz[i], nbits[i]);
+            return FERHIP_E_DEVICE;
+        }
+    return 0;
 }
 
 // ---- the parse direction.  dec_block is wave-uniform (fer_decode_dev.h), so the unit of work is a wavefront; the SEAM_PW
@@ -341,7 +318,7 @@ extern "C" int ferhip_cavlc_parse_blocks(const uint8_t *bits, size_t nbytes, con
     DevBuf<uint64_t> dpos;
     DevBuf<int32_t> dn, dm, dc, dt;
     DevBuf<uint32_t> du;
-    const size_t padded = ((nbytes + 3) & ~(size_t)3) + 16;  // what DecBits asks for: hipMalloc aligns, the tail is zero
+    const size_t padded = ((nbytes + 3) & ~(size_t)3) + 16;  // what DecBits asks for: the buffer is aligned, the tail is zero
     if (dbits.reserve(padded) || dpos.reserve(n) || dn.reserve(n) || dm.reserve(n) || dc.reserve(n * 16) || dt.reserve(n) || du.reserve(n))
         return FERHIP_E_HIP;
     const DecLuts *luts = dec_luts(0);
@@ -475,12 +452,35 @@ __global__ __launch_bounds__(64 * SEAM_PW) void k_residual_parse(const ferhip_re
     }
 }
 
-static int count_nz(const int32_t *v, int n)
-{
-    int c = 0;
-    for (int i = 0; i < n; i++) c += v[i] != 0;
-    return c;
-}
+// The hand-built context on the device: one buffer per array of SEAM_ARRAYS (fer_seam_pack_host.h) in use, and the FerDev
+// over them.  Sizes, copies and the offsets of a stream range all come from that table.
+struct __attribute__((visibility("hidden"))) SeamDev {
+#define X(n, T, per, e) DevBuf<T> n;
+    SEAM_ARRAYS(X)
+#undef X
+    int reserve(size_t S, int nmb, unsigned use)
+    {
+        return seam_each(*this, [&](int a, auto &b) { return (use >> a & 1) ? b.reserve(S * seam_stride(a, nmb)) : 0; });
+    }
+    int copy(SeamHost &h, unsigned which, bool up)  // the arrays in `which`: host to device, or back
+    {
+        return seam_each(*this, h, [&](int a, auto &b, auto &v) {
+            if ((which >> a & 1) && up) CK(hipMemcpy(b, v.data(), v.size() * sizeof v[0], hipMemcpyHostToDevice));
+            if ((which >> a & 1) && !up) CK(hipMemcpy(v.data(), b, v.size() * sizeof v[0], hipMemcpyDeviceToHost));
+            return 0;
+        });
+    }
+    // the context of S streams of W x H pictures (mbw x mbh = nmb macroblocks) that begins at stream s0 of the buffers
+    FerDev dev(int W, int H, int mbw, int mbh, int nmb, size_t S, size_t s0 = 0) const
+    {
+        FerDev d = {};
+        d.W = W, d.H = H, d.Wc = W / 2, d.Hc = H / 2;
+        d.mbw = mbw, d.mbh = mbh, d.nmb = nmb, d.S = (int)S;
+        d.ysz = (size_t)W * H, d.csz = d.ysz / 4;
+        seam_each(*this, d, [&](int a, auto &b, auto *&q) { return b.p ? (q = b.p + s0 * seam_stride(a, nmb), 0) : 0; });
+        return d;
+    }
+};
 
 extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result *results, size_t n)
 {
@@ -488,56 +488,15 @@ extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result
     bool any_write = false, any_parse = false;
     for (size_t j = 0; j < n; j++) (jobs[j].op == FERHIP_RES_WRITE ? any_write : any_parse) = true;
     // the FerDev side information cavlc_nC and the block loop read: mb_type, cbp, tc, levels of [n streams][4 macroblocks]
-    std::vector<int> mbt;
-    std::vector<uint8_t> cbp, tc, cur(n, 0);
-    std::vector<int16_t> lev;
-    if (any_write) {
-        mbt.assign(n * 4, 0);
-        cbp.assign(n * 8, 0);
-        tc.assign(n * 96, 0);
-        lev.assign(n * 4 * FER_LEVELS, 0);
-    }
-    for (size_t j = 0; j < n && any_write; j++) {
-        const ferhip_res_job &J = jobs[j];
-        if (J.op != FERHIP_RES_WRITE) continue;
-        const int c = J.avail;  // both neighbours: address 3 (A = 2, B = 1); A only: 1 (A = 0); B only: 2 (B = 0); neither: 0
-        cur[j] = (uint8_t)c;
-        for (int k = 0; k < 2; k++) {
-            if (!(J.avail & (1 << k))) continue;
-            const ferhip_res_nb &N = J.nb[k];
-            const size_t m = j * 4 + (size_t)(k == 0 ? c - 1 : c - 2);
-            mbt[m] = N.p_skip ? FER_P_SKIP : 0;
-            cbp[m * 2] = (uint8_t)N.cbp_luma;
-            cbp[m * 2 + 1] = (uint8_t)N.cbp_chroma;
-            for (int b = 0; b < 16; b++) tc[m * 24 + b] = (uint8_t)N.tc_luma[b];
-            for (int b = 0; b < 8; b++) tc[m * 24 + 16 + b] = (uint8_t)N.tc_chroma[b >> 2][b & 3];
-        }
-        // the macroblock itself: its levels, and its own cbp and tc, which the blocks inside it read -- tc by the rule of
-        // k_p_resid / k_intra_mb: the non-zero levels of each block's list (15 entries for Intra16x16 AC and chroma AC)
-        const size_t m = j * 4 + (size_t)c;
-        int16_t *lv = lev.data() + m * FER_LEVELS;
-        const bool i16 = J.cls == 1;
-        cbp[m * 2] = (uint8_t)J.cbp_luma;
-        cbp[m * 2 + 1] = (uint8_t)J.cbp_chroma;
-        for (int b = 0; b < 16; b++) {
-            const int32_t *src = i16 ? J.ac16[b] : J.lumaLevel[b];
-            for (int k = 0; k < (i16 ? 15 : 16); k++) lv[b * 16 + k] = (int16_t)src[k];
-            if (J.cbp_luma & (1 << (b >> 2))) tc[m * 24 + b] = (uint8_t)count_nz(src, i16 ? 15 : 16);  // (0 for a block the CBP leaves out)
-            lv[FER_LV_DC16 + b] = (int16_t)J.dc16[b];
-        }
-        for (int b = 0; b < 8; b++) {
-            lv[FER_LV_CDC + b] = (int16_t)J.cdc[b >> 2][b & 3];
-            for (int k = 0; k < 15; k++) lv[FER_LV_CAC + b * 15 + k] = (int16_t)J.cac[b >> 2][b & 3][k];
-            if (J.cbp_chroma & 2) tc[m * 24 + 16 + b] = (uint8_t)count_nz(J.cac[b >> 2][b & 3], 15);
-        }
-    }
-    DevBuf<uint8_t> dj, dr, dcbp, dtc, dcur;
-    DevBuf<int> dmbt;
-    DevBuf<int16_t> dlev;
+    const unsigned use = any_write ? SEAM_RES_USE : 0;
+    SeamHost h(n, SEAM_RES_NMB, use);
+    std::vector<uint8_t> cur(n, 0);
+    seam_pack_res_write(h, cur.data(), jobs);
+    SeamDev sd;
+    DevBuf<uint8_t> dj, dr, dcur;
     const size_t jbytes = n * sizeof(ferhip_res_job) + 16;  // DecBits reads a padded stream: behind the last job's bits
     if (dj.reserve(jbytes) || dr.reserve(n * sizeof(ferhip_res_result))) return FERHIP_E_HIP;
-    if (any_write && (dcbp.reserve(cbp.size()) || dtc.reserve(tc.size()) || dcur.reserve(n) || dmbt.reserve(mbt.size()) || dlev.reserve(lev.size())))
-        return FERHIP_E_HIP;
+    if (any_write && (sd.reserve(n, SEAM_RES_NMB, use) || dcur.reserve(n))) return FERHIP_E_HIP;
     const DecLuts *luts = any_parse ? dec_luts(0) : nullptr;
     if (any_parse && !luts) return FERHIP_E_HIP;
     CK(hipMemset(dj, 0, jbytes));
@@ -546,19 +505,9 @@ extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result
     const ferhip_res_job *djobs = (const ferhip_res_job *)dj.p;
     ferhip_res_result *dres = (ferhip_res_result *)dr.p;
     if (any_write) {
-        CK(hipMemcpy(dmbt, mbt.data(), mbt.size() * sizeof(int), hipMemcpyHostToDevice));
-        CK(hipMemcpy(dcbp, cbp.data(), cbp.size(), hipMemcpyHostToDevice));
-        CK(hipMemcpy(dtc, tc.data(), tc.size(), hipMemcpyHostToDevice));
-        CK(hipMemcpy(dlev, lev.data(), lev.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        if (sd.copy(h, use, true)) return FERHIP_E_HIP;
         CK(hipMemcpy(dcur, cur.data(), n, hipMemcpyHostToDevice));
-        FerDev d = {};
-        d.mbw = d.mbh = 2;
-        d.nmb = 4;
-        d.S = (int)n;
-        d.mb_type = dmbt;
-        d.cbp = dcbp;
-        d.tc = dtc;
-        d.levels = dlev;
+        const FerDev d = sd.dev(0, 0, SEAM_RES_MBW, SEAM_RES_NMB / SEAM_RES_MBW, SEAM_RES_NMB, n);
         hipLaunchKernelGGL(k_residual_write, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, d, djobs, dcur.p, (int)n, dres);
         CK(hipGetLastError());
     }
@@ -571,7 +520,7 @@ extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result
     // TotalCoeff_luma_array[CurrMbAddr][0] of an Intra16x16 macroblock without AC blocks is what its DC block left there
     // (F/residual.cpp:530-541); no neighbour can read it (the CBP gates it), the encoder's side information keeps the AC count
     for (size_t j = 0; j < n; j++)
-        if (jobs[j].op == FERHIP_RES_WRITE && jobs[j].cls == 1 && !(jobs[j].cbp_luma & 1)) results[j].tc_luma[0] = count_nz(jobs[j].dc16, 16);
+        if (jobs[j].op == FERHIP_RES_WRITE && jobs[j].cls == 1 && !(jobs[j].cbp_luma & 1)) results[j].tc_luma[0] = seam_count_nz(jobs[j].dc16, 16);
     return 0;
 }
 
@@ -581,9 +530,6 @@ extern "C" int ferhip_residual_mbs(const ferhip_res_job *jobs, ferhip_res_result
 // k_dec_intra (DECODE) are launched for the one anti-diagonal of pos, over the streams of the jobs with that pos.  A
 // diagonal launch also visits the other macroblock of the diagonal (2 and 3 share one); nothing it reads or writes there
 // is a neighbour of the job's macroblock, and in DECODE its type is set to P_Skip so that k_dec_intra passes it by.
-#define SEAM_YSZ (FERHIP_NB_W * FERHIP_NB_H)
-#define SEAM_CSZ (SEAM_YSZ / 4)
-#define SEAM_MBW (FERHIP_NB_W / 16)
 
 // getIntra4x4PredMode of the DECODE jobs: dec_i4_modes (fer_decode_dev.h) fed from the FerDev side information the way
 // k_dec_parse feeds it from its neighbour rows.  One thread per stream (the function is scalar code).
@@ -657,216 +603,41 @@ __global__ __launch_bounds__(64) void k_seam_intra_pred(FerDev d, const uint8_t 
     }
 }
 
-static FerDev seam_streams(const FerDev &d, int s0, int cnt)  // the same context, streams s0 .. s0 + cnt - 1 only
-{
-    FerDev g = d;
-    g.S = cnt;
-    g.curY += (size_t)s0 * d.ysz;
-    g.curCb += (size_t)s0 * d.csz;
-    g.curCr += (size_t)s0 * d.csz;
-    g.qp += s0;
-    g.hdr += (size_t)s0 * 4;
-    g.mb_type += (size_t)s0 * d.nmb;
-    g.cbp += (size_t)s0 * d.nmb * 2;
-    g.tc += (size_t)s0 * d.nmb * 24;
-    g.i4mode += (size_t)s0 * d.nmb * 16;
-    g.i4flag += (size_t)s0 * d.nmb * 16;
-    g.chroma_mode += (size_t)s0 * d.nmb;
-    g.levels += (size_t)s0 * d.nmb * FER_LEVELS;
-    g.mbsize += (size_t)s0 * d.nmb * 2;
-    g.dec_qp += (size_t)s0 * d.nmb;
-    g.dec_state += (size_t)s0 * 4;
-    return g;
-}
-
 extern "C" int ferhip_chroma_qp(int qpy);  // fer_api.hip: qPiToQPc for chroma_qp_index_offset 0, the encoder's
 
 extern "C" int ferhip_intra_mbs(const ferhip_intra_job *jobs, ferhip_intra_result *results, size_t n)
 {
     if (fer_seam_check_intra_mbs(jobs, results, n)) return FERHIP_E_ARG;
-    const int NM = FERHIP_NB_MBS;
-    // stream s = job order[s]: the jobs of one (op, pos) side by side, so that a launch covers a range of streams
-    std::vector<uint32_t> order(n);
-    for (size_t j = 0; j < n; j++) order[j] = (uint32_t)j;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].op * NM + jobs[a].pos < jobs[b].op * NM + jobs[b].pos; });
-    std::vector<uint8_t> Y(n * SEAM_YSZ), Cb(n * SEAM_CSZ), Cr(n * SEAM_CSZ), cbp(n * NM * 2, 0), tc(n * NM * 24, 0), i4m(n * NM * 16, 0),
-        i4f(n * NM * 16, 0), cmode(n * NM, 0), dqp(n * NM, 0), pos(n);
-    std::vector<int> mbt(n * NM, 0), qp(n), dst(n * 4, 0), mbsz(n * NM * 2, 0);
-    std::vector<uint32_t> hdr(n * 4, 0);
-    std::vector<int16_t> lev(n * NM * FER_LEVELS, 0);
-    for (size_t s = 0; s < n; s++) {
-        const ferhip_intra_job &J = jobs[order[s]];
-        const bool dec = J.op == FERHIP_INTRA_DECODE;
-        memcpy(&Y[s * SEAM_YSZ], J.Y, SEAM_YSZ);
-        memcpy(&Cb[s * SEAM_CSZ], J.Cb, SEAM_CSZ);
-        memcpy(&Cr[s * SEAM_CSZ], J.Cr, SEAM_CSZ);
-        pos[s] = (uint8_t)J.pos;
-        qp[s] = J.qp | (ferhip_chroma_qp(J.qp) << 8);
-        hdr[s * 4] = (uint32_t)J.chroma_qp_offset;
-        hdr[s * 4 + 1] = (uint32_t)J.constrained_intra;
-        hdr[s * 4 + 3] = (uint32_t)J.slice_type;
-        dst[s * 4 + 1] = NM;  // k_dec_intra: every macroblock was reached by the parser
-        for (int m = 0; m < NM; m++) {
-            const size_t mi = s * NM + m;
-            const ferhip_nb_mb &N = J.mb[m];
-            dqp[mi] = (uint8_t)J.qp;
-            if (m > J.pos) mbt[mi] = dec ? FER_P_SKIP : 0;
-            if (m >= J.pos) continue;
-            mbt[mi] = N.mb_type;
-            cbp[mi * 2] = (uint8_t)N.cbp_luma;
-            cbp[mi * 2 + 1] = (uint8_t)N.cbp_chroma;
-            for (int b = 0; b < 16; b++) {
-                tc[mi * 24 + b] = (uint8_t)N.tc_luma[b];
-                i4m[mi * 16 + b] = (uint8_t)N.i4mode[b];
-            }
-            for (int b = 0; b < 8; b++) tc[mi * 24 + 16 + b] = (uint8_t)N.tc_chroma[b >> 2][b & 3];
-        }
-        if (dec && J.pos == 3) mbt[s * NM + 2] = FER_P_SKIP;  // shares the diagonal of pos 3 and is none of its neighbours
-        const size_t mi = s * NM + J.pos;
-        mbt[mi] = J.mb[J.pos].mb_type;
-        if (!dec) continue;
-        cmode[mi] = (uint8_t)J.chroma_mode;
-        for (int b = 0; b < 16; b++) i4f[mi * 16 + b] = (uint8_t)((J.prev_flag[b] << 3) | J.rem_mode[b]);
-        int16_t *lv = &lev[mi * FER_LEVELS];
-        const bool i16 = fer_seam_is_i16(J.mb[J.pos].mb_type, J.slice_type);
-        for (int b = 0; b < 16; b++) {
-            for (int k = 0; k < (i16 ? 15 : 16); k++) lv[b * 16 + k] = (int16_t)(i16 ? J.ac16[b][k] : J.lumaLevel[b][k]);
-            if (i16) lv[FER_LV_DC16 + b] = (int16_t)J.dc16[b];
-        }
-        for (int b = 0; b < 8; b++) {
-            lv[FER_LV_CDC + b] = (int16_t)J.cdc[b >> 2][b & 3];
-            for (int k = 0; k < 15; k++) lv[FER_LV_CAC + b * 15 + k] = (int16_t)J.cac[b >> 2][b & 3][k];
-        }
-    }
-    DevBuf<uint8_t> dY, dCb, dCr, dcbp, dtc, di4m, di4f, dcm, ddqp, dpos;
-    DevBuf<int> dmbt, dqpw, ddst, dmbsz;
-    DevBuf<uint32_t> dhdr;
-    DevBuf<int16_t> dlev;
+    const SeamOrder o = seam_intra_order(jobs, n);  // stream s = job o.order[s]
+    SeamHost h(n, FERHIP_NB_MBS, SEAM_INTRA_USE);
+    std::vector<uint8_t> pos(n);
+    std::vector<int32_t> pred(n * 384);
+    seam_pack_intra(h, pos.data(), jobs, o.order.data(), ferhip_chroma_qp);
+    SeamDev sd;
+    DevBuf<uint8_t> dpos;
     DevBuf<int32_t> dpred;
-    if (dY.reserve(Y.size()) || dCb.reserve(Cb.size()) || dCr.reserve(Cr.size()) || dcbp.reserve(cbp.size()) || dtc.reserve(tc.size()) ||
-        di4m.reserve(i4m.size()) || di4f.reserve(i4f.size()) || dcm.reserve(cmode.size()) || ddqp.reserve(dqp.size()) || dpos.reserve(n) ||
-        dmbt.reserve(mbt.size()) || dqpw.reserve(n) || ddst.reserve(dst.size()) || dmbsz.reserve(mbsz.size()) || dhdr.reserve(hdr.size()) ||
-        dlev.reserve(lev.size()) || dpred.reserve(n * 384))
-        return FERHIP_E_HIP;
-#define SEAM_UP(dv, hv) CK(hipMemcpy(dv, hv.data(), hv.size() * sizeof hv[0], hipMemcpyHostToDevice))
-#define SEAM_DOWN(hv, dv) CK(hipMemcpy(hv.data(), dv, hv.size() * sizeof hv[0], hipMemcpyDeviceToHost))
-    SEAM_UP(dY, Y);
-    SEAM_UP(dCb, Cb);
-    SEAM_UP(dCr, Cr);
-    SEAM_UP(dcbp, cbp);
-    SEAM_UP(dtc, tc);
-    SEAM_UP(di4m, i4m);
-    SEAM_UP(di4f, i4f);
-    SEAM_UP(dcm, cmode);
-    SEAM_UP(ddqp, dqp);
-    SEAM_UP(dpos, pos);
-    SEAM_UP(dmbt, mbt);
-    SEAM_UP(dqpw, qp);
-    SEAM_UP(ddst, dst);
-    SEAM_UP(dmbsz, mbsz);
-    SEAM_UP(dhdr, hdr);
-    SEAM_UP(dlev, lev);
-    FerDev d = {};
-    d.W = FERHIP_NB_W;
-    d.H = FERHIP_NB_H;
-    d.Wc = d.W / 2;
-    d.Hc = d.H / 2;
-    d.mbw = SEAM_MBW;
-    d.mbh = FERHIP_NB_H / 16;
-    d.nmb = NM;
-    d.S = (int)n;
-    d.ysz = SEAM_YSZ;
-    d.csz = SEAM_CSZ;
-    d.curY = dY;
-    d.curCb = dCb;
-    d.curCr = dCr;
-    d.qp = dqpw;
-    d.hdr = dhdr;
-    d.mb_type = dmbt;
-    d.cbp = dcbp;
-    d.tc = dtc;
-    d.i4mode = di4m;
-    d.i4flag = di4f;
-    d.chroma_mode = dcm;
-    d.levels = dlev;
-    d.mbsize = dmbsz;
-    d.dec_qp = ddqp;
-    d.dec_state = ddst;
-    for (size_t s0 = 0; s0 < n;) {  // one launch per (op, pos)
-        const ferhip_intra_job &J = jobs[order[s0]];
-        size_t s1 = s0 + 1;
-        while (s1 < n && jobs[order[s1]].op == J.op && jobs[order[s1]].pos == J.pos) s1++;
-        const FerDev g = seam_streams(d, (int)s0, (int)(s1 - s0));
+    if (sd.reserve(n, FERHIP_NB_MBS, SEAM_INTRA_USE) || dpos.reserve(n) || dpred.reserve(pred.size())) return FERHIP_E_HIP;
+    if (sd.copy(h, SEAM_INTRA_USE, true)) return FERHIP_E_HIP;
+    CK(hipMemcpy(dpos, pos.data(), n, hipMemcpyHostToDevice));
+    for (size_t r = 0; r + 1 < o.run.size(); r++) {  // one launch per (op, pos)
+        const size_t s0 = o.run[r], cnt = o.run[r + 1] - s0;
+        const ferhip_intra_job &J = jobs[o.order[s0]];
+        const FerDev g = sd.dev(FERHIP_NB_W, FERHIP_NB_H, SEAM_MBW, FERHIP_NB_H / 16, FERHIP_NB_MBS, cnt, s0);
         const int diag = J.pos % SEAM_MBW + 2 * (J.pos / SEAM_MBW);
         if (J.op == FERHIP_INTRA_ENCODE) {
             fer_launch_intra_diag(g, diag, 0);
         } else {
-            hipLaunchKernelGGL(k_seam_i4_modes, dim3((unsigned)((s1 - s0 + 63) / 64)), dim3(64), 0, 0, g, dpos.p + s0);
+            hipLaunchKernelGGL(k_seam_i4_modes, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, 0, g, dpos.p + s0);
             fer_launch_decode_intra_diag(g, diag, 0);
         }
         CK(hipGetLastError());
-        s0 = s1;
     }
+    const FerDev d = sd.dev(FERHIP_NB_W, FERHIP_NB_H, SEAM_MBW, FERHIP_NB_H / 16, FERHIP_NB_MBS, n);
     hipLaunchKernelGGL(k_seam_intra_pred, dim3((unsigned)n), dim3(64), 0, 0, d, dpos.p, dpred.p);
     CK(hipGetLastError());
-    std::vector<int32_t> pred(n * 384);
-    SEAM_DOWN(Y, dY);
-    SEAM_DOWN(Cb, dCb);
-    SEAM_DOWN(Cr, dCr);
-    SEAM_DOWN(cbp, dcbp);
-    SEAM_DOWN(tc, dtc);
-    SEAM_DOWN(i4m, di4m);
-    SEAM_DOWN(i4f, di4f);
-    SEAM_DOWN(cmode, dcm);
-    SEAM_DOWN(mbt, dmbt);
-    SEAM_DOWN(mbsz, dmbsz);
-    SEAM_DOWN(lev, dlev);
-    SEAM_DOWN(pred, dpred);
-#undef SEAM_UP
-#undef SEAM_DOWN
-    for (size_t s = 0; s < n; s++) {
-        const ferhip_intra_job &J = jobs[order[s]];
-        ferhip_intra_result &R = results[order[s]];
-        memset(&R, 0, sizeof R);
-        const bool enc = J.op == FERHIP_INTRA_ENCODE;
-        const size_t mi = s * NM + J.pos;
-        const int t = mbt[mi];
-        const bool i4 = fer_seam_is_i4(t, J.slice_type);
-        R.mb_type = t;
-        R.ret = i4 ? -1 : ((J.slice_type == 2 ? t : t - 5) - 1) & 3;
-        R.chroma_mode = cmode[mi];
-        for (int b = 0; b < 16; b++) R.i4mode[b] = (enc || i4) ? i4m[mi * 16 + b] : 0;
-        const int xp = (J.pos % SEAM_MBW) << 4, yp = (J.pos / SEAM_MBW) << 4;
-        for (int i = 0; i < 256; i++) R.recY[i] = Y[s * SEAM_YSZ + (size_t)(yp + (i >> 4)) * FERHIP_NB_W + xp + (i & 15)];
-        for (int i = 0; i < 64; i++) {
-            const size_t o = s * SEAM_CSZ + (size_t)(yp / 2 + (i >> 3)) * (FERHIP_NB_W / 2) + xp / 2 + (i & 7);
-            R.recCb[i] = Cb[o];
-            R.recCr[i] = Cr[o];
-        }
-        memcpy(R.predL, &pred[s * 384], sizeof R.predL);
-        memcpy(R.predCb, &pred[s * 384 + 256], sizeof R.predCb);
-        memcpy(R.predCr, &pred[s * 384 + 320], sizeof R.predCr);
-        if (!enc) continue;
-        R.cbp_luma = cbp[mi * 2];
-        R.cbp_chroma = cbp[mi * 2 + 1];
-        R.mbsize[0] = mbsz[mi * 2];
-        R.mbsize[1] = mbsz[mi * 2 + 1];
-        for (int b = 0; b < 16; b++) {  // as the macroblock layer reads them (k_cavlc): bit 3 = the flag, bits 0..2 = rem
-            R.prev_flag[b] = (i4f[mi * 16 + b] >> 3) & 1;
-            R.rem_mode[b] = i4f[mi * 16 + b] & 7;
-            R.tc_luma[b] = tc[mi * 24 + b];
-        }
-        for (int b = 0; b < 8; b++) R.tc_chroma[b >> 2][b & 3] = tc[mi * 24 + 16 + b];
-        const int16_t *lv = &lev[mi * FER_LEVELS];
-        for (int b = 0; b < 16; b++) {
-            for (int k = 0; k < (i4 ? 16 : 15); k++) (i4 ? R.lumaLevel : R.ac16)[b][k] = lv[b * 16 + k];
-            if (!i4) R.dc16[b] = lv[FER_LV_DC16 + b];
-        }
-        for (int b = 0; b < 8; b++) {
-            R.cdc[b >> 2][b & 3] = lv[FER_LV_CDC + b];
-            for (int k = 0; k < 15; k++) R.cac[b >> 2][b & 3][k] = lv[FER_LV_CAC + b * 15 + k];
-        }
-    }
+    if (sd.copy(h, SEAM_INTRA_DOWN, false)) return FERHIP_E_HIP;
+    CK(hipMemcpy(pred.data(), dpred, pred.size() * sizeof pred[0], hipMemcpyDeviceToHost));
+    seam_unpack_intra(results, h, pred.data(), jobs, o.order.data());
     return 0;
 }
 
@@ -930,20 +701,11 @@ extern "C" int ferhip_mv_mbs(const ferhip_mv_job *jobs, ferhip_mv_result *result
     if (fer_seam_check_mv_mbs(jobs, results, n)) return FERHIP_E_ARG;
     DevBuf<ferhip_mv_job> dj;
     DevBuf<ferhip_mv_result> dr;
-    DevBuf<short> dmv;
-    DevBuf<int> dmbt;
-    if (dj.reserve(n) || dr.reserve(n) || dmv.reserve(n * FERHIP_NB_MBS * 8) || dmbt.reserve(n * FERHIP_NB_MBS)) return FERHIP_E_HIP;
+    SeamDev sd;  // the kernel fills the vector field and the type array itself
+    if (dj.reserve(n) || dr.reserve(n) || sd.reserve(n, FERHIP_NB_MBS, SA_BIT(mv) | SA_BIT(mb_type))) return FERHIP_E_HIP;
     CK(hipMemcpy(dj, jobs, n * sizeof *jobs, hipMemcpyHostToDevice));
     CK(hipMemset(dr, 0, n * sizeof *results));
-    FerDev d = {};
-    d.W = FERHIP_NB_W;
-    d.H = FERHIP_NB_H;
-    d.mbw = SEAM_MBW;
-    d.mbh = FERHIP_NB_H / 16;
-    d.nmb = FERHIP_NB_MBS;
-    d.S = (int)n;
-    d.mv = dmv;
-    d.mb_type = dmbt;
+    const FerDev d = sd.dev(FERHIP_NB_W, FERHIP_NB_H, SEAM_MBW, FERHIP_NB_H / 16, FERHIP_NB_MBS, n);
     hipLaunchKernelGGL(k_seam_mv, dim3((unsigned)n), dim3(64), 0, 0, d, dj.p, dr.p);
     CK(hipGetLastError());
     CK(hipMemcpy(results, dr, n * sizeof *results, hipMemcpyDeviceToHost));
@@ -989,42 +751,27 @@ extern "C" int ferhip_mc_sub_mb_parts(const uint8_t *ref_i420, int width, int he
 {
     if (fer_seam_check_mc_parts(ref_i420, width, height, desc, n, predL, predCb, predCr)) return FERHIP_E_ARG;
     const size_t fsz = (size_t)width * height * 3 / 2;
-    uint8_t *dref = nullptr;
-    int32_t *dd = nullptr, *dl = nullptr, *db = nullptr, *dr = nullptr, *rb = nullptr, *rr = nullptr;
+    DevBuf<uint8_t> dref;
+    DevBuf<int32_t> dd, dl, db, dr, rb, rr;
     std::vector<int32_t> hb(n * 4), hr(n * 4);
-    auto body = [&]() -> int {
-        CK(hipMalloc((void **)&dref, fsz + 256));
-        CK(hipMalloc((void **)&dd, n * 20));
-        CK(hipMalloc((void **)&dl, n * 64));
-        CK(hipMalloc((void **)&db, n * 16));
-        CK(hipMalloc((void **)&dr, n * 16));
-        CK(hipMalloc((void **)&rb, n * 16));
-        CK(hipMalloc((void **)&rr, n * 16));
-        CK(hipMemcpy(dref, ref_i420, fsz, hipMemcpyHostToDevice));
-        CK(hipMemcpy(dd, desc, n * 20, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_mc_parts, dim3((unsigned)n), dim3(64), 0, 0, dref, width, height, dd, (int)n, dl, db, dr, rb, rr);
-        CK(hipGetLastError());
-        CK(hipMemcpy(predL, dl, n * 64, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(predCb, db, n * 16, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(predCr, dr, n * 16, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(hb.data(), rb, n * 16, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(hr.data(), rr, n * 16, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n * 4; i++)
-            if (hb[i] != predCb[i] || hr[i] != predCr[i]) {
-                fprintf(stderr, "ferhip_mc_sub_mb_parts: the row form of the chroma interpolation differs at sub-block %zu\n", i / 4);
-                return FERHIP_E_DEVICE;
-            }
-        return 0;
-    };
-    const int rc = body();
-    hipFree(dref);
-    hipFree(dd);
-    hipFree(dl);
-    hipFree(db);
-    hipFree(dr);
-    hipFree(rb);
-    hipFree(rr);
-    return rc;
+    if (dref.reserve(fsz + 256) || dd.reserve(n * 5) || dl.reserve(n * 16) || db.reserve(n * 4) || dr.reserve(n * 4) || rb.reserve(n * 4) ||
+        rr.reserve(n * 4))
+        return FERHIP_E_HIP;
+    CK(hipMemcpy(dref, ref_i420, fsz, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dd, desc, n * 20, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_mc_parts, dim3((unsigned)n), dim3(64), 0, 0, dref.p, width, height, dd.p, (int)n, dl.p, db.p, dr.p, rb.p, rr.p);
+    CK(hipGetLastError());
+    CK(hipMemcpy(predL, dl, n * 64, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(predCb, db, n * 16, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(predCr, dr, n * 16, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hb.data(), rb, n * 16, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hr.data(), rr, n * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n * 4; i++)
+        if (hb[i] != predCb[i] || hr[i] != predCr[i]) {
+            fprintf(stderr, "ferhip_mc_sub_mb_parts: the row form of the chroma interpolation differs at sub-block %zu\n", i / 4);
+            return FERHIP_E_DEVICE;
+        }
+    return 0;
 }
 
 // ---- block-level KATs: the reference's per-block entry points (F/quantizationTransform.h, F/scaleTransform.h) as
@@ -1068,23 +815,15 @@ __global__ void k_block_kat(int op, int qP, const int32_t *in, int32_t *out, int
 
 static int block_kat(int op, int qP, const int32_t *in, int32_t *out, int flag, size_t n)
 {
-    if (!in || !out || qP < 0 || qP > 51) return FERHIP_E_ARG;
+    if (fer_seam_check_block_kat(qP, in, out)) return FERHIP_E_ARG;
     if (n == 0) return 0;
-    int32_t *di = nullptr, *dout = nullptr;
-    CK(hipMalloc((void **)&di, n * 64));
-    if (hipMalloc((void **)&dout, n * 64) != hipSuccess) {
-        hipFree(di);
-        return FERHIP_E_HIP;
-    }
-    int rc = 0;
-    if (hipMemcpy(di, in, n * 64, hipMemcpyHostToDevice) != hipSuccess) rc = FERHIP_E_HIP;
-    if (!rc) {
-        hipLaunchKernelGGL(k_block_kat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, qP, di, dout, flag, n);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, n * 64, hipMemcpyDeviceToHost) != hipSuccess) rc = FERHIP_E_HIP;
-    }
-    hipFree(di);
-    hipFree(dout);
-    return rc;
+    DevBuf<int32_t> di, dout;
+    if (di.reserve(n * 16) || dout.reserve(n * 16)) return FERHIP_E_HIP;
+    CK(hipMemcpy(di, in, n * 64, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_block_kat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, qP, di.p, dout.p, flag, n);
+    CK(hipGetLastError());
+    CK(hipMemcpy(out, dout, n * 64, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int ferhip_forward_residual(int qP, const int32_t *in, int32_t *out, int keep_dc, size_t n)

@@ -71,6 +71,12 @@ static inline int fer_seam_check_mc_parts(const uint8_t *ref_i420, int width, in
     return 0;
 }
 
+// the block-level KATs (ferhip_forward_residual .. ferhip_transform_inverse_scan): any number of blocks, none included
+static inline int fer_seam_check_block_kat(int qP, const int32_t *in, const int32_t *out)
+{
+    return (!in || !out || qP < 0 || qP > 51) ? FERHIP_E_ARG : 0;
+}
+
 static inline bool fer_seam_levels16(const int32_t *v, size_t n)  // the device keeps levels in 16 bits
 {
     for (size_t i = 0; i < n; i++)

@@ -638,15 +638,10 @@ def mb_unit(jobs):
     J = (MbJob * n)()
     R = (MbResult * n)()
     for k, j in enumerate(jobs):
-        for name, val in j.items():
-            if isinstance(val, (int, np.integer)):
-                setattr(J[k], name, int(val))
-            else:
-                a = np.ascontiguousarray(val, np.int32).reshape(-1)
-                C.memmove(getattr(J[k], name), a.ctypes.data, a.nbytes)
+        _set_fields(J[k], j)
     lib.ferhip_mb_unit.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     _chk(lib.ferhip_mb_unit(J, R, n), "ferhip_mb_unit")
-    return [{f: np.frombuffer(getattr(R[k], f), np.int32).copy() for f, _ in MbResult._fields_} for k in range(n)]
+    return [_get_fields(R[k]) for k in range(n)]
 
 
 def cavlc_blocks(coef, nC, max_num_coeff):
@@ -707,27 +702,17 @@ def residual_jobs(jobs):
     the fields of ferhip_res_nb; bits = the stream of a PARSE job (bytes or uint8 array; nbytes defaults to its length)"""
     J = (ResJob * len(jobs))()
     for k, j in enumerate(jobs):
-        for name, val in j.items():
-            if name == "nb":
-                for i, nb in enumerate(val):
-                    for f, v in (nb or {}).items():
-                        if isinstance(v, (int, np.integer, bool)):
-                            setattr(J[k].nb[i], f, int(v))
-                        else:
-                            a = np.ascontiguousarray(v, np.int32).reshape(-1)
-                            C.memmove(getattr(J[k].nb[i], f), a.ctypes.data, a.nbytes)
-            elif name == "bits":
-                a = np.ascontiguousarray(np.frombuffer(val, np.uint8) if isinstance(val, (bytes, bytearray)) else val, np.uint8).reshape(-1)
-                if a.size > RES_BITS_MAX:
-                    raise FerHipError(f"a PARSE job takes at most {RES_BITS_MAX} bytes")
-                C.memmove(J[k].bits, a.ctypes.data, a.size)
-                if "nbytes" not in j:
-                    J[k].nbytes = a.size
-            elif isinstance(val, (int, np.integer)):
-                setattr(J[k], name, int(val))
-            else:
-                a = np.ascontiguousarray(val, np.int32).reshape(-1)
-                C.memmove(getattr(J[k], name), a.ctypes.data, a.nbytes)
+        _set_fields(J[k], {f: v for f, v in j.items() if f not in ("nb", "bits")})
+        for i, nb in enumerate(j.get("nb", ())):
+            _set_fields(J[k].nb[i], nb or {})
+        if "bits" in j:
+            val = j["bits"]
+            a = np.ascontiguousarray(np.frombuffer(val, np.uint8) if isinstance(val, (bytes, bytearray)) else val, np.uint8).reshape(-1)
+            if a.size > RES_BITS_MAX:
+                raise FerHipError(f"a PARSE job takes at most {RES_BITS_MAX} bytes")
+            C.memmove(J[k].bits, a.ctypes.data, a.size)
+            if "nbytes" not in j:
+                J[k].nbytes = a.size
     return J
 
 

@@ -69,6 +69,35 @@ def test_intra_decode_kat(pkg, fo):
     x.close()
 
 
+def test_intra_mixed_batch(pkg, fo):
+    """ENCODE and DECODE jobs in ONE call, every pos under both ops twice, submitted in descending pos with the ops
+    alternating: the call sorts them into runs of one (op, pos), launches each run on its range of streams and scatters the
+    results back.  Every result is the oracle's, and the one the same job gets when it is submitted alone."""
+    F = pkg.ferhip
+    enc = [j for j in sn.encode_jobs(21, 1) if j["qp"] in (sn.ENC_QPS[0], sn.ENC_QPS[-1])]
+    dec = sn.decode_jobs(22, 12)
+    assert len(enc) == len(dec) == 12
+    jobs = []
+    for pos in range(5, -1, -1):
+        for e, d in zip([j for j in enc if j["pos"] == pos], [j for j in dec if j["pos"] == pos]):
+            jobs += [e, d]
+    assert len(jobs) == 24 and [j["op"] for j in jobs] == [F.INTRA_ENCODE, F.INTRA_DECODE] * 12
+    assert [j["pos"] for j in jobs] == [p for p in range(5, -1, -1) for _ in range(4)]
+    got = F.intra_mbs(jobs)
+    xe, xd = sn.NbOracle(fo), sn.NbOracle(fo)
+    for k, (j, g) in enumerate(zip(jobs, got)):
+        if j["op"] == F.INTRA_ENCODE:
+            _same([g], [xe.encode(j)], ENC_FIELDS, ("mixed encode", k))
+        else:
+            _same([g], [xd.decode(j)], DEC_FIELDS, ("mixed decode", k))
+        alone = F.intra_mbs([j])[0]
+        assert alone.keys() == g.keys()
+        for f in g:
+            assert np.array_equal(np.asarray(g[f]), np.asarray(alone[f])), ("alone", k, f)
+    xe.close()
+    xd.close()
+
+
 def test_mv_kat(pkg, fo):
     F = pkg.ferhip
     x = sn.NbOracle(fo)

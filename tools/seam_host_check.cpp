@@ -218,9 +218,19 @@ static void residual_mbs()
     GOOD(call());
 }
 
+static void block_kat()  // the pointers are only compared: a call of no blocks is a good call
+{
+    std::unique_ptr<int32_t[]> in(new int32_t[16]()), out(new int32_t[16]());
+    for (int qP : {0, 26, 51}) GOOD(fer_seam_check_block_kat(qP, in.get(), out.get()));
+    for (int qP : {-1, 52, INT32_MIN, INT32_MAX}) BAD(fer_seam_check_block_kat(qP, in.get(), out.get()));
+    BAD(fer_seam_check_block_kat(26, nullptr, out.get()));
+    BAD(fer_seam_check_block_kat(26, in.get(), nullptr));
+}
+
 int main()
 {
     blocks();
+    block_kat();
     mb_unit();
     mc_parts();
     residual_mbs();
