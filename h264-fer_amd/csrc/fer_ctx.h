@@ -1,5 +1,5 @@
 // fer_ctx.h -- the context of libferhip and the owners of its resources, for the host translation units that drive it
-// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
+// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_rtp.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
 // fer_mbunit.hip, every buffer of which is a DevBuf).
 #pragma once
 #include "fer_internal.h"
@@ -135,6 +135,13 @@ struct ferhip_ctx {
     PinnedRing ps_ring;                // [S][FER_NAL_PS_ROW]
     std::vector<uint8_t> ps_dirty;     // [S] the stream's row must be sent (empty until the table exists)
     bool ps_wide = false;              // a row was too long to record where its PPS begins: no length-prefixed form
+    // RTP packets (fer_rtp.hip), on first use: the callers' headers go to the device through a pinned ring of their own
+    ferhip_rtp_au *rtp_index = nullptr, *h_rtp_index = nullptr;  // device / pinned [S + 1]: ferhip_fetch_rtp's index
+    uint32_t *d_rtp_hdr = nullptr;     // device [S][3]: ferhip_rtp_hdr as three words
+    PinnedRing rtp_ring;               // [S] ferhip_rtp_hdr
+    DevBuf<uint8_t> rtp_buf;           // ferhip_fetch_rtp's packets and table on the device, regrown when a picture needs more
+    DevBuf<ferhip_rtp_pkt> rtp_pkts;
+    bool rtp_ready = false;            // the four above exist
     // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof = false;
     struct Span { int phase; hipEvent_t a, b; long launches; };

@@ -1,8 +1,9 @@
 // fer_dec_syntax_host.h -- the first readers of the bytes a caller hands the decoders (ferhip_decode_streams, ferhip_dec_nal,
 // ferhip_decs_*): the bit reader and the SPS, PPS and slice-header parsers (F/headers_and_parameter_sets.cpp:245-298,398-537),
-// the Annex-B and length-prefixed splitters with emulation-prevention removal (F/nal.cpp:68-223) and the walk over an
-// AVCDecoderConfigurationRecord.  Plain C++ without the HIP runtime, so that it can be compiled into a stand-alone host
-// program and run under a sanitizer (tools/dec_syntax_host_check.cpp).
+// the Annex-B and length-prefixed splitters with emulation-prevention removal (F/nal.cpp:68-223), the RTP depacketiser
+// (split_rtp) and the walk over an AVCDecoderConfigurationRecord.  Plain C++ without the HIP runtime, so that it can be
+// compiled into a stand-alone host program and run under a sanitizer (tools/dec_syntax_host_check.cpp,
+// tools/rtp_host_check.cpp).
 #pragma once
 #include "../../include/ferhip.h"
 #include <stddef.h>
@@ -279,6 +280,94 @@ static inline int split_avcc(const uint8_t *s, size_t n, int L, std::vector<NalR
         pos = en;
     }
     return pos < n;  // fewer than L bytes are left: a unit that cannot state its length
+}
+
+// The RTP packets of one stream, in order (RFC 6184, packetization-mode 1; the definition: ferhip.h) -> its NAL units like
+// split_avcc.  expect: the sequence number the first packet must carry, -1 = any; it leaves as the one behind the last
+// packet, or -1 after a fault.  Returns the fault: 0, or the first of FER_RTP_MALFORMED, _GAP, _TRUNCATED, which ends the
+// walk; the units completed in front of it stand.  A unit without payload ends the unit list (not the walk), as it ends a
+// length-prefixed range.  A fragmented unit is joined in `fu` before its emulation prevention bytes are dropped, so that a
+// 00 00 03 across a fragment seam is one.
+#define FER_RTP_MALFORMED 2
+#define FER_RTP_GAP 3
+#define FER_RTP_TRUNCATED 4
+struct RtpPacket {
+    const uint8_t *p;
+    size_t n;
+};
+static inline int split_rtp(const RtpPacket *pk, size_t npk, int32_t &expect, std::vector<NalRef> &out, std::vector<uint8_t> &store)
+{
+    size_t total = 0;
+    for (size_t k = 0; k < npk; k++) total += pk[k].n;
+    if (store.size() < total) store.resize(total);  // an RBSP is shorter than the packets that carried its unit
+    uint8_t *w = store.data();
+    std::vector<uint8_t> fu;
+    bool open = false, ended = false;  // an FU-A unit is being joined; a unit without payload has ended the list
+    auto unit = [&](const uint8_t *s, size_t n) {
+        if (ended) return;
+        if (n == 1)
+            ended = true;
+        else
+            out.push_back(nal_unit(s, 0, n, w));
+    };
+    const auto fault = [&](int f) {
+        expect = -1;
+        return f;
+    };
+    for (size_t k = 0; k < npk; k++) {
+        const uint8_t *p = pk[k].p;
+        const size_t L = pk[k].n;
+        if (L < 12 || p[0] >> 6 != 2) return fault(FER_RTP_MALFORMED);
+        size_t hl = 12 + 4 * (size_t)(p[0] & 15);
+        if (p[0] & 0x10) {  // the extension: a 4-byte header whose last two bytes count its words
+            if (hl + 4 > L) return fault(FER_RTP_MALFORMED);
+            hl += 4 + 4 * ((size_t)p[hl + 2] << 8 | p[hl + 3]);
+            if (hl > L) return fault(FER_RTP_MALFORMED);
+        }
+        size_t pad = 0;
+        if (p[0] & 0x20) {
+            pad = p[L - 1];
+            if (pad < 1) return fault(FER_RTP_MALFORMED);
+        }
+        if (hl + pad >= L) return fault(FER_RTP_MALFORMED);
+        const int32_t seq = (int32_t)p[2] << 8 | p[3];
+        if (expect >= 0 && seq != expect) return fault(FER_RTP_GAP);
+        expect = (seq + 1) & 0xffff;
+        const uint8_t *s = p + hl;
+        const size_t n = L - pad - hl;  // >= 1
+        const int t = s[0] & 31;
+        if (open && t != 28) return fault(FER_RTP_MALFORMED);
+        if (t >= 1 && t <= 23) {
+            unit(s, n);
+        } else if (t == 24) {
+            size_t pos = 1;
+            if (pos == n) return fault(FER_RTP_MALFORMED);
+            while (pos < n) {
+                if (n - pos < 2) return fault(FER_RTP_MALFORMED);
+                const size_t size = (size_t)s[pos] << 8 | s[pos + 1];
+                pos += 2;
+                if (size == 0 || size > n - pos) return fault(FER_RTP_MALFORMED);
+                unit(s + pos, size);
+                pos += size;
+            }
+        } else if (t == 28) {
+            if (n < 2) return fault(FER_RTP_MALFORMED);
+            const bool S = (s[1] & 0x80) != 0, E = (s[1] & 0x40) != 0;
+            if ((S && E) || (S && open) || (!S && !open)) return fault(FER_RTP_MALFORMED);
+            if (S) {
+                fu.assign(1, (uint8_t)((s[0] & 0xE0) | (s[1] & 0x1F)));
+                open = true;
+            }
+            fu.insert(fu.end(), s + 2, s + n);
+            if (E) {
+                unit(fu.data(), fu.size());
+                open = false;
+            }
+        } else {
+            return fault(FER_RTP_MALFORMED);
+        }
+    }
+    return open ? fault(FER_RTP_TRUNCATED) : 0;
 }
 
 // AVCDecoderConfigurationRecord avcc[0, n) -> the (at, len) spans of its SPS, then of its PPS units (header byte included) and

@@ -14,9 +14,11 @@ struct ferhip_decs {
     DecIsolate iso;
     DecOutput out;                            // ferhip_decs_set_display, _set_layout, _set_csc: where the pictures go
     FerSplit split;                           // ferhip_decs_decode_dev: the splitter's buffers and the store of the units' RBSP
+    FerUnrtp unrtp;                           // ferhip_decs_decode_rtp from device memory: the depacketiser's buffers in front of it
     std::vector<std::vector<uint8_t>> whole;  // ... parameter sets longer than the prefix, fetched whole
     int in_format = FERHIP_IN_ANNEXB, length_size = 4;  // ferhip_decs_set_input
-    std::vector<int> overrun;                 // [S] AVCC input: the stream's chunk of this call overran
+    std::vector<int> overrun;                 // [S] AVCC input: the stream's chunk of this call overran; RTP: its packets faulted
+    std::vector<int32_t> rtp_expect;          // [S] ferhip_decs_decode_rtp: the sequence number the stream's next packet must carry, -1 = any
     double t_split = 0;                       // seconds in the host splitter
 };
 
@@ -71,6 +73,7 @@ extern "C" int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, in
     d->queued.assign(nstreams, 0);
     d->need_idr.assign(nstreams, 0);
     d->overrun.assign(nstreams, 0);
+    d->rtp_expect.assign(nstreams, -1);
     d->out.win[2] = width;
     d->out.win[3] = height;
     d->out.ofsz = d->ss.fsz;
@@ -98,6 +101,7 @@ extern "C" int ferhip_decs_reset_stream(ferhip_decs *d, int s)
 {
     if (!d || s < 0 || s >= d->S) return FERHIP_E_ARG;
     (void)hipSetDevice(d->ss.c->device);
+    d->rtp_expect[s] = -1;
     return decs_reset(d, s, true);
 }
 
@@ -293,22 +297,13 @@ extern "C" int ferhip_decs_decode(ferhip_decs *d, const uint8_t *const *chunks, 
     return decs_run(d, out, out_on_device, pictures, status);
 }
 
-extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out,
-                                      int out_on_device, int *pictures, int *status)
+// the last job of the decoder's splitter -> the unit lists: a unit's RBSP stays in the splitter's store, its prefix is on the host
+static int decs_take_table(ferhip_decs *d)
 {
-    if (!d || !d_chunks || !lens || !pictures || !status || decs_layout_check(d, out, out_on_device)) return FERHIP_E_ARG;
-    const int S = d->S;
     ferhip_ctx *c = d->ss.c;
-    if (hipSetDevice(c->device) != hipSuccess) return FERHIP_E_HIP;
-    if (!decs_begin_call(d, d_chunks, lens, pictures, status)) return 0;
-    // range s = the chunk of stream s: one set of launches splits them all into the decoder's store
-    const bool avcc = d->in_format == FERHIP_IN_AVCC;
-    int rc = fer_split_run(d->split, c->st, d_chunks, lens, S, nullptr, 0, avcc ? d->length_size : 0);
-    if (rc) return rc;
     const FerSplit &sp = d->split;
-    for (int s = 0; avcc && s < S; s++) d->overrun[s] = sp.h_fault[s];
     d->whole.clear();
-    rc = fer_split_each_unit(sp, [&](size_t k, const ferhip_nal_unit &u) -> int {
+    int rc = fer_split_each_unit(sp, [&](size_t k, const ferhip_nal_unit &u) -> int {
         NalRef n;
         n.type = u.nal_type;
         n.ref_idc = u.ref_idc;
@@ -329,6 +324,84 @@ extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_ch
     });
     if (rc) return rc;
     d->ss.dev_rbsp = sp.d_store;
+    return 0;
+}
+
+extern "C" int ferhip_decs_decode_dev(ferhip_decs *d, const uint8_t *const *d_chunks, const size_t *lens, uint8_t *out,
+                                      int out_on_device, int *pictures, int *status)
+{
+    if (!d || !d_chunks || !lens || !pictures || !status || decs_layout_check(d, out, out_on_device)) return FERHIP_E_ARG;
+    const int S = d->S;
+    ferhip_ctx *c = d->ss.c;
+    if (hipSetDevice(c->device) != hipSuccess) return FERHIP_E_HIP;
+    if (!decs_begin_call(d, d_chunks, lens, pictures, status)) return 0;
+    // range s = the chunk of stream s: one set of launches splits them all into the decoder's store
+    const bool avcc = d->in_format == FERHIP_IN_AVCC;
+    int rc = fer_split_run(d->split, c->st, d_chunks, lens, S, nullptr, 0, avcc ? d->length_size : 0);
+    if (rc) return rc;
+    for (int s = 0; avcc && s < S; s++) d->overrun[s] = d->split.h_fault[s];
+    if ((rc = decs_take_table(d))) return rc;
+    return decs_run(d, out, out_on_device, pictures, status);
+}
+
+// RTP packets (RFC 6184, packetization-mode 1), the packets of every stream in table order, into the same unit lists as the
+// other two framings: from host memory through split_rtp (no synchronisation of its own), from device memory through
+// fer_unrtp_run and the length-prefixed splitter (two).
+extern "C" int ferhip_decs_decode_rtp(ferhip_decs *d, const void *base, int base_on_device, const ferhip_rtp_pkt *pkts, size_t npkts,
+                                      uint8_t *out, int out_on_device, int *pictures, int *status)
+{
+    if (!d || !pictures || !status || (npkts && (!base || !pkts)) || decs_layout_check(d, out, out_on_device)) return FERHIP_E_ARG;
+    const int S = d->S;
+    for (size_t k = 0; k < npkts; k++)
+        if (pkts[k].stream >= (uint32_t)S) return FERHIP_E_ARG;
+    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
+    const uint8_t *const none = nullptr;
+    std::vector<const uint8_t *> no_chunks(S, none);
+    std::vector<size_t> no_lens(S, 0);
+    decs_begin_call(d, no_chunks.data(), no_lens.data(), pictures, status);
+    const double ts = dec_now();
+    std::vector<std::vector<RtpPacket>> per(S);  // a stable sort by stream
+    for (size_t k = 0; k < npkts && !base_on_device; k++) per[pkts[k].stream].push_back({(const uint8_t *)base + pkts[k].offset, pkts[k].bytes});
+    const std::vector<int32_t> before = d->rtp_expect;
+    bool too_many = false;
+    if (base_on_device && npkts) {
+        // parse, walk and gather on the device (fer_rtp.hip), then the length-prefixed splitter on the staged units: one
+        // synchronisation for the walk's results and one for the splitter's table
+        std::vector<ferhip_rtp_pkt> sorted;
+        std::vector<uint32_t> first;
+        std::vector<int32_t> fault(S, 0);
+        int rc = fer_rtp_sort(pkts, npkts, S, sorted, first);
+        if (!rc) rc = fer_unrtp_run(d->unrtp, d->ss.c->st, (const uint8_t *)base, sorted.data(), npkts, first.data(), S, d->rtp_expect.data(), fault.data());
+        size_t staged = 0;
+        for (int s = 0; s < S && !rc; s++) {
+            d->overrun[s] = fault[s] != 0;
+            staged += d->unrtp.lens[s];
+        }
+        if (!rc && staged) {
+            rc = fer_split_run(d->split, d->ss.c->st, d->unrtp.ptrs.data(), d->unrtp.lens.data(), S, nullptr, 0, 4);
+            if (!rc) rc = decs_take_table(d);
+        }
+        if (rc) {
+            d->rtp_expect = before;
+            return rc;
+        }
+    }
+    for (int s = 0; s < S; s++) {
+        if (!base_on_device && !per[s].empty())
+            d->overrun[s] = split_rtp(per[s].data(), per[s].size(), d->rtp_expect[s], d->nals[s], d->store[s]) != 0;
+        size_t slices = 0;
+        for (const NalRef &n : d->nals[s]) slices += n.type == 1 || n.type == 5;
+        too_many |= slices > (size_t)d->P;
+    }
+    d->t_split += dec_now() - ts;
+    if (too_many) {  // refused as a whole: nothing was taken
+        d->rtp_expect = before;
+        for (int s = 0; s < S; s++) {
+            d->nals[s].clear();
+            d->overrun[s] = 0;
+        }
+        return FERHIP_E_ARG;
+    }
     return decs_run(d, out, out_on_device, pictures, status);
 }
 

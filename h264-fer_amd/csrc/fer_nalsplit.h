@@ -70,6 +70,29 @@ inline void fer_split_free(FerSplit &sp)
     new (&sp) FerSplit();
 }
 
+// RTP packets in device memory (fer_rtp.hip): the buffers of the depacketiser in front of the splitter, each a DevBuf that
+// grows to the largest job seen and stays; one job at a time.
+struct FerUnrtp {
+    DevBuf<ferhip_rtp_pkt> d_pkts;   // [npk] the table, sorted by stream ...
+    PinBuf<ferhip_rtp_pkt> h_pkts;   // ... as the host writes it
+    DevBuf<uint4> d_rec;             // [npk] what k_unrtp_parse reads of every packet's header
+    DevBuf<uint4> d_piece;           // [npk] what k_unrtp_gather copies for every packet: source, bytes, place in the staging range
+    DevBuf<uint32_t> d_job;          // [4][S]: first packet (S + 1), staging base, expectation in
+    PinBuf<uint32_t> h_job;
+    DevBuf<int32_t> d_res;           // [3][S]: staged bytes, fault, expectation out
+    PinBuf<int32_t> h_res;
+    DevBuf<uint8_t> d_stage;         // every stream's units behind 4-byte lengths: the ranges fer_split_run takes
+    std::vector<const uint8_t *> ptrs;  // [S] the last job's staging ranges
+    std::vector<size_t> lens;
+};
+// pkts[npk] (host) sorted by stream, first[S + 1] = every stream's first row; the packets lie at d_base + offset.  Parses,
+// walks (expect[S]: in the expectation or -1, out the next one or -1 after a fault; fault[S]: 0, 2, 3, 4) and gathers every
+// stream's units behind 4-byte lengths into u.ptrs / u.lens, on stream st.  One host synchronisation.
+int fer_unrtp_run(FerUnrtp &u, hipStream_t st, const uint8_t *d_base, const ferhip_rtp_pkt *pkts, size_t npk, const uint32_t *first, int S,
+                  int32_t *expect, int32_t *fault);
+// a stable sort of the caller's table by stream, and every stream's first row; FERHIP_E_ARG for a stream outside [0, S)
+int fer_rtp_sort(const ferhip_rtp_pkt *pkts, size_t npk, int S, std::vector<ferhip_rtp_pkt> &sorted, std::vector<uint32_t> &first);
+
 // The empty-payload cut of split_stream (fer_dec_syntax_host.h), which the device leaves to the host: a unit with bytes == 0
 // ends its range, and the later units of that range are skipped.  f(k, unit) for every entry k of the last job's table that
 // stays, in table order, until one returns non-zero; returns that value, or 0.

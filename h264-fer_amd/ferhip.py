@@ -55,6 +55,19 @@ AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.int3
 NAL_UNIT = np.dtype([("range", np.uint32), ("nal_type", np.int32), ("ref_idc", np.int32), ("bytes", np.uint32), ("offset", np.uint64)])
 SPLIT_PREFIX = 64  # FERHIP_SPLIT_PREFIX: bytes of every unit's RBSP that decode_dev parses headers from
 assert AU.itemsize == 16
+# ferhip_rtp_hdr, ferhip_rtp_pkt, ferhip_rtp_au: the caller's RTP header fields per stream, one row of the packet table, one
+# entry of the index of ferhip_pack_rtp / ferhip_fetch_rtp / ferhip_rtp_blocks
+RTP_HDR = np.dtype([("ssrc", np.uint32), ("timestamp", np.uint32), ("seq", np.uint16), ("payload_type", np.uint8), ("reserved", np.uint8)])
+RTP_PKT = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("stream", np.uint32)])
+RTP_AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.int32), ("first_pkt", np.uint32), ("npkts", np.uint32)])
+assert (RTP_HDR.itemsize, RTP_PKT.itemsize, RTP_AU.itemsize) == (12, 16, 24)
+
+
+def rtp_hdr(n, ssrc=0, timestamp=0, seq=0, payload_type=96):
+    """n entries of dtype RTP_HDR; every argument a scalar or a sequence of n"""
+    h = np.zeros(n, RTP_HDR)
+    h["ssrc"], h["timestamp"], h["seq"], h["payload_type"] = ssrc, timestamp, seq, payload_type
+    return h
 
 
 class Quality:
@@ -140,6 +153,11 @@ def load_library():
     lib.ferhip_frame_nal_blocks_fmt.argtypes = [vp, sz, vp, vp, sz, i, vp, sz, vp]
     lib.ferhip_write_avcc_config.argtypes = [vp, i, vp, sz]
     lib.ferhip_write_avcc_config.restype = sz
+    lib.ferhip_pack_rtp.argtypes = [vp, i, i, vp, vp, sz, vp, sz, vp]
+    lib.ferhip_fetch_rtp.argtypes = [vp, i, i, vp, vp, sz, vp, sz, vp]
+    lib.ferhip_rtp_blocks.argtypes = [vp, sz, vp, vp, sz, i, vp, vp, sz, vp, sz, vp]
+    lib.ferhip_write_sdp_fmtp.argtypes = [vp, i, vp, sz]
+    lib.ferhip_write_sdp_fmtp.restype = sz
     lib.ferhip_get_stats.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_status.argtypes = [vp, C.POINTER(i)]
     lib.ferhip_fill_interpolated.argtypes = [vp]
@@ -163,6 +181,8 @@ def load_library():
     lib.ferhip_decs_set_layout.argtypes = [vp, i, C.c_uint32, C.c_uint32]
     lib.ferhip_decs_set_csc.argtypes = [vp, i]
     lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_decs_decode_rtp.argtypes = [vp, vp, i, vp, sz, vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_unrtp_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz, C.POINTER(sz), vp, vp]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
     lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
     lib.ferhip_split_avcc_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, sz, vp, sz, C.POINTER(sz), vp]
@@ -512,6 +532,54 @@ class FerHip:
         return ([bytes(buf[int(idx["offset"][s]): int(idx["offset"][s]) + int(idx["bytes"][s])]) for s in range(self.S)],
                 [int(t) for t in idx["nal_type"][: self.S]])
 
+    # --- RTP packets on the device
+    def pack_rtp_device(self, hdr, max_packet, dst_ptr, cap, pkts_ptr, pkts_cap, index_ptr, flags=0):
+        """ferhip_pack_rtp: the last picture's RTP packets (RFC 6184, packetization-mode 1) -> device memory at dst_ptr
+        (16-byte aligned, cap bytes), their table (pkts_cap rows of dtype RTP_PKT) at pkts_ptr and the index (S + 1 records of
+        dtype RTP_AU) at index_ptr, on the library's stream (asynchronous; sync() before reading).  hdr: S entries of dtype
+        RTP_HDR (rtp_hdr); the caller advances seq by index[s].npkts."""
+        h = np.ascontiguousarray(hdr, RTP_HDR)
+        assert h.size == self.S
+        _chk(self.lib.ferhip_pack_rtp(self.ctx, int(flags), int(max_packet), h.ctypes.data, C.c_void_p(int(dst_ptr) if dst_ptr else None),
+                                      int(cap), C.c_void_p(int(pkts_ptr) if pkts_ptr else None), int(pkts_cap), C.c_void_p(int(index_ptr))),
+             "ferhip_pack_rtp")
+
+    def fetch_rtp_raw(self, hdr, max_packet, cap, pkts_cap, flags=0, fill=0):
+        """ferhip_fetch_rtp into new host buffers -> (return code, buffer [cap], table [pkts_cap] of dtype RTP_PKT, index
+        [S + 1] of dtype RTP_AU)"""
+        h = np.ascontiguousarray(hdr, RTP_HDR)
+        assert h.size == self.S
+        buf = np.full(max(int(cap), 1), fill, np.uint8)
+        pkts = np.zeros(max(int(pkts_cap), 1), RTP_PKT)
+        idx = np.zeros(self.S + 1, RTP_AU)
+        rc = self.lib.ferhip_fetch_rtp(self.ctx, int(flags), int(max_packet), h.ctypes.data, buf.ctypes.data, int(cap), pkts.ctypes.data,
+                                       int(pkts_cap), idx.ctypes.data)
+        return rc, buf, pkts, idx
+
+    def fetch_rtp(self, hdr, max_packet=1400, flags=0):
+        """The last picture of every stream as RTP packets (waits) -> (list per stream of the packets as bytes, [] for the
+        streams without a picture; the index of dtype RTP_AU).  With AU_PARAM_SETS an IDR slice follows a STAP-A packet with
+        the SPS and the stream's PPS."""
+        cap, pcap = getattr(self, "_rtp_cap", (1 << 20, 1 << 12))
+        rc, buf, pkts, idx = self.fetch_rtp_raw(hdr, max_packet, cap, pcap, flags)
+        if rc == -1 and (int(idx["offset"][self.S]) > cap or int(idx["first_pkt"][self.S]) > pcap):  # a true index: too small
+            cap, pcap = self._rtp_cap = (max(cap, 2 * int(idx["offset"][self.S])), max(pcap, 2 * int(idx["first_pkt"][self.S])))
+            rc, buf, pkts, idx = self.fetch_rtp_raw(hdr, max_packet, cap, pcap, flags)
+        _chk(rc, "ferhip_fetch_rtp")
+        out = []
+        for s in range(self.S):
+            rows = pkts[int(idx["first_pkt"][s]): int(idx["first_pkt"][s]) + int(idx["npkts"][s])]
+            out.append([bytes(buf[int(r["offset"]): int(r["offset"]) + int(r["bytes"])]) for r in rows])
+        return out, idx
+
+    def sdp_fmtp(self, stream):
+        """ferhip_write_sdp_fmtp: the format parameters of a stream for an SDP a=fmtp line"""
+        o = C.create_string_buffer(512)
+        n = self.lib.ferhip_write_sdp_fmtp(self.ctx, int(stream), o, 512)
+        if n == 0:
+            raise FerHipError(f"ferhip_write_sdp_fmtp({stream}) failed")
+        return o.raw[:n].decode()
+
     # --- rate control
     def set_rate(self, stream=-1, mode=RC_CQP, qp=None, qp_min=0, qp_max=51, max_step=2, ip_offset=3, window=0,
                  target_bits=0, target_sse=0, target_psnr=None):
@@ -853,6 +921,56 @@ def frame_nal_blocks_raw(payloads, nal_types, cap=None, fill=0xA5, flags=None):
     return rc, out, idx
 
 
+def rtp_blocks_raw(payloads, nal_types, max_packet, hdr, cap=None, pkts_cap=None, fill=0xA5):
+    """ferhip_rtp_blocks on a list of payloads (bytes or uint8 arrays), one slice unit each -> (return code, out [cap]
+    pre-filled with `fill`, table [pkts_cap] of dtype RTP_PKT pre-filled with `fill`, index [n + 1] of dtype RTP_AU).
+    cap / pkts_cap None = room for every payload with every second byte escaped."""
+    lib = load_library()
+    n = len(payloads)
+    lens = np.array([len(p) for p in payloads], np.uint32)
+    stride = max(int(lens.max()) if n else 0, 1)
+    src = np.zeros((n, stride), np.uint8)
+    for k, p in enumerate(payloads):
+        src[k, : len(p)] = np.frombuffer(bytes(p), np.uint8) if not isinstance(p, np.ndarray) else p
+    worst = [int(m) * 3 // 2 + 2 for m in lens]  # header byte + escaped payload
+    frag = max(int(max_packet) - 14, 1)
+    if pkts_cap is None:
+        pkts_cap = sum(w // frag + 1 for w in worst)
+    if cap is None:
+        cap = sum((w // frag + 1) * ((int(max_packet) + 15) & ~15) for w in worst)
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    pkts = np.full(max(int(pkts_cap), 1) * RTP_PKT.itemsize, fill, np.uint8).view(RTP_PKT)
+    idx = np.zeros(n + 1, RTP_AU)
+    h = np.ascontiguousarray(hdr, RTP_HDR)
+    nt = np.ascontiguousarray(nal_types, np.int32)
+    rc = lib.ferhip_rtp_blocks(src.ctypes.data, stride, lens.ctypes.data, nt.ctypes.data, n, int(max_packet), h.ctypes.data,
+                               out.ctypes.data, int(cap), pkts.ctypes.data, int(pkts_cap), idx.ctypes.data)
+    return rc, out, pkts, idx
+
+
+def unrtp_blocks_raw(base, pkts, nstreams, seq_expect=None, misalign=0, cap=None, units_cap=None, fill=0xA5):
+    """ferhip_unrtp_blocks: RTP packets in `base` (bytes or a uint8 array) by the table `pkts` (rows of dtype RTP_PKT) through
+    the device depacketiser and splitter -> (return code, out [cap] pre-filled with `fill`, units [units_cap] of dtype
+    NAL_UNIT with range = the stream, the true unit count, fault [nstreams], seq_next [nstreams]).  seq_expect None = no
+    expectation; cap / units_cap None = room for everything."""
+    lib = load_library()
+    b = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+    rows = np.ascontiguousarray(pkts, RTP_PKT)
+    exp = np.full(nstreams, -1, np.int32) if seq_expect is None else np.ascontiguousarray(seq_expect, np.int32)
+    if cap is None:
+        cap = int(b.size) + 16 * int(b.size // 3 + rows.size + 1)
+    if units_cap is None:
+        units_cap = int(b.size // 3 + rows.size + 1)
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    units = np.zeros(max(int(units_cap), 1), NAL_UNIT)
+    fault, nxt = np.zeros(nstreams, np.int32), np.zeros(nstreams, np.int32)
+    count = C.c_size_t(0)
+    rc = lib.ferhip_unrtp_blocks(b.ctypes.data if b.size else None, b.size, rows.ctypes.data if rows.size else None, rows.size, int(nstreams),
+                                 int(misalign), exp.ctypes.data, out.ctypes.data, int(cap), units.ctypes.data, int(units_cap), C.byref(count),
+                                 fault.ctypes.data, nxt.ctypes.data)
+    return rc, out, units, count.value, fault, nxt
+
+
 def split_nal_blocks_raw(ranges, misalign=0, cap=None, units_cap=None, fill=0xA5):
     """ferhip_split_nal_blocks on a list of byte ranges (bytes or uint8 arrays) -> (return code, out [cap] pre-filled with
     `fill`, units [min(count, units_cap)] of dtype NAL_UNIT, true count).  cap None = room for every range with every unit
@@ -1077,6 +1195,25 @@ class LiveDecoder:
             arr = (C.c_void_p * self.S)(*[int(c) if c else None for c in chunks])
             lens = (C.c_size_t * self.S)(*[int(n) if c else 0 for c, n in zip(chunks, dev_lens)])
             _chk(self.lib.ferhip_decs_decode_dev(self.h, arr, lens, C.c_void_p(ptr), on_dev, pics, status), "ferhip_decs_decode_dev")
+        return out, list(pics), list(status)
+
+    def decode_rtp(self, base, pkts, out=None, base_on_device=False):
+        """ferhip_decs_decode_rtp: RTP packets (RFC 6184, packetization-mode 1) -> (out, pictures, status) like decode().
+        base: the bytes that hold the packets (bytes or a uint8 array; an integer device address with base_on_device);
+        pkts: rows of dtype RTP_PKT (offset from base, bytes, stream) in arrival order.  out: a host uint8 array or None."""
+        if base_on_device:
+            ptr_in = int(base)
+        else:
+            keep = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+            ptr_in = keep.ctypes.data if keep.size else None
+        rows = np.ascontiguousarray(pkts, RTP_PKT)
+        if out is None:
+            out = np.zeros((self.P, self.S, self.fsz), np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < self.P * self.S * self.fsz:
+            raise FerHipError("LiveDecoder.decode_rtp: out must be a C-contiguous uint8 array of [max_pictures][S][W*H*3/2]")
+        pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
+        _chk(self.lib.ferhip_decs_decode_rtp(self.h, C.c_void_p(ptr_in), int(bool(base_on_device)), rows.ctypes.data if rows.size else None,
+                                             rows.size, C.c_void_p(out.ctypes.data), 0, pics, status), "ferhip_decs_decode_rtp")
         return out, list(pics), list(status)
 
     def decode_dev(self, ptrs, lens, out=None):

@@ -306,6 +306,56 @@ int ferhip_frame_nal_blocks_fmt(const uint8_t *payloads, size_t stride, const ui
                                 size_t n, int flags, uint8_t *out, size_t cap, ferhip_au *index /* [n+1] */);
 size_t ferhip_write_avcc_config(ferhip_ctx *c, int s, uint8_t *out, size_t cap);
 
+/* ---- RTP packets on the device: the coded pictures in the payload format of RFC 6184, packetization-mode 1 ----
+ * The third framing of the same pictures, for the wire: every NAL unit becomes datagrams of at most max_packet bytes.
+ * Let P = max_packet (the whole datagram with its 12-byte RTP header, 80 <= P <= 65535), B = P - 12 and F = B - 2.
+ * A stream that coded a picture in the context's last ferhip_encode_picture[_dev] call has one access unit.  Its units, in
+ * order: with FERHIP_AU_PARAM_SETS and in front of an IDR slice only, the SPS and the stream's own PPS; then the slice.  A
+ * unit is its header byte h (1 << 5 | type) and the payload with its emulation prevention bytes: the N bytes that
+ * ferhip_write_nal writes behind the start code.  The packets:
+ *   parameter sets   one STAP-A packet: the byte 0x20 | 24, then for the SPS and then the PPS a big-endian u16 size and the
+ *                    unit.  It always fits: a context's two parameter sets are at most 63 bytes with their start codes.
+ *   slice, N <= B    one single-NAL packet whose payload is the unit;
+ *   slice, N > B     n = ceil((N - 1) / F) >= 2 FU-A packets; packet k carries the indicator (h & 0xE0) | 28, the FU header
+ *                    S << 7 | E << 6 | (h & 0x1F) with S on k = 0 and E on k = n - 1, and the unit's bytes
+ *                    [1 + k F, 1 + min((k + 1) F, N - 1)).
+ * RTP header of every packet: 0x80, M << 7 | payload_type, seq + (index of the packet within its stream) mod 65536,
+ * timestamp, ssrc, all big-endian; M = 1 on the last packet of the stream's access unit and on no other.
+ * The library keeps no RTP state: hdr[s] (host, S entries, those of streams without a picture included) is read before the
+ * call returns, and the caller advances seq by index[s].npkts, which it reads anyway to send the packets; a repeated call
+ * with the same hdr gives the same bytes.
+ * Layout: stream order, then packet order; every packet starts at a multiple of 16, and the bytes between a packet's end
+ * and the next multiple of 16 are not written.  pkts[k] = (offset, bytes, stream).  index[s] = (offset of the stream's
+ * first packet, sum of its packets' sizes each rounded up to 16, NAL unit type of the slice, first_pkt, npkts); a stream
+ * without a picture has zeros.  index[S] = (total bytes, number of streams written, 0, total packets, 0).
+ * Overflow is ferhip_pack_nal's rule, per stream: the index always holds the true values; a stream's packets and table
+ * rows are written all or none, only if they end within both cap (offset + bytes <= cap) and pkts_cap (first_pkt + npkts
+ * <= pkts_cap); nothing at or beyond either is touched.  ferhip_pack_rtp then still returns 0, ferhip_fetch_rtp fills
+ * h_index and returns FERHIP_E_ARG.
+ * FERHIP_E_ARG: payload_type > 127, reserved != 0, P out of range, a flag other than FERHIP_AU_PARAM_SETS, a null c, hdr
+ * or index, a null buffer with a cap, and for ferhip_pack_rtp a d_dst not aligned to 16 or d_pkts / d_index not aligned to
+ * 8.  FERHIP_E_STATE before the context's first picture.
+ * ferhip_pack_rtp: device to device, asynchronous on the context's stream; it waits for nothing except a context's first
+ * call's allocations.  ferhip_fetch_rtp: the same bytes and table in host memory; it waits once for the index and once for
+ * the two copies.  Packing changes nothing the encoder reads and may be mixed with the other framings.
+ * ferhip_rtp_blocks: known-answer surface with the conventions of ferhip_frame_nal_blocks: host payloads, one slice unit
+ * each (no parameter sets), hdr[n], n <= 65535, and bytes and rows the kernels do not write keep the caller's values.
+ * ferhip_write_sdp_fmtp (host): the format parameters of stream s for an SDP a=fmtp line,
+ * profile-level-id=%02x%02x%02x;packetization-mode=1;sprop-parameter-sets=<base64 SPS unit>,<base64 PPS unit> -- the hex
+ * bytes are the first three bytes of the SPS RBSP, the units those of ferhip_write_avcc_config, base64 with padding.
+ * Returns the length (out is 0-terminated behind it), 0 if cap is too small or s is out of range. */
+typedef struct { uint32_t ssrc, timestamp; uint16_t seq; uint8_t payload_type, reserved; } ferhip_rtp_hdr; /* 12 bytes, host */
+typedef struct { uint64_t offset; uint32_t bytes; uint32_t stream; } ferhip_rtp_pkt;                        /* 16 bytes */
+typedef struct { uint64_t offset; uint32_t bytes; int32_t nal_type; uint32_t first_pkt, npkts; } ferhip_rtp_au; /* 24 bytes */
+int ferhip_pack_rtp(ferhip_ctx *c, int flags, int max_packet, const ferhip_rtp_hdr *hdr /* host [S] */, void *d_dst, size_t cap,
+                    ferhip_rtp_pkt *d_pkts, size_t pkts_cap, ferhip_rtp_au *d_index /* [S+1] */);
+int ferhip_fetch_rtp(ferhip_ctx *c, int flags, int max_packet, const ferhip_rtp_hdr *hdr, void *h_dst, size_t cap,
+                     ferhip_rtp_pkt *h_pkts, size_t pkts_cap, ferhip_rtp_au *h_index);
+int ferhip_rtp_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type, size_t n,
+                      int max_packet, const ferhip_rtp_hdr *hdr /* [n] */, uint8_t *out, size_t cap, ferhip_rtp_pkt *pkts,
+                      size_t pkts_cap, ferhip_rtp_au *index /* [n+1] */);
+size_t ferhip_write_sdp_fmtp(ferhip_ctx *c, int s, char *out, size_t cap);
+
 /* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134), each stream with its own PPS:
  * frames host [T][S][W*H*3/2]; out host [S][out_stride] Annex-B; out_len[S].
  * recon (optional) host [T][S][W*H*3/2]. */
@@ -677,6 +727,46 @@ int ferhip_decs_set_config(ferhip_decs *d, int s, const uint8_t *avcc, size_t n)
 int ferhip_split_avcc_blocks(const uint8_t *ranges, size_t stride, const uint32_t *lens, size_t n, int misalign, int length_size,
                              uint8_t *out, size_t cap, ferhip_nal_unit *units, size_t units_cap, size_t *nunits,
                              int32_t *range_fault /* [n], may be NULL */);
+
+/* ---- RTP input: the live decoder takes the packets of RFC 6184 (packetization-mode 1) where a receiver has them ----
+ * A packet is pkts[k].bytes bytes at base + pkts[k].offset, at any alignment; the packets of stream pkts[k].stream are
+ * taken in table order, and streams may interleave: the table ferhip_pack_rtp writes, and what recvmmsg leaves.
+ * Per stream the state is the expected sequence number (none at first) and an open FU-A unit (none).  For a packet of L
+ * bytes:
+ *   1. header: L >= 12 and version b0 >> 6 == 2, else malformed.  hl = 12 + 4 CC; with X another 4 + 4 * (the u16 at
+ *      hl + 2), which must lie within the packet; with the P bit pad = the last byte, >= 1; hl + pad < L, else malformed.
+ *      The payload is [hl, L - pad).  The payload type and M are not looked at.
+ *   2. sequence: with an expectation that seq differs from, a gap.  Then the expectation is seq + 1 mod 65536.
+ *   3. payload, t = payload[0] & 31.  1..23: the payload is one unit.  24 (STAP-A): behind the first byte [u16 size][unit]
+ *      to the payload's end, at least one; a size of 0 or one that overruns is malformed (the units in front of it stand).
+ *      28 (FU-A): at least 2 bytes; S and E together are malformed; S opens a unit with the header byte
+ *      (payload[0] & 0xE0) | (payload[1] & 0x1F); the bytes behind the FU header are appended (there may be none); E
+ *      closes it; a fragment without S while none is open, S while one is open, and any other type while one is open are
+ *      malformed.  Every other t is malformed.
+ *   4. a unit still open when the stream's packets of this call end is truncated: a call takes whole access units.
+ * The first fault ends the stream's walk (2 malformed, 3 gap, 4 truncated; 1 is the overrun of the length walk); the units
+ * completed in front of it stand, and the expectation is cleared.  The units then are units of the length-prefixed
+ * definition above (steps 5 to 6): header byte, RBSP without emulation prevention bytes -- one that lies across a fragment
+ * seam included -- and a unit without payload ends the stream's units of the call.
+ * ferhip_decs_decode_rtp: pictures, pictures[], status[] and the isolation rules are those of ferhip_decs_decode given the
+ * same NAL units in Annex-B.  Every fault gives status[s] = FERHIP_E_ARG: the units in front of it decode, the stream
+ * restarts at its next IDR slice, the other streams are untouched.  ferhip_decs_reset_stream clears the expectation.
+ * FERHIP_E_ARG for the call, before anything is taken: pkts[k].stream >= S, a stream with more than max_pictures slices,
+ * null pointers.  It may be mixed freely with the other decode calls.
+ * base_on_device = 0: the depacketiser runs on the host (no synchronisation of its own).  base_on_device = 1: base is device
+ * memory on the decoder's device, and nothing but the table crosses the bus: the table is sorted by stream on the host, one
+ * lane per packet parses its header, one wavefront per stream walks the sequence numbers and the FU-A state, the payloads
+ * are gathered behind 4-byte lengths into a staging range per stream, and the length-prefixed splitter above does the rest.
+ * Two host synchronisations: one for the walk's results, one for the splitter's table (more only when a buffer had to grow).
+ * ferhip_unrtp_blocks: known-answer surface of that path, context-free like ferhip_split_avcc_blocks.  The packets lie in
+ * base[0, base_bytes) (host; copied to device memory `misalign` bytes behind a 16-byte boundary; a row that leaves it is
+ * FERHIP_E_ARG); seq_expect[s] = the expectation stream s starts with, -1 = none; fault[s] and seq_next[s] (-1 after a fault)
+ * come back; out, units (units[k].range = the stream), *nunits and the overflow rule are ferhip_split_avcc_blocks'. */
+int ferhip_decs_decode_rtp(ferhip_decs *d, const void *base, int base_on_device, const ferhip_rtp_pkt *pkts /* host */, size_t npkts,
+                           uint8_t *out, int out_on_device, int *pictures, int *status);
+int ferhip_unrtp_blocks(const uint8_t *base, size_t base_bytes, const ferhip_rtp_pkt *pkts, size_t npkts, int nstreams, int misalign,
+                        const int32_t *seq_expect /* [nstreams], -1 = none */, uint8_t *out, size_t cap, ferhip_nal_unit *units,
+                        size_t units_cap, size_t *nunits, int32_t *fault /* [nstreams] */, int32_t *seq_next /* [nstreams] */);
 
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
