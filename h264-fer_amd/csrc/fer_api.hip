@@ -264,7 +264,7 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
     if (c->nal_buf) hipFree(c->nal_buf);
     for (void *p : c->pinned) hipHostFree(p);
     for (hipEvent_t e : c->events) hipEventDestroy(e);
-    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring, &c->pic_ring, &c->rtp_ring}) r->destroy();
+    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring, &c->pic_ring, &c->rtp_ring, &c->ts_ring, &c->ts_psi_ring}) r->destroy();
     for (hipStream_t st : {c->st, c->st_hi, c->st_aux, c->st_copy})
         if (st) hipStreamDestroy(st);
     delete c;

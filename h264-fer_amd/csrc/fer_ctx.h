@@ -1,5 +1,5 @@
 // fer_ctx.h -- the context of libferhip and the owners of its resources, for the host translation units that drive it
-// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_rtp.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
+// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_rtp.hip, fer_ts.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
 // fer_mbunit.hip, every buffer of which is a DevBuf).
 #pragma once
 #include "fer_internal.h"
@@ -142,6 +142,16 @@ struct ferhip_ctx {
     DevBuf<uint8_t> rtp_buf;           // ferhip_fetch_rtp's packets and table on the device, regrown when a picture needs more
     DevBuf<ferhip_rtp_pkt> rtp_pkts;
     bool rtp_ready = false;            // the four above exist
+    // transport stream packets (fer_ts.hip), on first use, as the RTP members above; the PSI table only once FERHIP_TS_PSI
+    // was asked for
+    ferhip_ts_au *ts_index = nullptr, *h_ts_index = nullptr;  // device / pinned [S + 1]: ferhip_fetch_ts's index
+    ferhip_ts_hdr *d_ts_hdr = nullptr;  // device [S]
+    PinnedRing ts_ring;                // [S] ferhip_ts_hdr
+    DevBuf<uint8_t> ts_buf;            // ferhip_fetch_ts's packets on the device, regrown when a picture needs more
+    bool ts_ready = false;             // the four above exist
+    uint8_t *d_ts_psi = nullptr;       // device [S][376]: every stream's PAT and PMT packet
+    PinnedRing ts_psi_ring;            // [S][376]
+    std::vector<uint32_t> ts_psi_ids;  // [S] pid << 16 | pmt_pid of the stream's row, 0 = none yet (empty until the table exists)
     // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof = false;
     struct Span { int phase; hipEvent_t a, b; long launches; };

@@ -370,6 +370,74 @@ static inline int split_rtp(const RtpPacket *pk, size_t npk, int32_t &expect, st
     return open ? fault(FER_RTP_TRUNCATED) : 0;
 }
 
+// The transport stream packets of one stream's runs, in order (ISO/IEC 13818-1; the definition: ferhip.h) -> its NAL units
+// like split_stream.  Every run is a whole number of 188-byte packets; pid: the PID the stream listens to; expect: the
+// continuity counter the first payload packet must carry, -1 = any; it leaves as the one behind the last payload packet, or
+// -1 after a fault.  Returns the fault: 0, or the first of FER_TS_MALFORMED and FER_TS_GAP, which ends the walk; the PES
+// packets completed in front of it stand, the open one is dropped.  The elementary-stream bytes that stand are joined in
+// `es` and split as one Annex-B range.
+#define FER_TS_MALFORMED 2
+#define FER_TS_GAP 3
+typedef RtpPacket TsRun;
+static inline int split_ts(const TsRun *runs, size_t nruns, unsigned pid, int32_t &expect, std::vector<NalRef> &out, std::vector<uint8_t> &store)
+{
+    std::vector<uint8_t> es;
+    size_t pes_at = 0;  // where the open PES packet's bytes begin in es
+    bool open = false;
+    int fault = 0;
+    for (size_t r = 0; r < nruns && !fault; r++) {
+        for (size_t at = 0; at + 188 <= runs[r].n && !fault; at += 188) {
+            const uint8_t *p = runs[r].p + at;
+            if (p[0] != 0x47 || (p[1] & 0x80)) {
+                fault = FER_TS_MALFORMED;
+                break;
+            }
+            if ((((unsigned)p[1] & 0x1F) << 8 | p[2]) != pid) continue;
+            const unsigned afc = (p[3] >> 4) & 3;
+            if (p[3] >> 6 || afc == 0) {
+                fault = FER_TS_MALFORMED;
+                break;
+            }
+            if (afc == 2) continue;
+            size_t pay = 4;
+            if (afc == 3) {
+                if (p[4] > 183) {
+                    fault = FER_TS_MALFORMED;
+                    break;
+                }
+                pay = 5 + (size_t)p[4];
+            }
+            const int32_t cc = p[3] & 15;
+            if (expect >= 0 && cc != expect) {
+                fault = FER_TS_GAP;
+                break;
+            }
+            expect = (cc + 1) & 15;
+            const size_t n = 188 - pay;
+            const uint8_t *q = p + pay;
+            if (p[1] & 0x40) {
+                if (n < 9 || q[0] != 0 || q[1] != 0 || q[2] != 1 || (q[3] & 0xF0) != 0xE0 || (q[6] & 0xC0) != 0x80 || n < 9 + (size_t)q[8]) {
+                    fault = FER_TS_MALFORMED;
+                    break;
+                }
+                open = true;
+                pes_at = es.size();
+                es.insert(es.end(), q + 9 + q[8], q + n);
+            } else if (!open) {
+                fault = FER_TS_MALFORMED;
+            } else {
+                es.insert(es.end(), q, q + n);
+            }
+        }
+    }
+    if (fault) {
+        expect = -1;
+        if (open) es.resize(pes_at);
+    }
+    if (!es.empty()) split_stream(es.data(), es.size(), out, store);
+    return fault;
+}
+
 // AVCDecoderConfigurationRecord avcc[0, n) -> the (at, len) spans of its SPS, then of its PPS units (header byte included) and
 // the longest.  FERHIP_E_ARG: another version, a record that ends inside a count, length or unit, a count or length of zero.
 struct AvccSpan { size_t at, len; };

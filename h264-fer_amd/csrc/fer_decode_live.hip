@@ -19,6 +19,8 @@ struct ferhip_decs {
     int in_format = FERHIP_IN_ANNEXB, length_size = 4;  // ferhip_decs_set_input
     std::vector<int> overrun;                 // [S] AVCC input: the stream's chunk of this call overran; RTP: its packets faulted
     std::vector<int32_t> rtp_expect;          // [S] ferhip_decs_decode_rtp: the sequence number the stream's next packet must carry, -1 = any
+    FerUnts unts;                             // ferhip_decs_decode_ts from device memory: the demultiplexer's buffers in front of the splitter
+    std::vector<int32_t> ts_expect;           // [S] ferhip_decs_decode_ts: the continuity counter the stream's next payload packet must carry, -1 = any
     double t_split = 0;                       // seconds in the host splitter
 };
 
@@ -74,6 +76,7 @@ extern "C" int ferhip_decs_create(ferhip_decs **out, int nstreams, int width, in
     d->need_idr.assign(nstreams, 0);
     d->overrun.assign(nstreams, 0);
     d->rtp_expect.assign(nstreams, -1);
+    d->ts_expect.assign(nstreams, -1);
     d->out.win[2] = width;
     d->out.win[3] = height;
     d->out.ofsz = d->ss.fsz;
@@ -102,6 +105,7 @@ extern "C" int ferhip_decs_reset_stream(ferhip_decs *d, int s)
     if (!d || s < 0 || s >= d->S) return FERHIP_E_ARG;
     (void)hipSetDevice(d->ss.c->device);
     d->rtp_expect[s] = -1;
+    d->ts_expect[s] = -1;
     return decs_reset(d, s, true);
 }
 
@@ -396,6 +400,69 @@ extern "C" int ferhip_decs_decode_rtp(ferhip_decs *d, const void *base, int base
     d->t_split += dec_now() - ts;
     if (too_many) {  // refused as a whole: nothing was taken
         d->rtp_expect = before;
+        for (int s = 0; s < S; s++) {
+            d->nals[s].clear();
+            d->overrun[s] = 0;
+        }
+        return FERHIP_E_ARG;
+    }
+    return decs_run(d, out, out_on_device, pictures, status);
+}
+
+// Transport stream packets (ISO/IEC 13818-1), the runs of every stream in table order, into the same unit lists as the other
+// framings: from host memory through split_ts (no synchronisation of its own), from device memory through fer_unts_run and
+// the Annex-B splitter (two).
+extern "C" int ferhip_decs_decode_ts(ferhip_decs *d, const void *base, int base_on_device, const ferhip_ts_run *runs, size_t nruns,
+                                     const uint16_t *pids, uint8_t *out, int out_on_device, int *pictures, int *status)
+{
+    if (!d || !pictures || !status || !pids || (nruns && (!base || !runs)) || decs_layout_check(d, out, out_on_device)) return FERHIP_E_ARG;
+    const int S = d->S;
+    for (size_t k = 0; k < nruns; k++)
+        if (runs[k].stream >= (uint32_t)S || runs[k].bytes % 188u) return FERHIP_E_ARG;
+    for (int s = 0; s < S; s++)
+        if (pids[s] > 0x1FFF) return FERHIP_E_ARG;
+    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
+    const uint8_t *const none = nullptr;
+    std::vector<const uint8_t *> no_chunks(S, none);
+    std::vector<size_t> no_lens(S, 0);
+    decs_begin_call(d, no_chunks.data(), no_lens.data(), pictures, status);
+    const double ts = dec_now();
+    std::vector<std::vector<TsRun>> per(S);  // a stable sort by stream
+    for (size_t k = 0; k < nruns && !base_on_device; k++) per[runs[k].stream].push_back({(const uint8_t *)base + runs[k].offset, runs[k].bytes});
+    const std::vector<int32_t> before = d->ts_expect;
+    bool too_many = false;
+    if (base_on_device && nruns) {
+        // parse, walk and gather on the device (fer_ts.hip), then the Annex-B splitter on the staged bytes: one
+        // synchronisation for the walk's results and one for the splitter's table
+        std::vector<ferhip_ts_run> sorted;
+        std::vector<uint32_t> first;
+        std::vector<int32_t> fault(S, 0);
+        int rc = fer_rtp_sort(runs, nruns, S, sorted, first);
+        if (!rc) rc = fer_unts_run(d->unts, d->ss.c->st, (const uint8_t *)base, sorted.data(), nruns, first.data(), S, pids, d->ts_expect.data(), fault.data());
+        size_t staged = 0;
+        for (int s = 0; s < S && !rc; s++) {
+            d->overrun[s] = fault[s] != 0;
+            staged += d->unts.lens[s];
+        }
+        if (!rc && staged) {
+            rc = fer_split_run(d->split, d->ss.c->st, d->unts.ptrs.data(), d->unts.lens.data(), S, nullptr, 0, 0);
+            if (!rc) rc = decs_take_table(d);
+        }
+        if (rc) {
+            d->ts_expect = before;
+            return rc;
+        }
+    }
+    for (int s = 0; s < S; s++) {
+        if (!base_on_device && !per[s].empty())
+            d->overrun[s] = split_ts(per[s].data(), per[s].size(), pids[s], d->ts_expect[s], d->nals[s], d->store[s]) != 0;
+        size_t slices = 0;
+        for (const NalRef &n : d->nals[s]) slices += n.type == 1 || n.type == 5;
+        too_many |= slices > (size_t)d->P;
+    }
+    d->t_split += dec_now() - ts;
+    if (too_many) {  // refused as a whole: nothing was taken
+        d->ts_expect = before;
         for (int s = 0; s < S; s++) {
             d->nals[s].clear();
             d->overrun[s] = 0;

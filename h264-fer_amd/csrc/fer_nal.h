@@ -1,7 +1,7 @@
-// fer_nal.h -- what the two framings of the coded pictures share (fer_nalpack.hip: Annex-B and length-prefixed units;
-// fer_rtp.hip: RTP packets): the framing job, writeNAL's counter as a function that composes (NalCompose), the function of
+// fer_nal.h -- what the framings of the coded pictures share (fer_nalpack.hip: Annex-B and length-prefixed units;
+// fer_rtp.hip: RTP packets; fer_ts.hip: transport stream packets): the framing job, writeNAL's counter as a function that composes (NalCompose), the function of
 // 16 payload bytes (nal_piece) and their load (nal_load).  The kernels that scan it (k_nal_count, k_nal_plan) live in
-// fer_nalpack.hip; fer_launch_nal_count launches them for either framing.
+// fer_nalpack.hip; fer_launch_nal_count launches them for every framing.
 #pragma once
 #include "fer_ctx.h"
 #include "fer_scan.h"

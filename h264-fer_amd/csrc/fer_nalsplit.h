@@ -93,6 +93,28 @@ int fer_unrtp_run(FerUnrtp &u, hipStream_t st, const uint8_t *d_base, const ferh
 // a stable sort of the caller's table by stream, and every stream's first row; FERHIP_E_ARG for a stream outside [0, S)
 int fer_rtp_sort(const ferhip_rtp_pkt *pkts, size_t npk, int S, std::vector<ferhip_rtp_pkt> &sorted, std::vector<uint32_t> &first);
 
+// Transport stream packets in device memory (fer_ts.hip): the buffers of the demultiplexer in front of the splitter, as
+// FerUnrtp's; one job at a time.
+struct FerUnts {
+    DevBuf<ferhip_ts_run> d_runs;    // [nruns] the table, sorted by stream ...
+    PinBuf<ferhip_ts_run> h_runs;    // ... as the host writes it
+    DevBuf<uint4> d_rec;             // [npk] what k_unts_parse reads of every 188-byte packet
+    DevBuf<uint4> d_piece;           // [npk] what k_unts_gather copies for every packet: source, bytes | stream << 8, place
+    DevBuf<uint32_t> d_job;          // first packet of every stream (S + 1), PID [S], expectation in [S], first packet of every
+    PinBuf<uint32_t> h_job;          // run (nruns + 1), staging bases (64-bit) [S]
+    DevBuf<int32_t> d_res;           // [3][S]: staged bytes, fault, expectation out
+    PinBuf<int32_t> h_res;
+    DevBuf<uint8_t> d_stage;         // every stream's elementary-stream bytes: the Annex-B ranges fer_split_run takes
+    std::vector<const uint8_t *> ptrs;  // [S] the last job's staging ranges
+    std::vector<size_t> lens;
+};
+// runs[nruns] (host) sorted by stream, first[S + 1] = every stream's first row; the runs' packets lie at d_base + offset and
+// stream s listens to pids[s].  Parses, walks (expect[S]: in the continuity counter expected or -1, out the next one or -1
+// after a fault; fault[S]: 0, 2, 3) and gathers the elementary-stream bytes that stand into u.ptrs / u.lens, on stream st.
+// One host synchronisation.
+int fer_unts_run(FerUnts &u, hipStream_t st, const uint8_t *d_base, const ferhip_ts_run *runs, size_t nruns, const uint32_t *first, int S,
+                 const uint16_t *pids, int32_t *expect, int32_t *fault);
+
 // The empty-payload cut of split_stream (fer_dec_syntax_host.h), which the device leaves to the host: a unit with bytes == 0
 // ends its range, and the later units of that range are skipped.  f(k, unit) for every entry k of the last job's table that
 // stays, in table order, until one returns non-zero; returns that value, or 0.

@@ -61,12 +61,27 @@ RTP_HDR = np.dtype([("ssrc", np.uint32), ("timestamp", np.uint32), ("seq", np.ui
 RTP_PKT = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("stream", np.uint32)])
 RTP_AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.int32), ("first_pkt", np.uint32), ("npkts", np.uint32)])
 assert (RTP_HDR.itemsize, RTP_PKT.itemsize, RTP_AU.itemsize) == (12, 16, 24)
+# ferhip_ts_hdr, ferhip_ts_au: the caller's transport stream fields per stream and one entry of the index of ferhip_pack_ts /
+# ferhip_fetch_ts / ferhip_ts_blocks; a row of ferhip_decs_decode_ts's table of runs has dtype RTP_PKT
+TS_HDR = np.dtype([("pts", np.uint64), ("pcr", np.uint64), ("pid", np.uint16), ("pmt_pid", np.uint16), ("cc", np.uint8), ("psi_cc", np.uint8),
+                   ("reserved", np.uint16)])
+TS_AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.int32), ("npkts", np.uint32), ("reserved", np.uint32)])
+TS_RUN = RTP_PKT
+TS_PSI = 8  # FERHIP_TS_PSI
+assert (TS_HDR.itemsize, TS_AU.itemsize) == (24, 24)
 
 
 def rtp_hdr(n, ssrc=0, timestamp=0, seq=0, payload_type=96):
     """n entries of dtype RTP_HDR; every argument a scalar or a sequence of n"""
     h = np.zeros(n, RTP_HDR)
     h["ssrc"], h["timestamp"], h["seq"], h["payload_type"] = ssrc, timestamp, seq, payload_type
+    return h
+
+
+def ts_hdr(n, pts=0, pcr=0, pid=0x100, pmt_pid=0x1000, cc=0, psi_cc=0):
+    """n entries of dtype TS_HDR; every argument a scalar or a sequence of n"""
+    h = np.zeros(n, TS_HDR)
+    h["pts"], h["pcr"], h["pid"], h["pmt_pid"], h["cc"], h["psi_cc"] = pts, pcr, pid, pmt_pid, cc, psi_cc
     return h
 
 
@@ -181,6 +196,13 @@ def load_library():
     lib.ferhip_decs_set_layout.argtypes = [vp, i, C.c_uint32, C.c_uint32]
     lib.ferhip_decs_set_csc.argtypes = [vp, i]
     lib.ferhip_decs_decode_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_pack_ts.argtypes = [vp, i, vp, vp, sz, vp]
+    lib.ferhip_fetch_ts.argtypes = [vp, i, vp, vp, sz, vp]
+    lib.ferhip_ts_blocks.argtypes = [vp, sz, vp, vp, sz, vp, vp, sz, vp]
+    lib.ferhip_write_ts_psi.argtypes = [i, i, i, vp, sz]
+    lib.ferhip_write_ts_psi.restype = sz
+    lib.ferhip_decs_decode_ts.argtypes = [vp, vp, i, vp, sz, vp, vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_unts_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, vp, vp, sz, vp, sz, C.POINTER(sz), vp, vp]
     lib.ferhip_decs_decode_rtp.argtypes = [vp, vp, i, vp, sz, vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_unrtp_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz, C.POINTER(sz), vp, vp]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
@@ -580,6 +602,37 @@ class FerHip:
             raise FerHipError(f"ferhip_write_sdp_fmtp({stream}) failed")
         return o.raw[:n].decode()
 
+    # --- transport stream packets on the device
+    def pack_ts_device(self, hdr, dst_ptr, cap, index_ptr, flags=0):
+        """ferhip_pack_ts: the last picture's 188-byte transport stream packets -> device memory at dst_ptr (16-byte aligned,
+        cap bytes) and the index (S + 1 records of dtype TS_AU) at index_ptr, on the library's stream (asynchronous; sync()
+        before reading).  hdr: S entries of dtype TS_HDR (ts_hdr); the caller advances cc and psi_cc."""
+        h = np.ascontiguousarray(hdr, TS_HDR)
+        assert h.size == self.S
+        _chk(self.lib.ferhip_pack_ts(self.ctx, int(flags), h.ctypes.data, C.c_void_p(int(dst_ptr) if dst_ptr else None), int(cap),
+                                     C.c_void_p(int(index_ptr))), "ferhip_pack_ts")
+
+    def fetch_ts_raw(self, hdr, cap, flags=0, fill=0):
+        """ferhip_fetch_ts into a new host buffer -> (return code, buffer [cap], index [S + 1] of dtype TS_AU)"""
+        h = np.ascontiguousarray(hdr, TS_HDR)
+        assert h.size == self.S
+        buf = np.full(max(int(cap), 1), fill, np.uint8)
+        idx = np.zeros(self.S + 1, TS_AU)
+        rc = self.lib.ferhip_fetch_ts(self.ctx, int(flags), h.ctypes.data, buf.ctypes.data, int(cap), idx.ctypes.data)
+        return rc, buf, idx
+
+    def fetch_ts(self, hdr, flags=0):
+        """The last picture of every stream as transport stream packets (waits) -> (list per stream of its packets as one
+        bytes, b"" for the streams without a picture; the index of dtype TS_AU).  With TS_PSI a PAT and a PMT packet stand
+        in front of an I picture's packets."""
+        cap = getattr(self, "_ts_cap", 1 << 20)
+        rc, buf, idx = self.fetch_ts_raw(hdr, cap, flags)
+        if rc == -1 and int(idx["offset"][self.S]) > cap:  # a true index: the buffer was too small
+            cap = self._ts_cap = 2 * int(idx["offset"][self.S])
+            rc, buf, idx = self.fetch_ts_raw(hdr, cap, flags)
+        _chk(rc, "ferhip_fetch_ts")
+        return [bytes(buf[int(idx["offset"][s]): int(idx["offset"][s]) + int(idx["bytes"][s])]) for s in range(self.S)], idx
+
     # --- rate control
     def set_rate(self, stream=-1, mode=RC_CQP, qp=None, qp_min=0, qp_max=51, max_step=2, ip_offset=3, window=0,
                  target_bits=0, target_sse=0, target_psnr=None):
@@ -948,6 +1001,60 @@ def rtp_blocks_raw(payloads, nal_types, max_packet, hdr, cap=None, pkts_cap=None
     return rc, out, pkts, idx
 
 
+def ts_blocks_raw(payloads, nal_types, hdr, cap=None, fill=0xA5):
+    """ferhip_ts_blocks on a list of payloads (bytes or uint8 arrays), one slice unit each -> (return code, out [cap]
+    pre-filled with `fill`, index [n + 1] of dtype TS_AU).  cap None = room for every payload with every second byte escaped."""
+    lib = load_library()
+    n = len(payloads)
+    lens = np.array([len(p) for p in payloads], np.uint32)
+    stride = max(int(lens.max()) if n else 0, 1)
+    src = np.zeros((n, stride), np.uint8)
+    for k, p in enumerate(payloads):
+        src[k, : len(p)] = np.frombuffer(bytes(p), np.uint8) if not isinstance(p, np.ndarray) else p
+    if cap is None:
+        cap = sum((((int(m) * 3 // 2 + 26) // 184 + 2) * 188 + 15) & ~15 for m in lens)
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    idx = np.zeros(n + 1, TS_AU)
+    h = np.ascontiguousarray(hdr, TS_HDR)
+    nt = np.ascontiguousarray(nal_types, np.int32)
+    rc = lib.ferhip_ts_blocks(src.ctypes.data, stride, lens.ctypes.data, nt.ctypes.data, n, h.ctypes.data, out.ctypes.data, int(cap),
+                              idx.ctypes.data)
+    return rc, out, idx
+
+
+def write_ts_psi(pid, pmt_pid, psi_cc, cap=376):
+    """ferhip_write_ts_psi -> the PAT and the PMT packet as bytes, b"" where the library refuses"""
+    o = np.zeros(max(int(cap), 1), np.uint8)
+    n = load_library().ferhip_write_ts_psi(int(pid), int(pmt_pid), int(psi_cc), o.ctypes.data, int(cap))
+    return bytes(o[:n])
+
+
+def unts_blocks_raw(base, runs, pids, cc_expect=None, misalign=0, cap=None, units_cap=None, fill=0xA5):
+    """ferhip_unts_blocks: transport stream packets in `base` (bytes or a uint8 array) by the table `runs` (rows of dtype
+    TS_RUN) through the device demultiplexer and splitter, stream s listening to pids[s] -> (return code, out [cap]
+    pre-filled with `fill`, units [units_cap] of dtype NAL_UNIT with range = the stream, the true unit count, fault
+    [nstreams], cc_next [nstreams]).  cc_expect None = no expectation; cap / units_cap None = room for everything."""
+    lib = load_library()
+    b = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+    rows = np.ascontiguousarray(runs, TS_RUN)
+    pid = np.ascontiguousarray(pids, np.uint16)
+    nstreams = pid.size
+    exp = np.full(nstreams, -1, np.int32) if cc_expect is None else np.ascontiguousarray(cc_expect, np.int32)
+    room = int(rows["bytes"].sum()) if rows.size else 0
+    if cap is None:
+        cap = room + 16 * (room // 4 + 1)
+    if units_cap is None:
+        units_cap = room // 4 + 1
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    units = np.zeros(max(int(units_cap), 1), NAL_UNIT)
+    fault, nxt = np.zeros(max(nstreams, 1), np.int32), np.zeros(max(nstreams, 1), np.int32)
+    count = C.c_size_t(0)
+    rc = lib.ferhip_unts_blocks(b.ctypes.data if b.size else None, b.size, rows.ctypes.data if rows.size else None, rows.size, int(nstreams),
+                                int(misalign), pid.ctypes.data if pid.size else None, exp.ctypes.data if exp.size else None, out.ctypes.data,
+                                int(cap), units.ctypes.data, int(units_cap), C.byref(count), fault.ctypes.data, nxt.ctypes.data)
+    return rc, out, units, count.value, fault[:nstreams], nxt[:nstreams]
+
+
 def unrtp_blocks_raw(base, pkts, nstreams, seq_expect=None, misalign=0, cap=None, units_cap=None, fill=0xA5):
     """ferhip_unrtp_blocks: RTP packets in `base` (bytes or a uint8 array) by the table `pkts` (rows of dtype RTP_PKT) through
     the device depacketiser and splitter -> (return code, out [cap] pre-filled with `fill`, units [units_cap] of dtype
@@ -1214,6 +1321,29 @@ class LiveDecoder:
         pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
         _chk(self.lib.ferhip_decs_decode_rtp(self.h, C.c_void_p(ptr_in), int(bool(base_on_device)), rows.ctypes.data if rows.size else None,
                                              rows.size, C.c_void_p(out.ctypes.data), 0, pics, status), "ferhip_decs_decode_rtp")
+        return out, list(pics), list(status)
+
+    def decode_ts(self, base, runs, pids, out=None, base_on_device=False):
+        """ferhip_decs_decode_ts: 188-byte transport stream packets -> (out, pictures, status) like decode().
+        base: the bytes that hold the packets (bytes or a uint8 array; an integer device address with base_on_device);
+        runs: rows of dtype TS_RUN (offset from base, bytes: a multiple of 188, stream) in arrival order; pids: the PID every
+        stream listens to.  out: a host uint8 array or None."""
+        if base_on_device:
+            ptr_in = int(base)
+        else:
+            keep = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+            ptr_in = keep.ctypes.data if keep.size else None
+        rows = np.ascontiguousarray(runs, TS_RUN)
+        pid = np.ascontiguousarray(pids, np.uint16)
+        if pid.size != self.S:
+            raise FerHipError(f"LiveDecoder.decode_ts: {pid.size} PIDs for {self.S} streams")
+        if out is None:
+            out = np.zeros((self.P, self.S, self.fsz), np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < self.P * self.S * self.fsz:
+            raise FerHipError("LiveDecoder.decode_ts: out must be a C-contiguous uint8 array of [max_pictures][S][W*H*3/2]")
+        pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
+        _chk(self.lib.ferhip_decs_decode_ts(self.h, C.c_void_p(ptr_in), int(bool(base_on_device)), rows.ctypes.data if rows.size else None,
+                                            rows.size, pid.ctypes.data, C.c_void_p(out.ctypes.data), 0, pics, status), "ferhip_decs_decode_ts")
         return out, list(pics), list(status)
 
     def decode_dev(self, ptrs, lens, out=None):

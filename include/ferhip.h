@@ -356,6 +356,63 @@ int ferhip_rtp_blocks(const uint8_t *payloads, size_t stride, const uint32_t *le
                       size_t pkts_cap, ferhip_rtp_au *index /* [n+1] */);
 size_t ferhip_write_sdp_fmtp(ferhip_ctx *c, int s, char *out, size_t cap);
 
+/* ---- Transport stream packets on the device: the coded pictures in the MPEG-2 transport stream of ISO/IEC 13818-1 ----
+ * The fourth framing of the same pictures: what UDP multicast, SRT, HLS segments and DVB / ATSC carry.  A stream that coded
+ * a picture in the context's last ferhip_encode_picture[_dev] call has one access unit, one PES packet, in 188-byte packets.
+ * Elementary-stream bytes E: an access unit delimiter 00 00 00 01 09 a (a = 0x10 for an I picture, slice NAL unit type 5,
+ * and 0x30 for a P picture), then the stream's entry exactly as ferhip_pack_nal writes it with flags & FERHIP_AU_PARAM_SETS.
+ * PES packet = 14 header bytes + E, L = 14 + |E| bytes: 00 00 01 E0, 00 00 (PES_packet_length 0, as video in a transport
+ * stream may), 84 (data_alignment_indicator), 80 (PTS only), 05, then the PTS: 0x21 | ((pts >> 29) & 0x0E), (pts >> 22) & 0xFF,
+ * 0x01 | ((pts >> 14) & 0xFE), (pts >> 7) & 0xFF, 0x01 | ((pts << 1) & 0xFE).  No DTS: the encoder never reorders.
+ * Packets: 47, PUSI << 6 | pid >> 8, pid & 0xFF, afc << 4 | cc.  n = 1 if L <= 176, else 1 + ceil((L - 176) / 184); cc of
+ * packet k is (hdr.cc + k) & 15, counting the PES-carrying packets only.
+ *   packet 0       PUSI = 1, afc = 3; adaptation field: length byte a0 = 7 if L >= 176, else 183 - L; the flags byte
+ *                  0x10 | (I picture ? 0x40 : 0) -- PCR_flag and random_access_indicator --; the PCR (pcr >> 25) & 0xFF,
+ *                  (pcr >> 17) & 0xFF, (pcr >> 9) & 0xFF, (pcr >> 1) & 0xFF, ((pcr & 1) << 7) | 0x7E, 00 (extension 0); a0 - 7
+ *                  bytes FF; then PES bytes [0, min(L, 176)).
+ *   packet k >= 1  PUSI = 0, c = min(184, L - 176 - 184 (k - 1)) PES bytes.  c = 184: afc = 1, no adaptation field.
+ *                  c < 184: afc = 3, length byte 183 - c and, if that is >= 1, a flags byte 00 and 182 - c bytes FF.  The
+ *                  payload ends the packet.
+ * PSI.  With FERHIP_TS_PSI, and only in front of an I picture's packets, come a PAT and a PMT packet, so that the stream's
+ * packets from there on are a single-program transport stream a player can open:
+ *   PAT  47 40 00 10|psi_cc 00, the section 00 B0 0D 00 01 C1 00 00 00 01 E0|pmt_pid>>8 pmt_pid&FF + CRC, FF to 188;
+ *   PMT  47 40|pmt_pid>>8 pmt_pid&FF 10|psi_cc 00, the section 02 B0 12 00 01 C1 00 00 E0|pid>>8 pid&FF F0 00 1B
+ *        E0|pid>>8 pid&FF F0 00 + CRC, FF to 188.
+ * The CRC is CRC-32/MPEG-2 (polynomial 0x04C11DB7, initial value 0xFFFFFFFF, no reflection, no final xor, big-endian) over
+ * the section from its table_id: 2A B1 04 B2 for pmt_pid = 0x1000, 15 BD 4D 56 for pid = 0x100.  The sections are built on
+ * the host and kept in a small device table; a stream's row is sent again only when its (pid, pmt_pid) differ from what the
+ * table holds, and the kernel patches in psi_cc.  ferhip_write_ts_psi (host) writes the two packets, 376 bytes; 0 if cap is
+ * short or a PID or psi_cc is refused.
+ * The library keeps no TS state: the caller advances cc by the access unit's PES-carrying packets (npkts, less 2 where PSI
+ * was written) and psi_cc by 1 per access unit that carried PSI; a repeated call with the same hdr gives the same bytes.
+ * Layout: stream order; a stream's packets are contiguous, 188 bytes apart, PSI first; every stream begins at a multiple of
+ * 16, and the bytes between a stream's end and the next multiple of 16 are not written.  index[s] = (offset, 188 * npkts,
+ * NAL unit type of the slice, npkts, 0); a stream without a picture has zeros.  index[S] = (total rounded up to 16,
+ * streams written, 0, total packets, 0).
+ * Overflow is ferhip_pack_rtp's rule, per stream: the index always holds the true values, a stream is written whole or not
+ * at all, only if offset + bytes <= cap, and nothing at or beyond cap is touched.  ferhip_pack_ts then still returns 0,
+ * ferhip_fetch_ts fills h_index and returns FERHIP_E_ARG.
+ * FERHIP_E_ARG (hdr is read for every stream, those without a picture included): a flag other than FERHIP_AU_PARAM_SETS |
+ * FERHIP_TS_PSI, a null c, hdr or index, a null buffer with a cap, pts or pcr >= 2^33, pid or pmt_pid outside
+ * 0x0010..0x1FFE, pid == pmt_pid, cc or psi_cc > 15, reserved != 0, and for ferhip_pack_ts a d_dst not aligned to 16 or a
+ * d_index not aligned to 8.  FERHIP_E_STATE before the context's first picture.
+ * ferhip_pack_ts: device to device, asynchronous on the context's stream; it waits for nothing except a first call's
+ * allocations.  ferhip_fetch_ts: the same bytes in host memory; it waits once for the index and once for the copy.  Packing
+ * changes nothing the encoder reads, may be repeated and may be mixed with the other framings.
+ * ferhip_ts_blocks: known-answer surface with the conventions of ferhip_rtp_blocks: host payloads, one slice unit each (no
+ * parameter sets, no PSI), hdr[n], n <= 65535, and bytes the kernels do not write keep the caller's values.  A payload of
+ * length 0 gives L = 25.
+ * Not provided: multi-program output (the PIDs are the caller's, so the caller may interleave several streams' packets);
+ * null-packet padding to a constant rate and PCR pacing; a non-zero PES_packet_length; DTS. */
+#define FERHIP_TS_PSI 8
+typedef struct { uint64_t pts, pcr; uint16_t pid, pmt_pid; uint8_t cc, psi_cc; uint16_t reserved; } ferhip_ts_hdr; /* 24 bytes, host */
+typedef struct { uint64_t offset; uint32_t bytes; int32_t nal_type; uint32_t npkts, reserved; } ferhip_ts_au;      /* 24 bytes */
+int ferhip_pack_ts(ferhip_ctx *c, int flags, const ferhip_ts_hdr *hdr /* host [S] */, void *d_dst, size_t cap, ferhip_ts_au *d_index /* [S+1] */);
+int ferhip_fetch_ts(ferhip_ctx *c, int flags, const ferhip_ts_hdr *hdr, void *h_dst, size_t cap, ferhip_ts_au *h_index);
+int ferhip_ts_blocks(const uint8_t *payloads, size_t stride, const uint32_t *lens, const int32_t *nal_type, size_t n,
+                     const ferhip_ts_hdr *hdr /* [n] */, uint8_t *out, size_t cap, ferhip_ts_au *index /* [n+1] */);
+size_t ferhip_write_ts_psi(int pid, int pmt_pid, int psi_cc, uint8_t *out, size_t cap);
+
 /* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134), each stream with its own PPS:
  * frames host [T][S][W*H*3/2]; out host [S][out_stride] Annex-B; out_len[S].
  * recon (optional) host [T][S][W*H*3/2]. */
@@ -767,6 +824,50 @@ int ferhip_decs_decode_rtp(ferhip_decs *d, const void *base, int base_on_device,
 int ferhip_unrtp_blocks(const uint8_t *base, size_t base_bytes, const ferhip_rtp_pkt *pkts, size_t npkts, int nstreams, int misalign,
                         const int32_t *seq_expect /* [nstreams], -1 = none */, uint8_t *out, size_t cap, ferhip_nal_unit *units,
                         size_t units_cap, size_t *nunits, int32_t *fault /* [nstreams] */, int32_t *seq_next /* [nstreams] */);
+
+/* ---- Transport stream input: the live decoder takes 188-byte packets where a receiver has them ----
+ * runs[k] (host) names runs[k].bytes bytes at base + runs[k].offset: a whole number of 188-byte packets at any alignment,
+ * for stream runs[k].stream.  Runs of one stream are taken in table order, streams may interleave, and two runs may name the
+ * same bytes for different streams: a multi-program transport stream read by several slots.  pids[s] is the PID stream s
+ * listens to.  Per stream the state is the expected continuity counter (none at first); it survives calls, and
+ * ferhip_decs_reset_stream clears it.  For every packet of the stream's runs:
+ *   1. b0 != 0x47 or transport_error_indicator (b1 & 0x80): malformed.
+ *   2. PID != pids[s]: the packet is skipped, and nothing else of it is looked at.
+ *   3. scrambling control (b3 >> 6) != 0: malformed.
+ *   4. afc = (b3 >> 4) & 3.  0: malformed.  2: no payload, skipped, the counter not looked at.  1: payload [4, 188).
+ *      3: a = b4, a > 183 is malformed, payload [5 + a, 188), which may be empty.  The field's content is not looked at.
+ *   5. counter: with an expectation that b3 & 15 differs from, a gap (a duplicate is one, too).  Then the expectation is
+ *      (b3 & 15) + 1 mod 16.
+ *   6. with PUSI a PES packet begins: the payload p begins 00 00 01, its stream_id p[3] is E0..EF, (p[6] & 0xC0) == 0x80 and
+ *      it holds at least 9 + p[8] bytes, else malformed.  Its elementary-stream bytes begin at 9 + p[8]; PES_packet_length,
+ *      PTS and DTS are not looked at.
+ *   7. without PUSI the whole payload continues the open PES packet; with none open in this call the packet is malformed: a
+ *      call takes whole access units.
+ * A PES packet is complete at the stream's next PUSI packet that passes these rules, or when the stream's packets of the call
+ * end.  The first fault (2 malformed, 3 gap) ends the stream's walk: the PES packets completed in front of it stand, the
+ * open one is dropped, and the expectation is cleared.  The elementary-stream bytes that stand, concatenated, are one
+ * Annex-B range, and from there on the definition is the Annex-B splitter's and the decoder's: four-byte start codes begin
+ * units, a three-byte one ends a unit and begins none, and the delimiter is a unit of type 9 that is ignored like every other
+ * type the decoder does not know.
+ * ferhip_decs_decode_ts: pictures, pictures[], status[] and the isolation rules are those of ferhip_decs_decode given the
+ * same NAL units.  Every fault gives status[s] = FERHIP_E_ARG: the units in front of it decode, the stream restarts at its
+ * next IDR slice, the other streams are untouched.  FERHIP_E_ARG for the call, before anything is taken: runs[k].stream >= S,
+ * a bytes that is no multiple of 188, a pids[s] > 0x1FFF, a stream with more than max_pictures slices, null pointers.  It may
+ * be mixed freely with the other decode calls.
+ * base_on_device = 0: the walk runs on the host.  base_on_device = 1: base is device memory on the decoder's device and
+ * nothing but the table crosses the bus: the runs are sorted by stream on the host, one lane per 188-byte packet applies
+ * rules 1 to 4 and 6, one wavefront per stream walks the counter and the open PES packet with ballots and wave scans, the
+ * spans that stand are gathered into one staging range per stream, and the Annex-B splitter does the rest.  Two host
+ * synchronisations, more only when a buffer had to grow.  The kernels read nothing outside the runs' packets.
+ * ferhip_unts_blocks: known-answer surface of that path with the conventions of ferhip_unrtp_blocks; cc_expect[s] in
+ * -1..15, fault[s] and cc_next[s] (-1 after a fault) come back.
+ * Not provided: PSI parsing (the caller names the PID), and splitting at three-byte start codes. */
+typedef ferhip_rtp_pkt ferhip_ts_run; /* (offset, bytes: a multiple of 188, stream) */
+int ferhip_decs_decode_ts(ferhip_decs *d, const void *base, int base_on_device, const ferhip_ts_run *runs /* host */, size_t nruns,
+                          const uint16_t *pids /* host [S] */, uint8_t *out, int out_on_device, int *pictures, int *status);
+int ferhip_unts_blocks(const uint8_t *base, size_t base_bytes, const ferhip_ts_run *runs, size_t nruns, int nstreams, int misalign,
+                       const uint16_t *pids, const int32_t *cc_expect /* [nstreams], -1 = none */, uint8_t *out, size_t cap,
+                       ferhip_nal_unit *units, size_t units_cap, size_t *nunits, int32_t *fault, int32_t *cc_next /* -1 after a fault */);
 
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
