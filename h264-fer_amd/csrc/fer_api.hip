@@ -186,7 +186,9 @@ int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p, bo
     rc |= dalloc(c, &d.spec_hdr, decode_only ? (size_t)1 : (size_t)(nm * 4));
     rc |= dalloc(c, &d.spec_l1, decode_only ? (size_t)1 : (size_t)(nm * 4 * 17));
     rc |= dalloc(c, &d.spec_l2, decode_only ? (size_t)1 : (size_t)(nm * 4 * 33));
-    rc |= dalloc(c, &d.spec_stat, (size_t)8);
+    // one slot per workgroup of the chain: its grid is min(rows of all streams, FERHIP_TUNE_RESOLVE_WGS <= 65535)
+    d.spec_slots = decode_only ? 1 : (int)std::min<size_t>(65535, (size_t)2 * d.mbh * S);
+    rc |= dalloc(c, &d.spec_stat, (size_t)4 * d.spec_slots);
     d.speculate = 1;
     rc |= dalloc(c, &d.chain, (size_t)64);
     rc |= dalloc(c, &d.timing, (size_t)64);
@@ -201,6 +203,7 @@ int ctx_create(ferhip_ctx **out, int W, int H, int S, const ferhip_params *p, bo
     rc |= dalloc(c, &d.out_bytes, (size_t)S);
     rc |= dalloc(c, &d.status, (size_t)S);
     rc |= dalloc(c, &d.sad, (size_t)S);
+    rc |= dalloc(c, &d.sad_part, (size_t)FER_SAD_G * S);
     rc |= dalloc(c, &d.stats, (size_t)5 * S);
     rc |= dalloc(c, &d.dec_qp, nm);
     rc |= dalloc(c, &d.dec_state, (size_t)4 * S);
@@ -820,6 +823,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
             ProfScope ps(c, FERHIP_PH_P_RESID, 1);
             fer_launch_basic_stat(d, c->st);  // BasicInterEncoding only: brojTipova of the discarded exhaustive pass
             fer_launch_p_resid(d, c->st);
+            fer_launch_type_count(d, c->st);  // brojTipova of the P streams, from the types the two launches above left
         }
     }
     if (anyI) {
@@ -1189,6 +1193,7 @@ extern "C" int ferhip_inter_encoding(ferhip_ctx *c)
     }
     fer_launch_basic_stat(c->d, c->st);
     fer_launch_p_resid(c->d, c->st);  // partition merge + mvd share the residual wavefront of the macroblock
+    fer_launch_type_count(c->d, c->st);
     CK(hipStreamSynchronize(c->st));
     CK(hipGetLastError());
     return 0;
@@ -1254,7 +1259,17 @@ extern "C" size_t ferhip_read_buffer(ferhip_ctx *c, int which, void *dst, size_t
     case FERHIP_BUF_SPEC_L1: src = d.spec_l1; n = nm * 4 * 17 * 8; break;
     case FERHIP_BUF_SPEC_L2: src = d.spec_l2; n = nm * 4 * 33 * 8; break;
     case FERHIP_BUF_ST2: src = d.st2; n = nm * 4 * FER_ST2_CAP * 8; break;
-    case FERHIP_BUF_SPEC_STAT: src = d.spec_stat; n = 8 * 8; break;
+    case FERHIP_BUF_SPEC_STAT: {  // the four totals over the workgroups' slots, then four zero words
+        n = 8 * 8;
+        if (n > cap) return 0;
+        if (hipStreamSynchronize(c->st) != hipSuccess) return 0;
+        std::vector<unsigned long long> slots((size_t)4 * d.spec_slots);
+        if (hipMemcpy(slots.data(), d.spec_stat, slots.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+        unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (size_t i = 0; i < slots.size(); i++) tot[i & 3] += slots[i];
+        memcpy(dst, tot, n);
+        return n;
+    }
     case FERHIP_BUF_MBSIZE: src = d.mbsize; n = nm * 8; break;
     case FERHIP_BUF_CUR:
     case FERHIP_BUF_REF: {

@@ -143,7 +143,11 @@ struct FerDev {
                          // lists valid << 16 | P_Skip verdict valid << 17, z = guessed P_Skip vector (partition 0), w = its verdict
     int2 *spec_l1;       // [S][nmb][4][17] stage-1 list: (packed vector, SAD)
     int2 *spec_l2;       // [S][nmb][4][33] stage-2 list
-    unsigned long long *spec_stat;  // [8] partitions the chain decided, hits, P_Skip verdicts needed, taken from the guess
+    // [spec_slots][4] partitions the chain decided, hits, P_Skip verdicts needed, taken from the guess: one slot per workgroup
+    // of k_me_resolve (its owner for the launch adds with plain loads and stores), summed on read-back.  A slot is never
+    // cleared, so the totals do not depend on how many workgroups a picture was run with.
+    unsigned long long *spec_stat;
+    int spec_slots;      // >= any grid fer_launch_me_resolve uses
     int speculate;       // 0 = the chain searches everything itself (ferhip_tune; results do not depend on it)
     int *chain;          // row ticket of k_me_resolve
     unsigned long long *chain64;  // [S][nmb][4] vector | picture serial << 32 | P_Skip << 63, see k_me_resolve
@@ -159,7 +163,8 @@ struct FerDev {
     uint32_t *out_bytes; // [S] RBSP length
     int *status;         // [S] sticky error flags
     unsigned long long *sad; // [S] frame SAD for the IDR decision
-    int *stats;          // [S][5] brojTipova
+    unsigned long long *sad_part;  // [S][FER_SAD_G] per-workgroup partial sums of k_frame_sad, added by k_frame_sad_sum
+    int *stats;          // [S][5] brojTipova: P_Skip, 16x16, 16x8, 8x16, 8x8 (k_type_count, k_basic_stat)
     // decoder (row a19)
     uint8_t *dec_qp;     // [S][nmb] QPy of every macroblock
     int *dec_state;      // [S][4]: [0] mb_qp_delta carried from picture to picture; the reconstruction kernels are given the
@@ -190,6 +195,8 @@ struct DecBatch {
 // hdr[s][3] of a stream that has no picture in this call (FERHIP_NAL_NONE): every kernel that tests for 0 (P) or 2 (I)
 // skips it as written; k_rc_plan, k_cavlc, k_bits_scan, k_bits_zero and k_quality test for it
 #define FER_PIC_ABSENT 3
+
+#define FER_SAD_G 64  // most workgroups of k_frame_sad per stream = row length of FerDev::sad_part
 
 // bits 0 and 1 (stage-2 list overflow, zero-sum blocks) are no longer raised: both cases are handled exactly
 #define FER_ERR_BITS_OVERFLOW 4

@@ -29,6 +29,7 @@ void fer_launch_me_spec(const FerDev &d, hipStream_t st);
 void fer_launch_me_resolve(const FerDev &d, hipStream_t st);
 void fer_launch_basic_stat(const FerDev &d, hipStream_t st);
 void fer_launch_p_resid(const FerDev &d, hipStream_t st);
+void fer_launch_type_count(const FerDev &d, hipStream_t st);
 void fer_launch_intra(const FerDev &d, hipStream_t st);
 void fer_launch_intra_diag(const FerDev &d, int diag, hipStream_t st);  // one anti-diagonal of k_intra_mb
 void fer_launch_cavlc(const FerDev &d, hipStream_t st);

@@ -2246,11 +2246,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
                 }
             }
             const unsigned long long w = (unsigned)r | ((unsigned long long)(serial | (sk ? CH_SKIP : 0u)) << 32);
-            if (part == 0 && ln == 0) {
-                mbt[mb] = sk ? FER_P_SKIP : FER_P_8x8ref0;  // also clears a P_Skip left by the previous picture
-                // BasicInterEncoding makes the P_Skip test twice and counts it twice (F/moestimation.cpp:324,421)
-                if (sk) atomicAdd(&d.stats[s * 5 + 0], d.basic ? 2 : 1);
-            }
+            // also clears a P_Skip left by the previous picture; brojTipova counts the P_Skips from here (k_type_count)
+            if (part == 0 && ln == 0) mbt[mb] = sk ? FER_P_SKIP : FER_P_8x8ref0;
             const int nw = sk ? 4 : 1, q0 = sk ? 0 : part;
             if (ln < nw) {
                 __hip_atomic_store(chw + (size_t)mb * 4 + q0 + ln, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2268,11 +2265,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
 #undef PR_MARK
     if (timeout && lane == 0) atomicOr(&d.status[s], FER_ERR_CHAIN_TIMEOUT);
     }
+    // this workgroup's own slot: launches are serial on the stream and no other workgroup of this one touches it
     if (lane == 0 && st_parts + st_skq > 0) {
-        atomicAdd(&d.spec_stat[0], (unsigned long long)st_parts);
-        atomicAdd(&d.spec_stat[1], (unsigned long long)st_hits);
-        atomicAdd(&d.spec_stat[2], (unsigned long long)st_skq);
-        atomicAdd(&d.spec_stat[3], (unsigned long long)st_skh);
+        unsigned long long *o = d.spec_stat + (size_t)blockIdx.x * 4;
+        o[0] += st_parts;
+        o[1] += st_hits;
+        o[2] += st_skq;
+        o[3] += st_skh;
     }
 }
 
@@ -2366,7 +2365,7 @@ void fer_launch_me_resolve(const FerDev &d, hipStream_t st)
     const int gh = 2 * d.mbh;
     hipMemsetAsync(d.chain, 0, sizeof(int) * 8, st);
     const int cap = d.resolve_wgs;
-    dim3 g(min(gh * d.S, max(cap, 1)));
+    dim3 g(min(min(gh * d.S, max(cap, 1)), d.spec_slots));  // (spec_slots is no bound in practice: one slot of spec_stat per workgroup)
     if (d.window == 32)
         hipLaunchKernelGGL(k_me_resolve<32>, g, dim3(64), 0, st, d);
     else if (d.window == 16)

@@ -993,11 +993,16 @@ void fer_launch_refprep(const FerDev &d, FerSortTmp &t, const int *types, hipStr
 
 // ------------------------------------------------------------------ k_frame_sad
 // selectNALUnitType's whole-picture SAD (F/ref_frames.cpp:185-234): a pure stream of 2 bytes per luma sample, read as
-// 16-byte words, four of them in flight per lane
+// 16-byte words, four of them in flight per lane.  Every workgroup leaves one partial sum in sad_part[s][g] with a plain
+// store; k_frame_sad_sum, the next launch on the stream, adds a stream's partials and writes sad[s].  No atomics, no
+// cleared destination, no fences: the launch boundary hands the partials over.  (A ticket scheme in one launch, as in
+// k_quality, was measured first: its release fence writes this XCD's L2 back once per workgroup, and with 64 workgroups
+// per stream the launch took 0.94 ms against 0.24 ms with the atomics it was meant to replace.)
 __global__ __launch_bounds__(256) void k_frame_sad(FerDev d, const uint8_t *skip)
 {
+    __shared__ unsigned wsum[4];
     const int s = blockIdx.y;
-    if (skip && skip[s]) return;  // no picture in this call, or its type is decided already: sad[s] stays 0
+    if (skip && skip[s]) return;  // no picture in this call, or its type is decided already: k_frame_sad_sum writes its 0
     const uint4 *a = (const uint4 *)(d.curY + (size_t)s * d.ysz), *b = (const uint4 *)(d.refY + (size_t)s * d.ysz);
     const size_t n16 = d.ysz / 16, stride = (size_t)gridDim.x * blockDim.x;  // the luma plane is a multiple of 256 bytes
     unsigned acc0 = 0, acc1 = 0;
@@ -1021,12 +1026,27 @@ __global__ __launch_bounds__(256) void k_frame_sad(FerDev d, const uint8_t *skip
         acc1 = __builtin_amdgcn_sad_u8(va.w, vb.w, acc1);
     }
     int v = wave_sum((int)(acc0 + acc1));
-    if ((threadIdx.x & 63) == 0) atomicAdd(&d.sad[s], (unsigned long long)(unsigned)v);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)v;
+    __syncthreads();
+    if (threadIdx.x == 0) d.sad_part[(size_t)s * FER_SAD_G + blockIdx.x] = (unsigned long long)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// One wavefront per stream: lane g holds the partial of workgroup g < G, the butterfly adds them (exact integers: the order
+// does not matter).  The skip mask and the absent-stream rule are k_frame_sad's: such a stream's SAD is 0.
+__global__ __launch_bounds__(256) void k_frame_sad_sum(FerDev d, const uint8_t *skip, int G)
+{
+    const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= d.S) return;
+    unsigned long long t = 0;
+    if (!(skip && skip[s]) && lane < G) t = d.sad_part[(size_t)s * FER_SAD_G + lane];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+    if (lane == 0) d.sad[s] = t;
 }
 
 void fer_launch_frame_sad(const FerDev &d, const uint8_t *skip, hipStream_t st)
 {
-    hipMemsetAsync(d.sad, 0, sizeof(unsigned long long) * d.S, st);
-    const int gx = (int)std::min<size_t>(64, std::max<size_t>(1, d.ysz / 16 / (256 * 8)));  // ~8 words of 16 bytes per lane
+    const int gx = (int)std::min<size_t>(FER_SAD_G, std::max<size_t>(1, d.ysz / 16 / (256 * 8)));  // ~8 words of 16 bytes per lane
     hipLaunchKernelGGL(k_frame_sad, dim3(gx, d.S), dim3(256), 0, st, d, skip);
+    hipLaunchKernelGGL(k_frame_sad_sum, dim3((d.S + 3) / 4), dim3(256), 0, st, d, skip, gx);
 }

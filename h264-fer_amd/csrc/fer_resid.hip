@@ -86,17 +86,14 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
         mvx[i] = (int)(short)(w & 0xffff);
         mvy[i] = w >> 16;
     }
-    int type = FER_P_8x8ref0, stat = 4;
+    int type = FER_P_8x8ref0;
     if (mvx[0] == mvx[1] && mvx[0] == mvx[2] && mvx[0] == mvx[3] && mvy[0] == mvy[1] && mvy[0] == mvy[2] &&
         mvy[0] == mvy[3]) {
         type = FER_P_L0_16x16;
-        stat = 1;
     } else if (mvx[0] == mvx[1] && mvx[2] == mvx[3] && mvy[0] == mvy[1] && mvy[2] == mvy[3]) {
         type = FER_P_16x8;
-        stat = 2;
     } else if (mvx[0] == mvx[2] && mvx[1] == mvx[3] && mvy[0] == mvy[2] && mvy[1] == mvy[3]) {
         type = FER_P_8x16;
-        stat = 3;
     }
     auto mv_of = [&](int q, int &vx, int &vy) {  // vector of quadrant q (q differs per lane)
         const int w = __shfl(tbl, q);
@@ -132,10 +129,7 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
             const int dvx = i < np ? qx - px_ : 0, dvy = i < np ? qy - py_ : 0;
             *(uint32_t *)(d.mvd + ((size_t)s * d.nmb + mb) * 8 + lane * 2) = ((uint32_t)dvx & 0xffffu) | ((uint32_t)dvy << 16);
         }
-        if (lane == 0) {
-            mbt[mb] = type;
-            atomicAdd(&d.stats[s * 5 + stat], 1);
-        }
+        if (lane == 0) mbt[mb] = type;  // brojTipova is counted from these once per picture (k_type_count)
     }
     for (int i = lane; i < FER_LEVELS / 2; i += 64) ((uint32_t *)lvs)[i] = 0u;
     RES_SYNC();
@@ -256,4 +250,55 @@ __global__ __launch_bounds__(64 * RES_MBW) __attribute__((amdgpu_waves_per_eu(RE
 void fer_launch_p_resid(const FerDev &d, hipStream_t st)
 {
     hipLaunchKernelGGL(k_p_resid, dim3((d.nmb + RES_MBW - 1) / RES_MBW, d.S), dim3(64 * RES_MBW), 0, st, d);
+}
+
+// ------------------------------------------------------------------ k_type_count
+// brojTipova of a P picture (F/moestimation.cpp:421,529-560), counted from mb_type when k_p_resid has finished: by then
+// every macroblock of a P stream carries this picture's type (k_me_resolve writes P_Skip or 8x8 for every macroblock,
+// k_p_resid the merged type of those that are not skipped).  One workgroup per stream; a stream that codes an I picture
+// or sits the call out keeps its counts.  The counts accumulate over pictures: nothing else writes these words while
+// the kernel runs (k_basic_stat runs before it on the same stream), so one lane adds with plain loads and stores.
+// The kernel is a chain of round trips to memory, not a stream: sixteen wavefronts, each with four loads in flight, take
+// a 1080p stream's 8 040 entries in two rounds.
+#define CNT_WAVES 16
+#define CNT_DEPTH 4
+__global__ __launch_bounds__(64 * CNT_WAVES) void k_type_count(FerDev d)
+{
+    __shared__ int part[CNT_WAVES][5];
+    const int s = blockIdx.x;
+    if (d.hdr[s * 4 + 3] != 0) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int *mbt = d.mb_type + (size_t)s * d.nmb;
+    int n[5] = {0, 0, 0, 0, 0};
+    for (int i0 = wv * 64; i0 < d.nmb; i0 += 64 * CNT_WAVES * CNT_DEPTH) {  // (uniform over the wavefront: every lane takes part in the ballots)
+        int t[CNT_DEPTH];
+#pragma unroll
+        for (int k = 0; k < CNT_DEPTH; k++) {
+            const int i = i0 + k * 64 * CNT_WAVES + lane;
+            t[k] = i < d.nmb ? mbt[i] : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < CNT_DEPTH; k++) {
+            n[0] += __popcll(__ballot(t[k] == FER_P_SKIP));
+            n[1] += __popcll(__ballot(t[k] == FER_P_L0_16x16));
+            n[2] += __popcll(__ballot(t[k] == FER_P_16x8));
+            n[3] += __popcll(__ballot(t[k] == FER_P_8x16));
+            n[4] += __popcll(__ballot(t[k] == FER_P_8x8ref0));
+        }
+    }
+    if (lane == 0)
+        for (int k = 0; k < 5; k++) part[wv][k] = n[k];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 0; k < 5; k++) {
+        int t = 0;
+        for (int w = 0; w < CNT_WAVES; w++) t += part[w][k];
+        // BasicInterEncoding makes the P_Skip test twice and counts it twice (F/moestimation.cpp:324,421)
+        d.stats[s * 5 + k] += (k == 0 && d.basic) ? 2 * t : t;
+    }
+}
+
+void fer_launch_type_count(const FerDev &d, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_type_count, dim3(d.S), dim3(64 * CNT_WAVES), 0, st, d);
 }

@@ -571,7 +571,8 @@ int ferhip_inter_encoding(ferhip_ctx *c);
 #define FERHIP_BUF_TIMING 14  /* int64  [64] in-kernel wall-clock sums (10 ns units) when FER_DBG bit 7 is set */
 #define FERHIP_BUF_ST2N 15    /* int32  [S][nmb][4] stage-2 candidates of every 8x8 partition (before the list cap) */
 #define FERHIP_BUF_SPEC_STAT 17 /* uint64 [8] since the context was created: partitions the motion chain decided, of which the guessed
-                                 predictor was right, P_Skip verdicts needed, of which taken from the guess */
+                                 predictor was right, P_Skip verdicts needed, of which taken from the guess (kept per workgroup of the
+                                 chain on the device, summed here), then four zero words */
 #define FERHIP_BUF_MBSIZE 18   /* int32  [S][nmb][2] coded_mb_size (F/rbsp_encoding.cpp:330) of the Intra16x16 and of the Intra4x4 alternative of every
                                  macroblock of the last I picture */
 #define FERHIP_BUF_ST2 16     /* int32  [S][nmb][4][384][2] the candidates (position relative to the block, feature distance); a crowded
