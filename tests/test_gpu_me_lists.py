@@ -51,7 +51,11 @@ SHAPES = dict(SUMA=(4, 5), ST3=(4, 33, 3), ST3N=(4,), V0=(4,), SPEC_HDR=(4, 4), 
 
 
 def frames_of(pkg, kind, W, H, seed=1234):
-    """pictures 0 and 1 of a case"""
+    """pictures 0 and 1 of a case; kind "pan:<name>": of that sequence of tests/pan_content.py"""
+    if kind.startswith("pan:"):
+        import pan_content
+        assert (W, H) == pan_content.SEQS[kind[4:]][:2]
+        return tuple(pan_content.frames(kind[4:])[:2])
     if (W, H) == (176, 144) and seed == 1234:
         return _content(pkg, kind, 0), _content(pkg, kind, 1)
     out = []

@@ -69,7 +69,16 @@ def _cases(slices, jend, crowded):
 @pytest.mark.parametrize("window", [32, 48])
 @pytest.mark.parametrize("kind", ["textured", "letterbox", "flat-half", "soft", "patch"])
 def test_walk_matches_model(pkg, fo, kind, window):
-    f0, f1 = _content(pkg, kind, 0), _content(pkg, kind, 1)
+    seen_mid, seen_cap = walk_check(pkg, fo, kind, _content(pkg, kind, 0), _content(pkg, kind, 1), window)
+    if kind in ("soft", "patch"):
+        assert seen_mid > 0, "no partition whose step closes inside a batch that spans slices"
+    if kind == "patch":
+        assert seen_cap > 0, "no partition whose count passes CAP inside a dense batch"
+
+
+def walk_check(pkg, fo, kind, f0, f1, window):
+    """ST2N and ST2 of every partition of QCIF picture f1 searched in the oracle's reconstruction of f0 against the model ->
+    how many partitions showed each of the two lane-level cases of _cases()"""
     o = fo.Oracle(W, H, qp=12, window=window)
     o.set_frame(f0)
     o.encode_slice(5)
@@ -108,7 +117,4 @@ def test_walk_matches_model(pkg, fo, kind, window):
         assert n2[p] == len(ref), (kind, p)
         got = [(int(x), int(y)) for x, y in st2[p, : len(ref)]]
         assert got == [(int(np.uint32(rel & 0xffffffff).view(np.int32)), D) for rel, D in ref], (kind, p)
-    if kind in ("soft", "patch"):
-        assert seen_mid > 0, "no partition whose step closes inside a batch that spans slices"
-    if kind == "patch":
-        assert seen_cap > 0, "no partition whose count passes CAP inside a dense batch"
+    return seen_mid, seen_cap
