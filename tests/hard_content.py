@@ -147,18 +147,23 @@ def oracle_run(fo, W, H, seed, qp, window, planes=False):
     made from this picture's reconstruction.  Computed once per argument set and shared; callers leave it unchanged."""
     key = (W, H, seed, qp, window)
     if key not in _run_cache or (planes and "interp_sat" not in _run_cache[key][0]):
-        o = fo.Oracle(W, H, qp=qp, window=window, maxdiff=3, intra_every=1000)
-        out = []
-        for f, nt in zip(sequence(W, H, seed), NAL_TYPES):
-            o.set_frame(f)
-            r = dict(rbsp=o.encode_slice(nt))
-            r.update(recon=o.frame(), mb_type=o.mb_type(), cbp=o.cbp(), tc=o.tc(), mv=o.mv(), max_level=o.max_level(), stats=o.stats())
-            if nt == 5:
-                r.update(i4mode=o.i4mode(), mbsize=o.mbsize())
-            if planes:
-                p = np.stack([o.interp(k) for k in range(1, 16)])
-                r["interp_sat"] = (int((p == 0).sum()), int((p == 255).sum()))
-            out.append(r)
-        o.close()
-        _run_cache[key] = out
+        _run_cache[key] = oracle_run_frames(fo, W, H, sequence(W, H, seed), qp, window, planes)
     return _run_cache[key]
+
+
+def oracle_run_frames(fo, W, H, frames, qp, window, planes=False):
+    """oracle_run's four dicts for any four pictures (coded IDR, P, P, P), not cached"""
+    o = fo.Oracle(W, H, qp=qp, window=window, maxdiff=3, intra_every=1000)
+    out = []
+    for f, nt in zip(frames, NAL_TYPES):
+        o.set_frame(f)
+        r = dict(rbsp=o.encode_slice(nt))
+        r.update(recon=o.frame(), mb_type=o.mb_type(), cbp=o.cbp(), tc=o.tc(), mv=o.mv(), max_level=o.max_level(), stats=o.stats())
+        if nt == 5:
+            r.update(i4mode=o.i4mode(), mbsize=o.mbsize())
+        if planes:
+            p = np.stack([o.interp(k) for k in range(1, 16)])
+            r["interp_sat"] = (int((p == 0).sum()), int((p == 255).sum()))
+        out.append(r)
+    o.close()
+    return out

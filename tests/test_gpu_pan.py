@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import pan_content as pc
-from test_gpu_hard_content import _coded_tc_mask
+from enc_parity import coded_tc_mask as _coded_tc_mask
 from test_gpu_me_lists import run_case
 from test_gpu_walk_dense import walk_check
 
