@@ -267,7 +267,7 @@ extern "C" void ferhip_destroy(ferhip_ctx *c)
     if (c->nal_buf) hipFree(c->nal_buf);
     for (void *p : c->pinned) hipHostFree(p);
     for (hipEvent_t e : c->events) hipEventDestroy(e);
-    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring, &c->pic_ring, &c->rtp_ring, &c->ts_ring, &c->ts_psi_ring}) r->destroy();
+    for (PinnedRing *r : {&c->hdr_ring, &c->pres_ring, &c->ps_ring, &c->pic_ring, &c->rtp_ring, &c->ts_ring, &c->ts_psi_ring, &c->mp4_ring}) r->destroy();
     for (hipStream_t st : {c->st, c->st_hi, c->st_aux, c->st_copy})
         if (st) hipStreamDestroy(st);
     delete c;
@@ -743,6 +743,7 @@ static int run_picture(ferhip_ctx *c, int *nal_type)
     }
     if (hdr_upload(c)) return FERHIP_E_HIP;
     c->nal_ready = true;
+    c->pic_serial++;
     fer_launch_rc_plan(d, c->st);  // each stream's QP and slice_qp_delta, before anything reads qp[] or hdr[] (fer_rate.hip)
     if (!anyP && !anyI) {
         // every stream sat the call out: k_rc_plan has accounted what was pending and set every RBSP length to 0; no

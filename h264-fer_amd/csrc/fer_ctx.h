@@ -1,5 +1,5 @@
 // fer_ctx.h -- the context of libferhip and the owners of its resources, for the host translation units that drive it
-// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_rtp.hip, fer_ts.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
+// (fer_api.hip, fer_headers.hip, fer_nalpack.hip, fer_rtp.hip, fer_ts.hip, fer_mp4.hip, fer_nalsplit.hip, fer_dec_session.hip, fer_decode_host.hip, fer_decode_live.hip, and
 // fer_mbunit.hip, every buffer of which is a DevBuf).
 #pragma once
 #include "fer_internal.h"
@@ -152,6 +152,19 @@ struct ferhip_ctx {
     uint8_t *d_ts_psi = nullptr;       // device [S][376]: every stream's PAT and PMT packet
     PinnedRing ts_psi_ring;            // [S][376]
     std::vector<uint32_t> ts_psi_ids;  // [S] pid << 16 | pmt_pid of the stream's row, 0 = none yet (empty until the table exists)
+    // fragmented MP4 segments (fer_mp4.hip), on first use.  The open segment's cursors are state[] on the device; the host
+    // keeps only what it was given at open and whether the last picture has been appended
+    uint4 *mp4_state = nullptr;                // device [S]: sample bytes, samples, fault, first sample's NAL unit type
+    unsigned long long *mp4_place = nullptr;   // device [S]: where the append in flight puts each stream's sample
+    ferhip_mp4_hdr *d_mp4_hdr = nullptr;       // device [S]
+    ferhip_mp4_seg *mp4_index = nullptr, *h_mp4_index = nullptr;  // device / pinned [S + 1]: ferhip_mp4_fetch's index
+    PinnedRing mp4_ring;                       // [S] ferhip_mp4_hdr
+    bool mp4_ready = false;                    // the six above exist
+    bool mp4_open = false, mp4_appended = false;
+    uint8_t *mp4_dst = nullptr;                // the open segment: the caller's regions, K and flags
+    size_t mp4_stride = 0;
+    int mp4_K = 0, mp4_flags = 0;
+    unsigned long long pic_serial = 0, mp4_serial = 0;  // picture calls made; the one the last append took
     // live kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof = false;
     struct Span { int phase; hipEvent_t a, b; long launches; };

@@ -1,11 +1,13 @@
 // fer_dec_syntax_host.h -- the first readers of the bytes a caller hands the decoders (ferhip_decode_streams, ferhip_dec_nal,
 // ferhip_decs_*): the bit reader and the SPS, PPS and slice-header parsers (F/headers_and_parameter_sets.cpp:245-298,398-537),
 // the Annex-B and length-prefixed splitters with emulation-prevention removal (F/nal.cpp:68-223), the RTP depacketiser
-// (split_rtp) and the walk over an AVCDecoderConfigurationRecord.  Plain C++ without the HIP runtime, so that it can be
-// compiled into a stand-alone host program and run under a sanitizer (tools/dec_syntax_host_check.cpp,
-// tools/rtp_host_check.cpp).
+// (split_rtp), the transport stream and MP4 fragment demultiplexers (split_ts, split_mp4) and the walk over an
+// AVCDecoderConfigurationRecord.  Plain C++ without the HIP runtime, so that it can be compiled into a stand-alone host
+// program and run under a sanitizer (tools/dec_syntax_host_check.cpp, tools/rtp_host_check.cpp, tools/ts_host_check.cpp,
+// tools/mp4_host_check.cpp).
 #pragma once
 #include "../../include/ferhip.h"
+#include "fer_mp4_host.h"
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -263,10 +265,16 @@ static inline void split_stream(const uint8_t *s, size_t n, std::vector<NalRef> 
 
 // split a length-prefixed range (every unit behind its length of L = 1, 2 or 4 bytes, big-endian; the definition: ferhip.h)
 // like split_stream; an empty unit, one without payload and one that overruns the range end it.  Returns 1 if it overran.
+static inline int split_avcc_at(const uint8_t *s, size_t n, int L, std::vector<NalRef> &out, uint8_t *&w);
 static inline int split_avcc(const uint8_t *s, size_t n, int L, std::vector<NalRef> &out, std::vector<uint8_t> &store)
 {
     if (store.size() < n) store.resize(n);
     uint8_t *w = store.data();
+    return split_avcc_at(s, n, L, out, w);
+}
+// ... with the RBSP appended at w, which moves behind it (room for n bytes)
+static inline int split_avcc_at(const uint8_t *s, size_t n, int L, std::vector<NalRef> &out, uint8_t *&w)
+{
     size_t pos = 0;
     while (n - pos >= (size_t)L) {
         size_t len = 0;
@@ -435,6 +443,61 @@ static inline int split_ts(const TsRun *runs, size_t nruns, unsigned pid, int32_
         if (open) es.resize(pes_at);
     }
     if (!es.empty()) split_stream(es.data(), es.size(), out, store);
+    return fault;
+}
+
+// The fragments of one stream's runs, in order (ISO/IEC 14496-12 movie fragments; the definition: ferhip.h) -> its NAL units:
+// every run is a whole number of top-level boxes, fer_mp4_walk_run (fer_mp4_host.h) gives the samples of its whole fragments,
+// and every sample is one length-prefixed range as split_avcc takes it.  Returns the fault: 0, or the first of
+// FER_MP4_MALFORMED, _UNSUP, _TRUNCATED (the box walk: the samples of the fragments completed in front of it stand) and
+// FER_MP4_OVERRUN (the length walk of a sample: its units in front of the overrun stand), which ends the stream's walk.
+// spans (optional) receives every sample that stands as (run, offset in the run, bytes).
+struct Mp4Span {
+    size_t run;
+    uint64_t at;
+    uint32_t len;
+};
+struct Mp4HostSink {
+    std::vector<Mp4Span> &spans;
+    size_t run;
+    int64_t entries(const uint8_t *sizes, uint32_t count, uint32_t e, uint32_t dflt, int64_t at, uint64_t index)
+    {
+        if (spans.size() < index + count) spans.resize((size_t)(index + count));
+        for (uint32_t k = 0; k < count; k++) {
+            const uint32_t size = sizes ? fer_mp4_be32(sizes + (size_t)k * e) : dflt;
+            spans[(size_t)index + k] = {run, (uint64_t)at, size};
+            at += size;
+        }
+        return at;
+    }
+};
+static inline int split_mp4(const TsRun *runs, size_t nruns, int L, std::vector<NalRef> &out, std::vector<uint8_t> &store,
+                            std::vector<Mp4Span> *spans_out = nullptr)
+{
+    std::vector<Mp4Span> spans;
+    uint64_t done = 0;
+    int fault = 0;
+    for (size_t r = 0; r < nruns && !fault; r++) {
+        Mp4HostSink sink{spans, r};
+        fault = fer_mp4_walk_run(runs[r].p, runs[r].n, done, sink);
+    }
+    spans.resize((size_t)done);  // what a fragment that did not complete recorded goes
+    size_t total = 0;
+    for (const Mp4Span &sp : spans) total += sp.len;
+    if (store.size() < total) store.resize(total);
+    uint8_t *w = store.data();
+    size_t kept = spans.size();
+    for (size_t k = 0; k < spans.size(); k++) {
+        if (split_avcc_at(runs[spans[k].run].p + spans[k].at, spans[k].len, L, out, w)) {
+            if (!fault) fault = FER_MP4_OVERRUN;
+            kept = k + 1;
+            break;
+        }
+    }
+    if (spans_out) {
+        spans.resize(kept);
+        *spans_out = spans;
+    }
     return fault;
 }
 

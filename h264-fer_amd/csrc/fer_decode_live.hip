@@ -472,6 +472,45 @@ extern "C" int ferhip_decs_decode_ts(ferhip_decs *d, const void *base, int base_
     return decs_run(d, out, out_on_device, pictures, status);
 }
 
+// MP4 movie fragments (ISO/IEC 14496-12), the runs of every stream in table order, into the same unit lists as the other
+// framings, from host memory through split_mp4 (no synchronisation of its own).  Fragments in device memory are not taken
+// yet: FERHIP_E_UNSUP.
+extern "C" int ferhip_decs_decode_mp4(ferhip_decs *d, const void *base, int base_on_device, const ferhip_mp4_run *runs, size_t nruns,
+                                      int length_size, uint8_t *out, int out_on_device, int *pictures, int *status)
+{
+    if (!d || !pictures || !status || (nruns && (!base || !runs)) || (length_size != 1 && length_size != 2 && length_size != 4) ||
+        decs_layout_check(d, out, out_on_device))
+        return FERHIP_E_ARG;
+    const int S = d->S;
+    for (size_t k = 0; k < nruns; k++)
+        if (runs[k].stream >= (uint32_t)S) return FERHIP_E_ARG;
+    if (base_on_device) return FERHIP_E_UNSUP;
+    if (hipSetDevice(d->ss.c->device) != hipSuccess) return FERHIP_E_HIP;
+    const uint8_t *const none = nullptr;
+    std::vector<const uint8_t *> no_chunks(S, none);
+    std::vector<size_t> no_lens(S, 0);
+    decs_begin_call(d, no_chunks.data(), no_lens.data(), pictures, status);
+    const double ts = dec_now();
+    std::vector<std::vector<TsRun>> per(S);  // a stable sort by stream
+    for (size_t k = 0; k < nruns; k++) per[runs[k].stream].push_back({(const uint8_t *)base + runs[k].offset, runs[k].bytes});
+    bool too_many = false;
+    for (int s = 0; s < S; s++) {
+        if (!per[s].empty()) d->overrun[s] = split_mp4(per[s].data(), per[s].size(), length_size, d->nals[s], d->store[s]) != 0;
+        size_t slices = 0;
+        for (const NalRef &n : d->nals[s]) slices += n.type == 1 || n.type == 5;
+        too_many |= slices > (size_t)d->P;
+    }
+    d->t_split += dec_now() - ts;
+    if (too_many) {  // refused as a whole: nothing was taken
+        for (int s = 0; s < S; s++) {
+            d->nals[s].clear();
+            d->overrun[s] = 0;
+        }
+        return FERHIP_E_ARG;
+    }
+    return decs_run(d, out, out_on_device, pictures, status);
+}
+
 extern "C" int ferhip_decs_timing(ferhip_decs *d, double *t, int reset)
 {
     if (!d || !t) return FERHIP_E_ARG;

@@ -69,6 +69,12 @@ TS_AU = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nal_type", np.i
 TS_RUN = RTP_PKT
 TS_PSI = 8  # FERHIP_TS_PSI
 assert (TS_HDR.itemsize, TS_AU.itemsize) == (24, 24)
+# ferhip_mp4_hdr, ferhip_mp4_seg: the caller's fields of a stream's segment and one entry of the index of ferhip_mp4_close /
+# ferhip_mp4_fetch / ferhip_mp4_blocks
+MP4_HDR = np.dtype([("decode_time", np.uint64), ("sequence", np.uint32), ("duration", np.uint32)])
+MP4_SEG = np.dtype([("offset", np.uint64), ("bytes", np.uint32), ("nsamples", np.uint32), ("first_nal_type", np.int32), ("fault", np.uint32)])
+MP4_RUN = RTP_PKT
+assert (MP4_HDR.itemsize, MP4_SEG.itemsize) == (16, 24)
 
 
 def rtp_hdr(n, ssrc=0, timestamp=0, seq=0, payload_type=96):
@@ -83,6 +89,18 @@ def ts_hdr(n, pts=0, pcr=0, pid=0x100, pmt_pid=0x1000, cc=0, psi_cc=0):
     h = np.zeros(n, TS_HDR)
     h["pts"], h["pcr"], h["pid"], h["pmt_pid"], h["cc"], h["psi_cc"] = pts, pcr, pid, pmt_pid, cc, psi_cc
     return h
+
+
+def mp4_hdr(n, decode_time=0, sequence=1, duration=1):
+    """n entries of dtype MP4_HDR; every argument a scalar or a sequence of n"""
+    h = np.zeros(n, MP4_HDR)
+    h["decode_time"], h["sequence"], h["duration"] = decode_time, sequence, duration
+    return h
+
+
+def mp4_data_offset(max_samples):
+    """D of include/ferhip.h: where the samples of a region begin"""
+    return (104 + 12 * int(max_samples) + 15) & ~15
 
 
 class Quality:
@@ -201,6 +219,15 @@ def load_library():
     lib.ferhip_ts_blocks.argtypes = [vp, sz, vp, vp, sz, vp, vp, sz, vp]
     lib.ferhip_write_ts_psi.argtypes = [i, i, i, vp, sz]
     lib.ferhip_write_ts_psi.restype = sz
+    lib.ferhip_mp4_open.argtypes = [vp, i, i, vp, vp, sz]
+    lib.ferhip_mp4_append.argtypes = [vp]
+    lib.ferhip_mp4_close.argtypes = [vp, vp]
+    lib.ferhip_mp4_fetch.argtypes = [vp, vp, sz, vp]
+    lib.ferhip_write_mp4_init.argtypes = [vp, i, C.c_uint32, vp, sz]
+    lib.ferhip_write_mp4_init.restype = sz
+    lib.ferhip_mp4_blocks.argtypes = [vp, sz, vp, vp, sz, sz, i, vp, vp, sz, vp]
+    lib.ferhip_decs_decode_mp4.argtypes = [vp, vp, i, vp, sz, i, vp, i, C.POINTER(i), C.POINTER(i)]
+    lib.ferhip_mp4_find_avcc.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
     lib.ferhip_decs_decode_ts.argtypes = [vp, vp, i, vp, sz, vp, vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_unts_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, vp, vp, sz, vp, sz, C.POINTER(sz), vp, vp]
     lib.ferhip_decs_decode_rtp.argtypes = [vp, vp, i, vp, sz, vp, i, C.POINTER(i), C.POINTER(i)]
@@ -633,6 +660,44 @@ class FerHip:
         _chk(rc, "ferhip_fetch_ts")
         return [bytes(buf[int(idx["offset"][s]): int(idx["offset"][s]) + int(idx["bytes"][s])]) for s in range(self.S)], idx
 
+    # --- fragmented MP4 segments on the device
+    def mp4_open(self, hdr, max_samples, dst_ptr, stride, flags=0):
+        """ferhip_mp4_open: begin a segment of at most max_samples pictures per stream in device memory at dst_ptr (16-byte
+        aligned; stream s owns stride bytes at dst_ptr + s * stride).  hdr: S entries of dtype MP4_HDR (mp4_hdr); the caller
+        advances decode_time by nsamples * duration and sequence by 1 from segment to segment."""
+        h = np.ascontiguousarray(hdr, MP4_HDR)
+        assert h.size == self.S
+        _chk(self.lib.ferhip_mp4_open(self.ctx, int(flags), int(max_samples), h.ctypes.data, C.c_void_p(int(dst_ptr)), int(stride)), "ferhip_mp4_open")
+
+    def mp4_append(self):
+        """ferhip_mp4_append: the last picture of every stream that coded one becomes the stream's next sample (asynchronous)"""
+        _chk(self.lib.ferhip_mp4_append(self.ctx), "ferhip_mp4_append")
+
+    def mp4_close_device(self, index_ptr):
+        """ferhip_mp4_close: moof, free and mdat headers into every region, the index (S + 1 records of dtype MP4_SEG) to
+        device memory at index_ptr (asynchronous; sync() before reading)"""
+        _chk(self.lib.ferhip_mp4_close(self.ctx, C.c_void_p(int(index_ptr))), "ferhip_mp4_close")
+
+    def mp4_fetch_raw(self, cap, fill=0):
+        """ferhip_mp4_fetch into a new host buffer -> (return code, buffer [cap], index [S + 1] of dtype MP4_SEG)"""
+        buf = np.full(max(int(cap), 1), fill, np.uint8)
+        idx = np.zeros(self.S + 1, MP4_SEG)
+        rc = self.lib.ferhip_mp4_fetch(self.ctx, buf.ctypes.data, int(cap), idx.ctypes.data)
+        return rc, buf, idx
+
+    def mp4_fetch(self, cap):
+        """Close the segment and bring it to the host (waits) -> (list per stream of its moof + mdat as bytes, b"" for the
+        streams without a sample; the index of dtype MP4_SEG).  cap: at least the sum of the segments, S * stride at most."""
+        rc, buf, idx = self.mp4_fetch_raw(cap)
+        _chk(rc, "ferhip_mp4_fetch")
+        return [bytes(buf[int(idx["offset"][s]): int(idx["offset"][s]) + int(idx["bytes"][s])]) for s in range(self.S)], idx
+
+    def mp4_init(self, stream, timescale, cap=1024):
+        """ferhip_write_mp4_init: the initialisation segment (ftyp + moov) of a stream, b"" where the library refuses"""
+        o = np.zeros(max(int(cap), 1), np.uint8)
+        n = self.lib.ferhip_write_mp4_init(self.ctx, int(stream), int(timescale), o.ctypes.data, int(cap))
+        return bytes(o[:n])
+
     # --- rate control
     def set_rate(self, stream=-1, mode=RC_CQP, qp=None, qp_min=0, qp_max=51, max_step=2, ip_offset=3, window=0,
                  target_bits=0, target_sse=0, target_psnr=None):
@@ -1022,6 +1087,26 @@ def ts_blocks_raw(payloads, nal_types, hdr, cap=None, fill=0xA5):
     return rc, out, idx
 
 
+def mp4_blocks_raw(payloads, nal_types, m, max_samples, hdr, stride, fill=0xA5):
+    """ferhip_mp4_blocks on a list of payloads (bytes or uint8 arrays), one slice unit each, in segments of m consecutive
+    payloads -> (return code, out [nseg][stride] pre-filled with `fill`, index [nseg + 1] of dtype MP4_SEG)"""
+    lib = load_library()
+    n = len(payloads)
+    nseg = (n + int(m) - 1) // int(m) if m > 0 else 1
+    lens = np.array([len(p) for p in payloads], np.uint32)
+    pstride = max(int(lens.max()) if n else 0, 1)
+    src = np.zeros((max(n, 1), pstride), np.uint8)
+    for k, p in enumerate(payloads):
+        src[k, : len(p)] = np.frombuffer(bytes(p), np.uint8) if not isinstance(p, np.ndarray) else p
+    out = np.full((max(nseg, 1), max(int(stride), 1)), fill, np.uint8)
+    idx = np.zeros(nseg + 1, MP4_SEG)
+    h = np.ascontiguousarray(hdr, MP4_HDR)
+    nt = np.ascontiguousarray(nal_types, np.int32)
+    rc = lib.ferhip_mp4_blocks(src.ctypes.data, pstride, lens.ctypes.data, nt.ctypes.data, n, int(m), int(max_samples), h.ctypes.data,
+                               out.ctypes.data, int(stride), idx.ctypes.data)
+    return rc, out, idx
+
+
 def write_ts_psi(pid, pmt_pid, psi_cc, cap=376):
     """ferhip_write_ts_psi -> the PAT and the PMT packet as bytes, b"" where the library refuses"""
     o = np.zeros(max(int(cap), 1), np.uint8)
@@ -1053,6 +1138,14 @@ def unts_blocks_raw(base, runs, pids, cc_expect=None, misalign=0, cap=None, unit
                                 int(misalign), pid.ctypes.data if pid.size else None, exp.ctypes.data if exp.size else None, out.ctypes.data,
                                 int(cap), units.ctypes.data, int(units_cap), C.byref(count), fault.ctypes.data, nxt.ctypes.data)
     return rc, out, units, count.value, fault[:nstreams], nxt[:nstreams]
+
+
+def mp4_find_avcc(init):
+    """ferhip_mp4_find_avcc -> (offset, length) of the avcC box's content in an initialisation segment, or None"""
+    b = np.frombuffer(bytes(init), np.uint8)
+    off, n = C.c_size_t(0), C.c_size_t(0)
+    rc = load_library().ferhip_mp4_find_avcc(b.ctypes.data if b.size else None, b.size, C.byref(off), C.byref(n))
+    return (off.value, n.value) if rc == 0 else None
 
 
 def unrtp_blocks_raw(base, pkts, nstreams, seq_expect=None, misalign=0, cap=None, units_cap=None, fill=0xA5):
@@ -1344,6 +1437,27 @@ class LiveDecoder:
         pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
         _chk(self.lib.ferhip_decs_decode_ts(self.h, C.c_void_p(ptr_in), int(bool(base_on_device)), rows.ctypes.data if rows.size else None,
                                             rows.size, pid.ctypes.data, C.c_void_p(out.ctypes.data), 0, pics, status), "ferhip_decs_decode_ts")
+        return out, list(pics), list(status)
+
+    def decode_mp4(self, base, runs, length_size=4, out=None, base_on_device=False):
+        """ferhip_decs_decode_mp4: MP4 movie fragments -> (out, pictures, status) like decode().
+        base: the bytes that hold the fragments (bytes or a uint8 array; an integer device address with base_on_device,
+        which the library refuses for now: FERHIP_E_UNSUP);
+        runs: rows of dtype MP4_RUN (offset from base, bytes, stream), each a whole number of top-level boxes, in arrival
+        order.  out: a host uint8 array or None."""
+        if base_on_device:
+            ptr_in = int(base)
+        else:
+            keep = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+            ptr_in = keep.ctypes.data if keep.size else None
+        rows = np.ascontiguousarray(runs, MP4_RUN)
+        if out is None:
+            out = np.zeros((self.P, self.S, self.fsz), np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < self.P * self.S * self.fsz:
+            raise FerHipError("LiveDecoder.decode_mp4: out must be a C-contiguous uint8 array of [max_pictures][S][W*H*3/2]")
+        pics, status = (C.c_int * self.S)(), (C.c_int * self.S)()
+        _chk(self.lib.ferhip_decs_decode_mp4(self.h, C.c_void_p(ptr_in), int(bool(base_on_device)), rows.ctypes.data if rows.size else None,
+                                             rows.size, int(length_size), C.c_void_p(out.ctypes.data), 0, pics, status), "ferhip_decs_decode_mp4")
         return out, list(pics), list(status)
 
     def decode_dev(self, ptrs, lens, out=None):

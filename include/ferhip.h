@@ -413,6 +413,86 @@ int ferhip_ts_blocks(const uint8_t *payloads, size_t stride, const uint32_t *len
                      const ferhip_ts_hdr *hdr /* [n] */, uint8_t *out, size_t cap, ferhip_ts_au *index /* [n+1] */);
 size_t ferhip_write_ts_psi(int pid, int pmt_pid, int psi_cc, uint8_t *out, size_t cap);
 
+/* ---- Fragmented MP4 on the device: media segments of many pictures (ISO/IEC 14496-12, 14496-15; CMAF, DASH, MSE) ----
+ * The fifth framing, and the first that holds more than one picture: a segment -- one moof and one mdat -- per stream is
+ * accumulated in device memory over any number of encode calls, the write cursors live on the device, and the host reads
+ * nothing until the segment is closed.  All integers are big-endian; a box is a u32 size, a 4-byte type and size - 8
+ * content bytes.
+ * Region.  ferhip_mp4_open starts a segment of at most K = max_samples pictures per stream (1 <= K <= 4096).  Stream s
+ * owns d_dst + s * stride (d_dst 16-byte aligned, stride a multiple of 16 and < 2^31).  D = 104 + 12 K rounded up to 16 is
+ * where the samples begin; stride >= D + 16.  hdr[s] (host, read before the call returns) = the segment's sequence number,
+ * the decode time of its first sample and the duration of every sample, in the track's timescale.
+ * Samples.  ferhip_mp4_append, behind a ferhip_encode_picture[_dev] call, adds that call's picture of every stream that
+ * coded one as the stream's sample n = 0, 1, ...; a stream without a picture (FERHIP_NAL_NONE) adds nothing.  A sample is
+ * the stream's entry exactly as ferhip_pack_nal writes it with FERHIP_AU_AVCC -- with FERHIP_AU_PARAM_SETS in the
+ * segment's flags, with FERHIP_AU_AVCC | FERHIP_AU_PARAM_SETS -- and starts at D + the sizes of the samples in front:
+ * samples are contiguous, at whatever byte phase that gives.  Append also writes trun entry n at region offset 88 + 12 n:
+ * u32 hdr[s].duration, u32 sample size, u32 sample_flags = 0x02000000 for an IDR slice (sample_depends_on 2: an I
+ * picture, a sync sample) and 0x01010000 otherwise (sample_depends_on 1, sample_is_non_sync_sample).  It waits for
+ * nothing, copies nothing to the host and, after the segment's first append, allocates nothing.
+ * Faults.  A sample that would end beyond stride sets the stream's fault to 1, a sample number K + 1 sets it to 2; from a
+ * faulted sample on nothing more is added to that stream in this segment, and the samples in front stand.  No byte at or
+ * beyond a region's end and no byte of another region is ever touched.
+ * ferhip_mp4_close writes, for a stream with n >= 1 samples of M bytes in all, the front of its region:
+ *      0  moof, size 88 + 12 n
+ *      8  mfhd: 00000010 'mfhd' 00000000 (version, flags) u32 sequence
+ *     24  traf, size 64 + 12 n
+ *     32  tfhd: 00000010 'tfhd' 00020000 (default-base-is-moof) 00000001 (track_ID)
+ *     48  tfdt: 00000014 'tfdt' 01000000 (version 1) u64 decode_time
+ *     68  trun: size 20 + 12 n, 'trun', 00000701 (data-offset, sample duration, size and flags present), u32 n,
+ *         i32 data_offset = D (from the moof's first byte), then the n entries already in place
+ *     88 + 12 n  free, size D - 96 - 12 n, content zero
+ *     D - 8      mdat, size 8 + M; the samples follow
+ * and index[s] = (s * stride, D + M, n, NAL unit type of the first sample's slice, fault).  A stream with n = 0 has zeros
+ * (offset and fault only, if it faulted on its first sample) and nothing of its region is written.  index[S] = (0, streams
+ * with n >= 1, total samples, 0, OR of the faults).  Close ends the segment and is asynchronous like append (d_index
+ * 8-byte aligned).  ferhip_mp4_fetch is close plus the segments back to back in host memory, in stream order without gaps:
+ * h_index[s].offset is then the offset in h_dst; it waits once for the index and once for the copies, one per stream.  If
+ * cap is short it fills h_index and returns FERHIP_E_ARG; the segment is closed all the same and stays in the regions.
+ * The library keeps no MP4 state beyond the open segment: the caller advances decode_time by nsamples * duration and
+ * sequence by 1.
+ * FERHIP_E_STATE: open while a segment is open; append, close or fetch with none open; append twice behind one encode
+ * call; append before the context's first picture.  FERHIP_E_ARG: null pointers, a misaligned d_dst, d_index or stride, K
+ * or stride out of range, a flag other than FERHIP_AU_PARAM_SETS.  The other framings may be called freely while a segment
+ * is open and change nothing of it; ferhip_reset_stream inside a segment is allowed (the stream's next sample is then an
+ * IDR slice), and ferhip_destroy with a segment open is clean.
+ * ferhip_write_mp4_init (host): the initialisation segment of stream s, 0 if cap is short, s is out of range or timescale
+ * is 0; it follows ferhip_set_display_size and ferhip_set_rate as the SPS and PPS writers do.  Fields not named are 0:
+ *   ftyp  major 'iso6', minor 0, compatible 'iso6' 'cmfc' 'avc1'
+ *   moov
+ *     mvhd  version 0; timescale; duration 0; rate 00010000; volume 0100; the unity matrix 00010000 0 0 0 00010000 0 0 0
+ *           40000000; next_track_ID 2
+ *     trak
+ *       tkhd  version 0, flags 000003 (enabled, in movie); track_ID 1; duration 0; the unity matrix; width and height =
+ *             the display size in 16.16
+ *       mdia
+ *         mdhd  version 0; timescale; duration 0; language 55C4 ('und')
+ *         hdlr  handler 'vide'; name = one 00 byte
+ *         minf
+ *           vmhd  flags 000001
+ *           dinf  dref: entry_count 1, one 'url ' box with flags 000001 (the media is in this file) and no content
+ *           stbl
+ *             stsd  entry_count 1, one 'avc1' entry: data_reference_index 1; u16 width, u16 height = the display size;
+ *                   horizontal and vertical resolution 00480000 (72 dpi); frame_count 1; a compressor name of 32 zero
+ *                   bytes; depth 0018; pre_defined FFFF (-1); then the avcC box, whose content is the record of
+ *                   ferhip_write_avcc_config(c, s, ...)
+ *             stts, stsc, stco  entry_count 0;  stsz  sample_size 0, sample_count 0
+ *     mvex  trex: track_ID 1, default_sample_description_index 1, default duration, size and flags 0
+ * ferhip_mp4_blocks: known-answer surface with the conventions of ferhip_ts_blocks: n host payloads, one slice unit each
+ * with its nal_type (no parameter sets), in segments of m consecutive payloads (the last may be shorter: nseg = ceil(n /
+ * m)), hdr[nseg], K = max_samples and stride as above; out (host, nseg * stride bytes: bytes the kernels do not write keep
+ * the caller's values) receives the regions and index[nseg + 1] the index.  n <= 65535, m >= 1.
+ * The way in is ferhip_decs_decode_mp4, with the decoders below. */
+typedef struct { uint64_t decode_time; uint32_t sequence, duration; } ferhip_mp4_hdr; /* 16 bytes, host */
+typedef struct { uint64_t offset; uint32_t bytes, nsamples; int32_t first_nal_type; uint32_t fault; } ferhip_mp4_seg; /* 24 bytes */
+int ferhip_mp4_open(ferhip_ctx *c, int flags, int max_samples, const ferhip_mp4_hdr *hdr /* host [S] */, void *d_dst, size_t stride);
+int ferhip_mp4_append(ferhip_ctx *c);
+int ferhip_mp4_close(ferhip_ctx *c, ferhip_mp4_seg *d_index /* [S+1] */);
+int ferhip_mp4_fetch(ferhip_ctx *c, void *h_dst, size_t cap, ferhip_mp4_seg *h_index /* [S+1] */);
+size_t ferhip_write_mp4_init(ferhip_ctx *c, int s, uint32_t timescale, uint8_t *out, size_t cap);
+int ferhip_mp4_blocks(const uint8_t *payloads, size_t pstride, const uint32_t *lens, const int32_t *nal_type, size_t n, size_t m,
+                      int max_samples, const ferhip_mp4_hdr *hdr /* [nseg] */, uint8_t *out, size_t stride, ferhip_mp4_seg *index /* [nseg+1] */);
+
 /* encode() + NastaviEncode() for S streams of T pictures each (F/fer_h264.cpp:55-134), each stream with its own PPS:
  * frames host [T][S][W*H*3/2]; out host [S][out_stride] Annex-B; out_len[S].
  * recon (optional) host [T][S][W*H*3/2]. */
@@ -869,6 +949,53 @@ int ferhip_decs_decode_ts(ferhip_decs *d, const void *base, int base_on_device, 
 int ferhip_unts_blocks(const uint8_t *base, size_t base_bytes, const ferhip_ts_run *runs, size_t nruns, int nstreams, int misalign,
                        const uint16_t *pids, const int32_t *cc_expect /* [nstreams], -1 = none */, uint8_t *out, size_t cap,
                        ferhip_nal_unit *units, size_t units_cap, size_t *nunits, int32_t *fault, int32_t *cc_next /* -1 after a fault */);
+
+/* ---- MP4 fragments into the live decoder ----
+ * ferhip_decs_decode_mp4 takes movie fragments as ferhip_mp4_close writes them -- or as another muxer does -- "where they
+ * lie": runs[] (host) names byte ranges of base (host memory), each a whole number of
+ * top-level boxes of one stream; the runs of one stream are taken in table order, and streams may interleave.
+ * The box walk.  A run r[0, n) is walked from pos = 0 while pos < n:
+ *  1. Box header.  Fewer than 8 bytes left: malformed.  size = the u32 at pos, type = the next four bytes, h = 8.  size 1:
+ *     h = 16, fewer than 16 bytes left is malformed, and size = the u64 at pos + 8.  size 0: the box runs to the end of its
+ *     container.  Otherwise size < h, or pos + size beyond the container, is malformed.  The same rule walks the children of
+ *     moof and traf, and all of a container's children are walked before any of them is read.  pos advances by size >= 8.
+ *  2. moof.  Its first traf that holds a trun is the track; a second such traf is unsupported; a traf without a trun is
+ *     skipped.  The track's first tfhd (none: malformed): base-data-offset (flag 0x000001) is unsupported; the optional
+ *     fields are skipped in order by the flags 0x2, 0x8, 0x10 (default_sample_size, kept) and 0x20; a field beyond the
+ *     box is malformed.  Every trun in order: version above 1 is unsupported; sample_count; data_offset (0x1, signed);
+ *     first_sample_flags (0x4, skipped); then per sample duration (0x100, skipped), size (0x200), flags (0x400, skipped),
+ *     composition offset (0x800, skipped); fields or entries beyond the box are malformed.  A sample's size is its
+ *     entry's, else the tfhd default; with neither (and a count above 0) malformed.  The first trun must carry a
+ *     data_offset, else unsupported; its samples begin at the moof's first byte + data_offset and follow each other; a
+ *     later trun begins at its own data_offset, or behind the previous trun's samples.  A trun without any per-sample
+ *     field has entries of no bytes, so nothing above bounds its count: it is malformed if it would bring the samples of
+ *     its run (those of the fragments in front included) above the run's n bytes.
+ *  3. mdat.  With a moof pending, every one of its samples must lie inside this box's content, else malformed; the
+ *     samples then stand, in order.  Without a pending moof the box is skipped.
+ *  4. A moof still pending at another moof or at the run's end is truncated: a call takes whole fragments.
+ *  5. Every other type is skipped by its size: ftyp, styp, moov, sidx, free, skip, emsg and anything unknown.
+ * Faults: 2 malformed, 3 unsupported, 4 truncated, and 1 the overrun of the length walk inside a sample.  The first fault
+ * ends the stream's walk; the samples of the fragments completed in front of it stand.  Each standing sample is one range of
+ * the length-prefixed definition above with L = length_size in {1, 2, 4}; a sample of size 0 holds no units; behind a
+ * sample whose walk overruns, nothing more of the stream is taken.
+ * Pictures, pictures[], status[] and the isolation rules are those of ferhip_decs_decode given the same NAL units; every
+ * fault gives status[s] = FERHIP_E_ARG: the units in front of it decode, the stream restarts at its next IDR slice, the other
+ * streams are untouched.  Refused before anything is taken (FERHIP_E_ARG), as ferhip_decs_decode_ts refuses: null
+ * pointers, a stream outside [0, S), a length_size outside {1, 2, 4}, and a call in which a stream's units hold more
+ * slices than max_pictures.  The call mixes freely with the other decode calls and does not depend on
+ * ferhip_decs_set_input.  The parameter sets come inside the IDR samples (FERHIP_AU_PARAM_SETS) or from
+ * ferhip_decs_set_config with the record that ferhip_mp4_find_avcc finds in the initialisation segment.
+ * base_on_device = 0: the walk runs on the host (split_mp4), without a synchronisation of its own.  base_on_device = 1 is
+ * not provided yet and returns FERHIP_E_UNSUP before anything is taken: a device walk needs the length-prefixed splitter to
+ * take its ranges from a table in device memory, which it does not do yet.  Until then a receiver whose fragments lie in
+ * device memory copies them to the host, or hands the decoder the samples as FERHIP_IN_AVCC chunks.
+ * ferhip_mp4_find_avcc (host): walks moov, trak, mdia, minf, stbl, stsd of an initialisation segment; behind the 8 bytes of
+ * stsd the first entry must be avc1 or avc3, and behind the 78 bytes of its visual sample entry the child avcC is looked
+ * for; off and len name that child's content.  FERHIP_E_ARG if anything is missing or overruns. */
+typedef ferhip_rtp_pkt ferhip_mp4_run; /* (offset, bytes, stream): a whole number of top-level boxes */
+int ferhip_decs_decode_mp4(ferhip_decs *d, const void *base, int base_on_device, const ferhip_mp4_run *runs /* host */, size_t nruns,
+                           int length_size, uint8_t *out, int out_on_device, int *pictures, int *status);
+int ferhip_mp4_find_avcc(const uint8_t *init, size_t n, size_t *off, size_t *len);
 
 /* ---- Y4M ingest (row f3): LoadY4MHeader / ReadFromY4M of F/fileIO.cpp:228-346 without the globals ----
  * The picture size comes from the header's " W" / " H" tokens; coded size = cropped to multiples of 16 around the
