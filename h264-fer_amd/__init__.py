@@ -12,6 +12,7 @@ from .ferhip import (FerHip, FerHipError, Decoder, LiveDecoder, access_units, De
                      NAL_UNIT, SPLIT_PREFIX, split_nal_blocks, split_nal_blocks_raw, FMT_I420, FMT_NV12, FMT_YUY2, FMT_UYVY, FMT_BGRA, FMT_RGBA, CSC_BT601, CSC_BT709, Pic, pic_table,
                      AU_AVCC, IN_ANNEXB, IN_AVCC, split_avcc_blocks_raw, RTP_HDR, RTP_PKT, RTP_AU, rtp_hdr, rtp_blocks_raw, unrtp_blocks_raw,
                      TS_HDR, TS_AU, TS_RUN, TS_PSI, ts_hdr, ts_blocks_raw, unts_blocks_raw, write_ts_psi,
-                     MP4_HDR, MP4_SEG, MP4_RUN, mp4_hdr, mp4_data_offset, mp4_blocks_raw, mp4_find_avcc)
+                     MP4_HDR, MP4_SEG, MP4_RUN, mp4_hdr, mp4_data_offset, mp4_blocks_raw, mp4_find_avcc,
+                     SRTP_KEY, SRTP_INDEX, SRTP_PROTECT, SRTP_UNPROTECT, Srtp, srtp_derive, srtp_keys, srtp_blocks_raw)
 from .synth import gen_frame, gen_frames, crop_to_mb, pad_to_mb  # noqa: F401
 from .shard import gops_of_rank, merge_gop_streams, split_nals  # noqa: F401

@@ -24,6 +24,9 @@ struct ferhip_decs {
     double t_split = 0;                       // seconds in the host splitter
 };
 
+// the decoder's context for a pass that runs in front of it on its stream (fer_srtp.hip)
+__attribute__((visibility("hidden"))) ferhip_ctx *fer_decs_ctx(ferhip_decs *d) { return d->ss.c; }
+
 // Stream s back to the state of a new decoder; forget_ps = also forget its parameter sets, else keep them and refuse
 // P slices until the next IDR slice
 static int decs_reset(ferhip_decs *d, int s, bool forget_ps)

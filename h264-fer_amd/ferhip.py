@@ -77,6 +77,13 @@ MP4_RUN = RTP_PKT
 assert (MP4_HDR.itemsize, MP4_SEG.itemsize) == (16, 24)
 
 
+# ferhip_srtp_key, ferhip_srtp_index: a stream's master key and salt, and its packet index state (roc, s_l, set)
+SRTP_KEY = np.dtype([("master_key", np.uint8, 16), ("master_salt", np.uint8, 14), ("set", np.uint8), ("reserved", np.uint8)])
+SRTP_INDEX = np.dtype([("roc", np.uint32), ("s_l", np.uint16), ("set", np.uint16)])
+SRTP_PROTECT, SRTP_UNPROTECT = 0, 1
+assert (SRTP_KEY.itemsize, SRTP_INDEX.itemsize) == (32, 8)
+
+
 def rtp_hdr(n, ssrc=0, timestamp=0, seq=0, payload_type=96):
     """n entries of dtype RTP_HDR; every argument a scalar or a sequence of n"""
     h = np.zeros(n, RTP_HDR)
@@ -232,6 +239,17 @@ def load_library():
     lib.ferhip_unts_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, vp, vp, sz, vp, sz, C.POINTER(sz), vp, vp]
     lib.ferhip_decs_decode_rtp.argtypes = [vp, vp, i, vp, sz, vp, i, C.POINTER(i), C.POINTER(i)]
     lib.ferhip_unrtp_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz, C.POINTER(sz), vp, vp]
+    lib.ferhip_srtp_create.argtypes = [C.POINTER(vp), i]
+    lib.ferhip_srtp_destroy.argtypes = [vp]
+    lib.ferhip_srtp_destroy.restype = None
+    lib.ferhip_srtp_set_key.argtypes = [vp, i, vp, vp]
+    lib.ferhip_srtp_derive.argtypes = [vp, vp, vp]
+    lib.ferhip_srtp_get_index.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(i)]
+    lib.ferhip_srtp_set_index.argtypes = [vp, i, C.c_uint32, C.c_uint32, i]
+    lib.ferhip_srtp_protect.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp]
+    lib.ferhip_srtp_protect_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp]
+    lib.ferhip_srtp_unprotect.argtypes = [vp, vp, vp, i, vp, sz, vp, sz, vp, vp]
+    lib.ferhip_srtp_blocks.argtypes = [i, vp, vp, i, vp, sz, vp, sz, i, vp, sz, vp, vp, vp]
     lib.ferhip_decs_timing.argtypes = [vp, C.POINTER(C.c_double), i]
     lib.ferhip_split_nal_blocks.argtypes = [vp, sz, vp, sz, i, vp, sz, vp, sz, C.POINTER(sz)]
     lib.ferhip_split_avcc_blocks.argtypes = [vp, sz, vp, sz, i, i, vp, sz, vp, sz, C.POINTER(sz), vp]
@@ -1169,6 +1187,122 @@ def unrtp_blocks_raw(base, pkts, nstreams, seq_expect=None, misalign=0, cap=None
                                  int(misalign), exp.ctypes.data, out.ctypes.data, int(cap), units.ctypes.data, int(units_cap), C.byref(count),
                                  fault.ctypes.data, nxt.ctypes.data)
     return rc, out, units, count.value, fault, nxt
+
+
+def srtp_derive(master_key, master_salt):
+    """ferhip_srtp_derive (host): the session keys at key derivation rate 0 -> (k_e [16], k_a [20], k_s [14])"""
+    lib = load_library()
+    k, s, out = np.frombuffer(bytes(master_key), np.uint8), np.frombuffer(bytes(master_salt), np.uint8), np.zeros(50, np.uint8)
+    if k.size != 16 or s.size != 14:
+        raise FerHipError("srtp_derive: a master key of 16 and a master salt of 14 bytes")
+    _chk(lib.ferhip_srtp_derive(k.ctypes.data, s.ctypes.data, out.ctypes.data), "ferhip_srtp_derive")
+    out = out.tobytes()
+    return out[:16], out[16:36], out[36:]
+
+
+def srtp_keys(masters):
+    """[(master_key, master_salt) or None] -> entries of dtype SRTP_KEY (None: the stream has no key)"""
+    keys = np.zeros(len(masters), SRTP_KEY)
+    for s, m in enumerate(masters):
+        if m is not None:
+            keys[s]["master_key"], keys[s]["master_salt"], keys[s]["set"] = np.frombuffer(bytes(m[0]), np.uint8), np.frombuffer(bytes(m[1]), np.uint8), 1
+    return keys
+
+
+def srtp_blocks_raw(op, masters, states, base, pkts, misalign=0, cap=None, fill=0xA5):
+    """ferhip_srtp_blocks: the packets in `base` (bytes or a uint8 array) by the table `pkts` (rows of dtype RTP_PKT) through
+    the SRTP kernels.  masters: [(master_key, master_salt) or None] per stream, or entries of dtype SRTP_KEY; states:
+    [(roc, s_l, set)] per stream -> (return code, out [cap] pre-filled with `fill`, table [npkts + 1] of dtype RTP_PKT,
+    status [npkts], the states afterwards as a list of tuples).  cap None = room for everything."""
+    lib = load_library()
+    b = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+    rows = np.ascontiguousarray(pkts, RTP_PKT)
+    keys = masters if isinstance(masters, np.ndarray) else srtp_keys(masters)
+    n = len(keys)
+    st = np.zeros(n, SRTP_INDEX)
+    for s, (roc, s_l, sett) in enumerate(states):
+        st[s] = (roc, s_l, sett)
+    if cap is None:
+        cap = int(sum((int(r["bytes"]) + 10 + 15) & ~15 for r in rows)) + 16
+    out = np.full(max(int(cap), 1), fill, np.uint8)
+    table = np.full((rows.size + 1) * RTP_PKT.itemsize, fill, np.uint8).view(RTP_PKT)
+    status = np.full(max(rows.size, 1), -9, np.int32)
+    st_out = np.zeros(n, SRTP_INDEX)
+    rc = lib.ferhip_srtp_blocks(int(op), keys.ctypes.data, st.ctypes.data, n, b.ctypes.data if b.size else None, b.size,
+                                rows.ctypes.data if rows.size else None, rows.size, int(misalign), out.ctypes.data, int(cap), table.ctypes.data,
+                                status.ctypes.data, st_out.ctypes.data)
+    return rc, out, table, status[: rows.size], [(int(x["roc"]), int(x["s_l"]), int(x["set"])) for x in st_out]
+
+
+class Srtp:
+    """An SRTP session for nstreams streams on the current device (ferhip_srtp_*): session keys and packet index state in
+    device memory.  protect() runs on an encoder context's stream behind its pack_rtp_device(), unprotect() on a
+    LiveDecoder's stream in front of its decode_rtp(base_on_device=True)."""
+
+    def __init__(self, nstreams):
+        self.lib = load_library()
+        self.S = nstreams
+        self.h = C.c_void_p()
+        _chk(self.lib.ferhip_srtp_create(C.byref(self.h), int(nstreams)), "ferhip_srtp_create")
+
+    def set_key(self, s, master_key, master_salt):
+        k, t = np.frombuffer(bytes(master_key), np.uint8), np.frombuffer(bytes(master_salt), np.uint8)
+        if k.size != 16 or t.size != 14:
+            raise FerHipError("Srtp.set_key: a master key of 16 and a master salt of 14 bytes")
+        _chk(self.lib.ferhip_srtp_set_key(self.h, int(s), k.ctypes.data, t.ctypes.data), "ferhip_srtp_set_key")
+
+    def get_index(self, s):
+        """-> (roc, s_l, set); waits for the device"""
+        roc, s_l, sett = C.c_uint32(), C.c_uint32(), C.c_int()
+        _chk(self.lib.ferhip_srtp_get_index(self.h, int(s), C.byref(roc), C.byref(s_l), C.byref(sett)), "ferhip_srtp_get_index")
+        return roc.value, s_l.value, sett.value
+
+    def set_index(self, s, roc, s_l, sett=1):
+        _chk(self.lib.ferhip_srtp_set_index(self.h, int(s), int(roc), int(s_l), int(sett)), "ferhip_srtp_set_index")
+
+    def protect_raw(self, enc, src_ptr, pkts, npkts, dst_ptr, cap, out_pkts_ptr):
+        """ferhip_srtp_protect (pkts: rows of dtype RTP_PKT in host memory) or ferhip_srtp_protect_dev (pkts: an int, the
+        table's device address) -> the return code; asynchronous on enc's stream"""
+        vp = C.c_void_p
+        if isinstance(pkts, (int, np.integer)) or pkts is None:
+            return self.lib.ferhip_srtp_protect_dev(self.h, enc.ctx, vp(src_ptr), vp(pkts), int(npkts), vp(dst_ptr), int(cap), vp(out_pkts_ptr))
+        rows = np.ascontiguousarray(pkts, RTP_PKT)
+        return self.lib.ferhip_srtp_protect(self.h, enc.ctx, vp(src_ptr), rows.ctypes.data if rows.size else None, int(npkts), vp(dst_ptr),
+                                            int(cap), vp(out_pkts_ptr))
+
+    def protect(self, enc, src_ptr, pkts, npkts, dst_ptr, cap, out_pkts_ptr):
+        _chk(self.protect_raw(enc, src_ptr, pkts, npkts, dst_ptr, cap, out_pkts_ptr), "ferhip_srtp_protect")
+
+    def unprotect_raw(self, dec, base, pkts, dst_ptr, cap, base_on_device=False):
+        """ferhip_srtp_unprotect: base = bytes / a uint8 array (host) or a device address -> (return code, table
+        [npkts + 1] of dtype RTP_PKT, status [npkts])"""
+        rows = np.ascontiguousarray(pkts, RTP_PKT)
+        if base_on_device:
+            keep, ptr = None, int(base) if base else None
+        else:
+            keep = base if isinstance(base, np.ndarray) else np.frombuffer(bytes(base), np.uint8)
+            ptr = keep.ctypes.data if keep.size else None
+        table = np.zeros(rows.size + 1, RTP_PKT)
+        status = np.full(max(rows.size, 1), -9, np.int32)
+        rc = self.lib.ferhip_srtp_unprotect(self.h, dec.h, C.c_void_p(ptr), int(bool(base_on_device)), rows.ctypes.data if rows.size else None,
+                                            rows.size, C.c_void_p(dst_ptr), int(cap), table.ctypes.data, status.ctypes.data)
+        return rc, table, status[: rows.size]
+
+    def unprotect(self, dec, base, pkts, dst_ptr, cap, base_on_device=False):
+        rc, table, status = self.unprotect_raw(dec, base, pkts, dst_ptr, cap, base_on_device)
+        _chk(rc, "ferhip_srtp_unprotect")
+        return table, status
+
+    def close(self):
+        if self.h:
+            self.lib.ferhip_srtp_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def split_nal_blocks_raw(ranges, misalign=0, cap=None, units_cap=None, fill=0xA5):

@@ -906,6 +906,93 @@ int ferhip_unrtp_blocks(const uint8_t *base, size_t base_bytes, const ferhip_rtp
                         const int32_t *seq_expect /* [nstreams], -1 = none */, uint8_t *out, size_t cap, ferhip_nal_unit *units,
                         size_t units_cap, size_t *nunits, int32_t *fault /* [nstreams] */, int32_t *seq_next /* [nstreams] */);
 
+/* ---- SRTP on the device: RTP packets protected on the way out, checked and decrypted on the way into the decoder ----
+ * The profile is SRTP (RFC 3711) with its default transforms: AES-128 in counter mode, HMAC-SHA1 with an 80-bit tag, no MKI,
+ * key derivation rate 0.  Not provided: a replay list, SRTCP, an MKI, the other cipher suites, a key derivation rate other
+ * than 0.  AES(k, x) is the AES-128 encryption of the 16-byte block x (FIPS-197), HMAC-SHA1 that of RFC 2104 over SHA-1.
+ * Session: ferhip_srtp holds, for S streams, the session keys and the packet index state (roc: u32, s_l: u16, set: 0 / 1) in
+ * device memory, on the device that was current at ferhip_srtp_create.  The stream in the third column of a packet table
+ * selects the row of the session.
+ * Keys: ferhip_srtp_set_key(h, s, master_key[16], master_salt[14]) derives on the host, with r = 0: x_label = the 14-byte
+ * salt with `label` XORed into byte 7; the session key material of a label is the first bytes of the keystream
+ * AES(master_key, x_label || 00 00), AES(master_key, x_label || 00 01), ...; label 0 gives k_e (16 bytes), label 1 k_a (20),
+ * label 2 k_s (14).  ferhip_srtp_derive writes k_e | k_a | k_s into out[50].  The call uploads the 176 bytes of k_e's
+ * expanded round keys, k_s, and the two HMAC midstates (the SHA-1 state after the block k_a ^ 36 36 .. and after the block
+ * k_a ^ 5c 5c ..), and sets roc = 0, s_l = 0, set = 0.  It waits for the device: a call in flight keeps its key.
+ * Packet: a row (offset, bytes = L, stream) of a ferhip_rtp_pkt table names a packet at base + offset, at any alignment.
+ * Header rule: step 1 of the RTP input definition above without its padding clause -- L >= 12 and b0 >> 6 == 2, else
+ * malformed; hl = 12 + 4 CC; with X another 4 + 4 * (the u16 at hl + 2), which must lie within the packet; hl <= L, else
+ * malformed.  The P bit is not examined: padding is payload and is encrypted with it.  A payload of more than 2^20 bytes
+ * (65536 keystream blocks) is malformed too.
+ * Index: seq = the u16 at byte 2, ssrc = the u32 at byte 8, big-endian.  If the stream's state has set == 0, then for this
+ * call s_l is the seq of the stream's first well-formed row in table order (on the way in: well-formed without its tag,
+ * authentic or not).  v is the estimate of RFC 3711 section 3.3.1 against the state the call started with:
+ *   s_l < 32768:   v = roc - 1 when seq - s_l > 32768, else roc;
+ *   otherwise:     v = roc + 1 when s_l - 32768 > seq, else roc;    all modulo 2^32, and i = v << 16 | seq (48 bits).
+ * Every row of a call is estimated against the same starting state, whatever its place in the table; that is exact while a
+ * stream has fewer than 32768 packets in one call.
+ * Cipher: IV = k_s || 00 00 with ssrc XORed big-endian into bytes 4..7 and the 48-bit i into bytes 8..13.  Keystream block
+ * b = AES(k_e, IV + b), the sum in the last two bytes (b < 65536).  Payload byte p, at packet byte hl + p, is XORed with
+ * keystream byte p (byte p % 16 of block p / 16); the header's hl bytes are copied unchanged.
+ * Tag: the first 10 bytes of HMAC-SHA1(k_a, packet[0, L) with the payload encrypted || v as 4 big-endian bytes), appended:
+ * an SRTP packet has L + 10 bytes.
+ * ferhip_srtp_protect(h, c, d_src, src_pkts, npkts, d_dst, cap, d_out_pkts): device to device, asynchronous on the stream of
+ * encoder context c -- the one whose ferhip_pack_rtp wrote d_src; it waits for nothing except buffers that have to grow and
+ * the table copy of the fourth call before it (src_pkts is host memory, read before the call returns).
+ * ferhip_srtp_protect_dev is the same call with the table in device memory (aligned to 8), where ferhip_pack_rtp wrote it:
+ * that table never comes back to the host.  There a row whose stream is >= S or has no key cannot be refused: it is
+ * malformed.  Output row k = (offset: the sum over the rows in front of it of (bytes_j + 10) rounded up to 16 -- of 0 for a
+ * malformed row --, bytes: L + 10, the same stream); a malformed row has bytes 0 and takes no slot.  Row npkts = (total
+ * bytes, packets written, 0).  Overflow is ferhip_pack_rtp's rule, per packet: the table is always true, a packet is
+ * written only if it ends within cap (offset + bytes <= cap), and no byte at or beyond cap and no byte between a packet's
+ * end and the next multiple of 16 is touched.
+ * ferhip_srtp_unprotect(h, d, base, base_on_device, pkts, npkts, d_dst, cap, h_out_pkts, h_status): on the stream of live
+ * decoder d; it returns after one host synchronisation with the table and the status in host memory.  status[k]: 0
+ * authentic, 1 the tag differs, 2 malformed -- L < 10, the header rule on the L - 10 bytes without the tag, which is also
+ * L < hl + 10.  The tag is checked before anything is decrypted.  A row with status 0 is written as a plain RTP packet of
+ * L - 10 bytes under the slot rule above (sizes L - 10); every other row has bytes 0 and no slot.  base_on_device = 0: the
+ * range of base the rows span is copied up once; there is no host cipher.  The caller drops the rows with bytes 0 and hands
+ * the rest to the RTP input call above with d_dst as its base on the device; a dropped packet is then a gap, which that
+ * call isolates per stream.
+ * State update, both directions: the stream's state becomes (roc, s_l, set) = (i >> 16, i & 65535, 1) for the largest i over
+ * its rows of the call -- all well-formed rows on the way out, whether or not they fit cap, the status-0 rows on the way in --
+ * if that i is larger than the state's own index roc << 16 | s_l or the state has set == 0; else it stays.  The state stays
+ * on the device: consecutive calls continue it without the host.  ferhip_srtp_get_index reads it and ferhip_srtp_set_index
+ * writes it (s_l <= 65535, set 0 or 1); both wait for the device.
+ * FERHIP_E_ARG, before any HIP call: null pointers (a null table or base with npkts = 0 is fine), a null buffer with a cap,
+ * a d_dst not aligned to 16 or a device table not aligned to 8, pkts[k].stream >= S in a host table, s out of range, a
+ * session and a context or decoder on different devices; FERHIP_E_STATE: a host table that uses a stream whose key was
+ * never set.
+ * ferhip_srtp_blocks: known-answer surface, context-free and synchronous, host memory in and out, with the conventions of
+ * ferhip_unrtp_blocks: the packets lie in base[0, base_bytes) (copied to device memory `misalign` bytes behind a 16-byte
+ * boundary; a row that leaves it is FERHIP_E_ARG), and the bytes of out[0, cap) the kernels do not write keep the caller's
+ * values.  op = FERHIP_SRTP_PROTECT or FERHIP_SRTP_UNPROTECT, anything else FERHIP_E_ARG; keys[s].set = 0: stream s has no
+ * key; state_in / state_out [nstreams]: the index state before and after; out_pkts[npkts + 1]; status[npkts] (may be NULL
+ * for FERHIP_SRTP_PROTECT).  It runs the same kernels.
+ * Published vectors that hold (tests/test_srtp_model_host.py, tools/srtp_host_check.cpp): FIPS-197 appendix C.1, the
+ * keystream of RFC 3711 B.2, the derivation of RFC 3711 B.3, HMAC-SHA1 of RFC 2202 case 1; the model the device is compared
+ * with byte for byte is pinned to records made with the openssl command line (tests/golden/srtp_kat.json). */
+#define FERHIP_SRTP_PROTECT 0
+#define FERHIP_SRTP_UNPROTECT 1
+typedef struct ferhip_srtp ferhip_srtp;
+typedef struct { uint8_t master_key[16]; uint8_t master_salt[14]; uint8_t set, reserved; } ferhip_srtp_key; /* 32 bytes */
+typedef struct { uint32_t roc; uint16_t s_l, set; } ferhip_srtp_index;                                       /* 8 bytes */
+int ferhip_srtp_create(ferhip_srtp **out, int nstreams /* S <= 65535 */);
+void ferhip_srtp_destroy(ferhip_srtp *h);
+int ferhip_srtp_set_key(ferhip_srtp *h, int s, const uint8_t *master_key /* [16] */, const uint8_t *master_salt /* [14] */);
+int ferhip_srtp_derive(const uint8_t *master_key, const uint8_t *master_salt, uint8_t *out /* [50] */);
+int ferhip_srtp_get_index(ferhip_srtp *h, int s, uint32_t *roc, uint32_t *s_l, int *set);
+int ferhip_srtp_set_index(ferhip_srtp *h, int s, uint32_t roc, uint32_t s_l, int set);
+int ferhip_srtp_protect(ferhip_srtp *h, ferhip_ctx *c, const void *d_src, const ferhip_rtp_pkt *src_pkts /* host */, size_t npkts,
+                        void *d_dst, size_t cap, ferhip_rtp_pkt *d_out_pkts /* [npkts + 1] */);
+int ferhip_srtp_protect_dev(ferhip_srtp *h, ferhip_ctx *c, const void *d_src, const ferhip_rtp_pkt *d_src_pkts, size_t npkts,
+                            void *d_dst, size_t cap, ferhip_rtp_pkt *d_out_pkts /* [npkts + 1] */);
+int ferhip_srtp_unprotect(ferhip_srtp *h, ferhip_decs *d, const void *base, int base_on_device, const ferhip_rtp_pkt *pkts /* host */,
+                          size_t npkts, void *d_dst, size_t cap, ferhip_rtp_pkt *h_out_pkts /* [npkts + 1] */, int32_t *h_status /* [npkts] */);
+int ferhip_srtp_blocks(int op, const ferhip_srtp_key *keys, const ferhip_srtp_index *state_in, int nstreams, const uint8_t *base,
+                       size_t base_bytes, const ferhip_rtp_pkt *pkts, size_t npkts, int misalign, uint8_t *out, size_t cap,
+                       ferhip_rtp_pkt *out_pkts /* [npkts + 1] */, int32_t *status /* [npkts] */, ferhip_srtp_index *state_out);
+
 /* ---- Transport stream input: the live decoder takes 188-byte packets where a receiver has them ----
  * runs[k] (host) names runs[k].bytes bytes at base + runs[k].offset: a whole number of 188-byte packets at any alignment,
  * for stream runs[k].stream.  Runs of one stream are taken in table order, streams may interleave, and two runs may name the
