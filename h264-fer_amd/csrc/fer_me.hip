@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include "fer_internal.h"
 #include "fer_mvpred.h"
+#include "fer_chain_idx.h"
 
 #define INF_M 1000000000
 
@@ -1517,8 +1518,9 @@ __device__ __forceinline__ void take_best(int best, int bestxy, int &bmin, int &
 // The searches that depend on the predictor were run beforehand for a GUESSED predictor (k_me_spec): the common step
 // of the chain is "compute the true predictor, find that its integer part is the guessed one, price the stored
 // candidate lists" -- a few hundred instructions.  After a wrong guess the chain searches itself (stage 1, then stages
-// 2 and 3, in the same wavefront).  One wavefront per row: with thousands of rows in flight the launch is bound by the
-// instructions it issues, not by the latency of a row.
+// 2 and 3, in the same wavefront).  One wavefront per row, six rows per SIMD: what a step costs is mostly what its SIMD's
+// six wavefronts issue between them; the round trip for the stored lists, which come from HBM, is taken off the step by
+// asking for them one step ahead (ResStage, fer_chain_idx.h).
 // Everything after the vector of the partition is known (merge, mvd, final prediction, snapping, and the
 // reconstruction of P_Skip macroblocks) is not on any other partition's dependency chain and lives in k_p_resid
 // (fer_resid.hip).
@@ -1568,6 +1570,24 @@ __device__ __forceinline__ void res_prefetch(const FerDev &d, int s, int gx, int
 // flag, fence or store ordering is involved; loads and stores are agent scope (coherent across
 // the XCDs' L2s).
 #define CH_SKIP 0x80000000u
+// (native vectors, not int4 / int2: each is ONE value to the compiler, loaded into a register tuple that it keeps together
+// from step to step; three separate ints are copied out of the tuple of their load at once, which is a wait for it)
+typedef int res_i2 __attribute__((ext_vector_type(2)));
+typedef int res_i3 __attribute__((ext_vector_type(3)));
+typedef int res_i4 __attribute__((ext_vector_type(4)));
+struct ResStage {  // what the guessed search left for one step of the chain, as one lane holds it (fer_chain_idx.h)
+    res_i4 sh;      // spec_hdr
+    res_i2 e1, e2;  // the lane's entry of spec_l1, spec_l2
+    res_i3 c3;      // the lane's stage-3 survivor: x, y, SAD
+    int n3;         // ... and their number
+};
+// a register move the compiler cannot fold into its source: the source's live range ends here (k_me_resolve's rotation)
+__device__ __forceinline__ int res_mov(int x)
+{
+    int y;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
+    return y;
+}
 struct ResNbr {      // neighbour vectors of one partition (packed), v* = available
     bool vA, vB, vC, vD, vC16;
     int A, B, C, D, C16;
@@ -2036,8 +2056,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPEC_WAVES,
 #define RES_WAVES 6  // wavefronts per SIMD the chain kernel is compiled for
 #endif
 // ONE WAVEFRONT PER ROW.  With the guessed lists in place a step of the chain is a few hundred instructions, and with
-// thousands of rows in flight the launch is bound by how many instructions it issues, not by the latency of a row: a
-// second wavefront per row (which the chain's own search used to be split over) would only repeat them.
+// six rows per SIMD in flight the launch is bound mostly by how many instructions it issues: a second wavefront per row
+// (which the chain's own search used to be split over) would only repeat them.
 template <int WIN>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, RES_WAVES))) void k_me_resolve(FerDev d)
 {
@@ -2100,6 +2120,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
     const int4 *row_hdr = d.spec_hdr + pidx0;
     const int2 *row_l1 = d.spec_l1 + pidx0 * 17, *row_l2 = d.spec_l2 + pidx0 * 33;
     const int *row_st3 = d.st3 + pidx0 * 33 * 3, *row_st3n = d.st3n + pidx0;
+    // What the guessed search left behind for a step -- the header, the lane's entry of either list and of the stage-3
+    // survivors -- is a function of (s, gy, gx) alone and comes from HBM: it is requested RES_AHEAD steps before it is
+    // priced (addressed relative to the row's first partition: 32-bit offsets per step, the 64-bit bases once per row;
+    // the step asked for is clamped to the row, fer_chain_idx.h).  (probe bit 512: list reads served from cache)
+    auto request = [&](int g, int l, ResStage &o) {
+        o.sh = 0;
+        o.e1 = o.e2 = 0;
+        o.c3 = 0;
+        o.n3 = 0;
+        if (spec) {
+            const ChainIdx ix = chain_idx(FER_DBGF(d, 512) ? 0u : chain_rel_part(g), l);
+            // 32-bit byte offsets from the scalar row bases (a row's share of any array is far below 4 GB).  The wave-uniform
+            // words (header, n3) are loaded per lane on purpose (l >> 6 is 0, which the compiler cannot know): a load
+            // it sees as uniform is moved to scalar registers where it is ISSUED, and that is a wait for it a step early.
+            const unsigned up = ix.rp + ((unsigned)l >> 6);
+            o.sh = *(const res_i4 *)((const char *)row_hdr + up * 16u);
+            o.e1 = *(const res_i2 *)((const char *)row_l1 + ix.l1 * 8u);
+            o.e2 = *(const res_i2 *)((const char *)row_l2 + ix.l2 * 8u);
+            if (!d.basic) {
+                __builtin_memcpy(&o.c3, (const char *)row_st3 + ix.st3 * 4u, 12);  // (one 12-byte load, 4-byte aligned)
+                o.n3 = *(const int *)((const char *)row_st3n + up * 4u);
+            }
+        }
+    };
+    ResStage ahead[RES_AHEAD];  // ahead[j] = the operands of step gx + j at the top of step gx: the rotation starts afresh with every row
+    // A wrong guess (about one step in a hundred) runs a search that needs every register: what was requested is not kept
+    // across it but asked for again behind it.
+    auto again = [&](int g0, int l) {
+#pragma unroll
+        for (int j = 0; j < RES_AHEAD; j++) request(chain_ahead_step(g0, j + 1, gw), l, ahead[j]);
+    };
+    {
+        int l0 = lane;  // (opaque, as in the loop below)
+        asm volatile("" : "+v"(l0));
+#pragma unroll
+        for (int j = 0; j < RES_AHEAD; j++) request(chain_ahead_step(0, j, gw), l0, ahead[j]);
+    }
     for (int gx = 0; gx < gw; gx++) {
         if (probe) tmark = wall_clock64();
         const int part = (gy & 1) * 2 + (gx & 1);
@@ -2109,24 +2166,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
         // are hoisted out of the loop and spilled
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        // what the guessed search left behind: the lane's entry of either list and of the stage-3 survivors (addressed
-        // relative to the row's first partition: 32-bit offsets per step, the 64-bit bases once per row)
-        int4 sh = make_int4(0, 0, 0, 0);
-        int2 e1 = make_int2(0, 0), e2 = make_int2(0, 0);
-        int c3x = 0, c3y = 0, c3s = 0, n3 = 0;
-        if (spec) {
-            const unsigned rp = (FER_DBGF(d, 512) ? 0u : (unsigned)((gx >> 1) * 4 + (gx & 1)));  // (probe: list reads served from cache)
-            sh = row_hdr[rp];
-            e1 = row_l1[rp * 17u + (unsigned)min(ln, 16)];
-            e2 = row_l2[rp * 33u + (unsigned)min(ln, 32)];
-            if (!d.basic) {
-                const int *c3 = row_st3 + (rp * 33u + (unsigned)min(ln, 32)) * 3u;
-                c3x = c3[0];
-                c3y = c3[1];
-                c3s = c3[2];
-                n3 = row_st3n[rp];
-            }
-        }
         // A window over the row above: every RES_WIN steps ONE 64-lane load fetches the words of the partitions gx - 1 ...
         // gx + 62 of that row; the four a step needs come out of it with two ds_bpermute.  A word that was not valid when
         // the window was loaded (the row above was not that far ahead) is polled for.  (Agent-scope loads cross the
@@ -2142,7 +2181,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
         // neighbours in the row above: lane 0 = B, 1 = C, 2 = D, 3 = C of the 16x16 (P_Skip) predictor -- the partitions
         // gx, gx + 1, gx - 1, gx + 2 of row gy - 1; which of them exist is wave-uniform (nbr_avail)
         ResNbr N;
-        nbr_avail(gx, gy, gw, N.vB, N.vC, N.vD, N.vC16);
+        // (the row is made opaque per iteration like the lane: what depends on gy alone is otherwise kept in vector
+        // registers across the row, spilled, and reloaded in the middle of the step -- a wait for everything in flight)
+        int gyo = gy;
+        asm volatile("" : "+s"(gyo));
+        nbr_avail(gx, gyo, gw, N.vB, N.vC, N.vD, N.vC16);
         // (bit tricks instead of per-lane selects of wave-uniform booleans, which compile to exec-mask branches)
         const unsigned vmask = (N.vB ? 1u : 0u) | (N.vC ? 2u : 0u) | (N.vD ? 4u : 0u) | (N.vC16 ? 8u : 0u);
         const int noff = (int)((0x3021u >> ((ln & 3) * 4)) & 15u) - 1;  // 0, +1, -1, +2 for lanes 0..3
@@ -2164,6 +2207,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
             __builtin_amdgcn_s_sleep(2);
         }
         PR_MARK(0)
+        // The rotation: this step prices what an earlier step asked for and (below, behind the P_Skip verdict) asks for
+        // step gx + RES_AHEAD.  Vector loads return in order, so the request stands BEHIND the wait for the row above (in
+        // front of it the window or a poll, younger, would wait for the lists as well) and in front of the pricing: the
+        // lists have the rest of this step and the top of the next one to arrive.  The staged registers are MOVED out here
+        // (res_mov, not a plain copy): their live range ends at this point, so the request loads into the very same
+        // registers and no copy of a value still in flight is left at the loop's back edge, where it would be a wait.
+        // (The header is wave-uniform: scalar from here on, so that the tests on it stay scalar branches.)
+        const int4 sh = make_int4(__builtin_amdgcn_readfirstlane(ahead[0].sh.x), __builtin_amdgcn_readfirstlane(ahead[0].sh.y),
+                                  __builtin_amdgcn_readfirstlane(ahead[0].sh.z), __builtin_amdgcn_readfirstlane(ahead[0].sh.w));
+        const int2 e1 = make_int2(res_mov(ahead[0].e1.x), res_mov(ahead[0].e1.y)), e2 = make_int2(res_mov(ahead[0].e2.x), res_mov(ahead[0].e2.y));
+        const int c3x = res_mov(ahead[0].c3.x), c3y = res_mov(ahead[0].c3.y), c3s = res_mov(ahead[0].c3.z), n3 = res_mov(ahead[0].n3);
+#pragma unroll
+        for (int j = 0; j + 1 < RES_AHEAD; j++) {
+            ResStage &a = ahead[j];
+            const ResStage &b = ahead[j + 1];
+            a.sh = res_i4{res_mov(b.sh.x), res_mov(b.sh.y), res_mov(b.sh.z), res_mov(b.sh.w)};
+            a.e1 = res_i2{res_mov(b.e1.x), res_mov(b.e1.y)};
+            a.e2 = res_i2{res_mov(b.e2.x), res_mov(b.e2.y)};
+            a.c3 = res_i3{res_mov(b.c3.x), res_mov(b.c3.y), res_mov(b.c3.z)};
+            a.n3 = res_mov(b.n3);
+        }
         N.vA = gx > 0;
         N.A = prevw;
         N.B = lane_bcast((int)wl, 0);
@@ -2174,21 +2238,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
             skip = (lane_bcast((int)wh, 0) & CH_SKIP) != 0;
             if (skip) prevw = N.B;
         }
-        if (part == 0 || !skip) {
-            bool sk = false;
-            int r = 0;
-            if (part == 0) {  // ---- P_Skip candidate
-                int smx, smy;
-                pskip_vector(d, mb, mbx, N, smx, smy);
-                r = pack_xy(smx, smy);
-                st_skq++;
-                if ((((sh.y >> 17) & 1) && sh.z == r) || FER_DBGF(d, 512)) {
-                    sk = sh.w != 0 && !FER_DBGF(d, 512);
-                    st_skh++;
-                } else {
-                    sk = pskip_test(d, s, mbx, mby, ln, smx, smy);
-                }
+        bool sk = false;
+        int r = 0;
+        if (part == 0) {  // ---- P_Skip candidate
+            int smx, smy;
+            pskip_vector(d, mb, mbx, N, smx, smy);
+            r = pack_xy(smx, smy);
+            st_skq++;
+            if ((((sh.y >> 17) & 1) && sh.z == r) || FER_DBGF(d, 512)) {
+                sk = sh.w != 0 && !FER_DBGF(d, 512);
+                st_skh++;
+            } else {
+                sk = pskip_test(d, s, mbx, mby, ln, smx, smy);
             }
+        }
+        // the one request of the step, on every path (a partition of a skipped macroblock prices nothing but the rotation
+        // goes on); the P_Skip test of a wrong guess, one macroblock in a hundred, is behind us
+        request(chain_ahead_step(gx, RES_AHEAD, gw), ln, ahead[RES_AHEAD - 1]);
+        if (part == 0 || !skip) {
             if (!sk) {
                 int mvpx, mvpy;
                 predict_nbr(N.vA, N.A, N.vB, N.B, N.vC, N.C, N.vD, N.D, mvpx, mvpy);
@@ -2243,6 +2310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RES_WAVES, R
                         bmin = k3 >> 6;
                         r = xy3;
                     }
+                    again(gx, ln);
                 }
             }
             const unsigned long long w = (unsigned)r | ((unsigned long long)(serial | (sk ? CH_SKIP : 0u)) << 32);
