@@ -656,7 +656,18 @@ int ferhip_inter_encoding(ferhip_ctx *c);
 #define FERHIP_BUF_MBSIZE 18   /* int32  [S][nmb][2] coded_mb_size (F/rbsp_encoding.cpp:330) of the Intra16x16 and of the Intra4x4 alternative of every
                                  macroblock of the last I picture */
 #define FERHIP_BUF_ST2 16     /* int32  [S][nmb][4][384][2] the candidates (position relative to the block, feature distance); a crowded
-                                 partition (count > 384) holds its summary instead: [40] = (last step, distance bound), [41] = (zeros, 0) */
+                                 partition (count > 384) holds its summary instead (k_me_walk, read by resolve_crowded):
+                                   [0 .. 32]   the first candidates of distance 0 in arrival order, (position, 0)
+                                   [40]        (J = the step the walk stopped in, the smallest positive distance: a lower bound)
+                                   [41]        (zeros = how many of [0 .. 32] are set, np2 | nbig << 16 | fallback << 30):
+                                               np2 = listed candidates in [64 .. 64 + np2), at most 320; nbig = big bucket
+                                               slices (more than 1024 records) described in [42 .. 44], at most 3; fallback =
+                                               more than 3 big slices, or one with more than 512 records outside its class, or
+                                               more than 320 candidates to list: no class is used then, and with nbig = 0 the
+                                               chain walks the buckets again
+                                   [42 .. 44]  (bucket, feature distance of its class; 0x7fffffff = no member can be a candidate)
+                                   [46]        (the smallest of the class distances, 0)
+                                   [64 ..]     listed candidates: (position, D | step << 20 | side << 28) */
 /* The lists the four motion kernels hand each other, as they stand after ferhip_inter_encoding (list-level parity
  * tests; the layouts below are ABI for tests).  A "packed vector" is one int32: (x & 0xffff) | (y << 16), x and y
  * signed 16-bit, in quarter samples for vectors and in whole samples for the centre of SPEC_HDR.  SPEC_HDR, SPEC_L1 and

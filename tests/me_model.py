@@ -16,6 +16,9 @@ arrival order, and the only place where a later arrival displaces an equal earli
 """
 import numpy as np
 
+# FER_ST2_CAP, FER_BIGS, FER_OUTL, FER_P2_CAP, FER_BIG_SLICE of fer_dev.h: what the crowded summary depends on
+ST2_CAP, BIGS, OUTL, P2_CAP, BIG_SLICE = 384, 3, 512, 320, 1024
+
 
 def box_sums(cur, sx, sy):
     """suma[5] of the 8x8 source block at (sx, sy), F/moestimation.cpp:440-451"""
@@ -37,10 +40,18 @@ class WalkModel:
         self.a, self.tx, self.ty = a[order], tx[order], ty[order]
         self.q = [k[order] for k in self.k[1:]]
         self.start = np.searchsorted(self.a, np.arange(16385))
+        self._walks = {}  # walk_arrays per partition, kept for the life of the model: small at QCIF, not meant for large pictures
 
     def walk_arrays(self, su, sx, sy):
         """-> (tmpx, tmpy, D) of the candidates in arrival order up to the stop, the stop step, and the records of
-        every slice read (step, side, first index, count, indices passing the filter) up to the stop step."""
+        every slice read (step, side, first index, count, indices passing the filter) up to the stop step.  Computed
+        once per argument set; callers leave the result unchanged."""
+        key = (tuple(su), sx, sy)
+        if key not in self._walks:
+            self._walks[key] = self._walk_arrays(su, sx, sy)
+        return self._walks[key]
+
+    def _walk_arrays(self, su, sx, sy):
         s0 = su[0]
         px, py, pd, slices = [], [], [], []
         count, jend = 0, 180
@@ -71,6 +82,7 @@ class WalkModel:
         """-> list of (rel, D) in arrival order up to the stop, the stop step, and the records of every slice read
         (step, side, first index, count, indices passing the filter) up to the stop step's group end."""
         px, py, pd, jend, slices = self.walk_arrays(su, sx, sy)
+        slices = list(slices)
         out = [((int(x) << 16) | (int(y) & 0xffff), int(d)) for x, y, d in zip(px, py, pd)]
         s0 = su[0]
         for j in range(jend + 1, min(jend - jend % 16 + 16, 181)):  # the rest of the group: in its batches, not read
@@ -199,6 +211,121 @@ class MeModel:
                     refuse64=bool(srt.size >= 33 and (m <= srt[32]).sum() > 64),
                     tie_end=bool(srt.size >= 34 and srt[32] == srt[33]))
 
+    def stage2_routes(self, p, genx, geny, cand=None):
+        """Sufficient conditions, independent of which lane holds which candidate, for the routes of select_topk_ex
+        under stage2_list at the centre (genx, geny).  The selection runs only on a partition that is not crowded, so
+        every predicate also requires 1 <= n <= ST2_CAP candidates.
+          general_t0:  every candidate's metric is >= 2^21: every lane minimum is, so T0 = 1 << 21 (or, with fewer
+                       than `need` lanes in use, 2^31 - 1) and the general route is entered through T0, not through ties
+          straddle:    at least 33 candidates below 2^21, at least one at or above it, and on each side one within one
+                       weight step (its own D) of 2^21: the fast route's guard and its `hi` bound from below
+          mixed_t0:    at most 64 candidates (each alone in its lane, so T0 is known), some of them below 2^21, and
+                       the need-th smallest at or above it: T0 = 1 << 21 with metrics on both sides of it
+        also max_metric, n, below = how many metrics are < 2^21, and nth = the need-th smallest metric (need = min(33,
+        n)), which IS T0 when n <= 64, every candidate then being alone in its lane."""
+        px, py, pd = cand if cand is not None else self.stage2_candidates(p)
+        m = (np.abs(px - genx) + np.abs(py - geny) + 4) * pd
+        n, lim = int(m.size), 1 << 21
+        out = dict(general_t0=False, straddle=False, mixed_t0=False, max_metric=int(m.max()) if n else 0, n=n, below=int((m < lim).sum()), nth=0)
+        if 1 <= n <= ST2_CAP:
+            lo, hi = m < lim, m >= lim
+            out["nth"] = int(np.sort(m)[min(33, n) - 1])
+            out["general_t0"] = bool(hi.all())
+            out["straddle"] = bool(lo.sum() >= 33 and hi.any() and (lo & (m + pd >= lim)).any() and (hi & (m - pd < lim)).any())
+            out["mixed_t0"] = bool(n <= 64 and lo.any() and out["nth"] >= lim)
+        return out
+
+    def crowded_summary(self, p):
+        """What k_me_walk writes into the summary of a crowded partition (more than ST2_CAP walk candidates), restated
+        from the model's buckets; None for a partition that is not crowded.  Only for pictures at most 280 samples wide:
+        the column-tile range bt_lo..bt_hi of k_me_walk is then the whole picture for every partition, and a "slice" is a
+        whole bucket of the sorted feature table.
+
+        With J the stop step, the buckets su[0] + dj, dj = -J..J, of more than BIG_SLICE positions are `raw_big`; the
+        device leaves bucket su[0] out of them when the ranges of its four other sums all contain the source's (the
+        bucket may hold distance 0 and is read whole), which gives `bigs`, in the device's order.  The three causes of
+        the fallback bit:
+          a  more than BIGS big buckets
+          b  (not a) a described big bucket with more than OUTL positions outside its class
+          c  (neither) more than P2_CAP listed candidates: everything with D > 0 in the other buckets of the steps
+             0..J (bucket su[0] once), and the outliers of the described big buckets that pass the walk's tests with a
+             distance other than 0 and the class's
+        The device takes the features of the bucket's MIDDLE record (sorted order) as its class; the modal class is the
+        most frequent (k1..k4).  Where the two differ the device's rule is not the modal one and the partition is
+        `undecided`; so is one with 33 or more candidates of distance 0, whose listing stops inside a batch.  An
+        undecided partition claims no cause and no value of slot 41.
+
+        This mirrors the KERNEL's rule (skip0, the order of the big buckets, outliers listed only for the buckets in front
+        of the one that sets b), not anything the reference computes: slot 41 is a device-side summary with no counterpart
+        there.  It tells which route a partition takes and pins the summary's layout; the independent check of what the
+        routes compute is the final vector, MVD and MBTYPE against the oracle."""
+        assert self.W <= 280, "a slice is a whole bucket only while the 280-diamond spans every column tile"
+        w, su = self.walkm, self.sums(p)
+        sx, sy = self.origin(p)
+        px, _, _, J, _ = w.walk_arrays(su, sx, sy)
+        if px.size <= ST2_CAP:
+            return None
+        s0 = su[0]
+
+        def bucket(dj):
+            a = s0 + dj
+            if a < 0 or a > 16383:
+                return None
+            lo, hi = int(w.start[a]), int(w.start[a + 1])
+            q = np.stack([x[lo:hi] for x in w.q], -1)  # [n][4]
+            ok = (np.abs(w.tx[lo:hi] - sx) + np.abs(w.ty[lo:hi] - sy) < 280) & (np.abs(q[:, 0] - su[1]) < 100) & (np.abs(q[:, 1] - su[2]) < 100)
+            D = abs(dj) + sum(np.abs(su[i + 1] - q[:, i]) + np.abs((s0 - su[i + 1]) - (a - q[:, i])) for i in range(4))
+            return q, ok, D
+
+        raw_big, bigs, skip0 = 0, [], False
+        for dj in range(-J, J + 1):
+            b = bucket(dj)
+            if b is None or len(b[0]) <= BIG_SLICE:
+                continue
+            raw_big += 1
+            if dj == 0 and all(b[0][:, i].min() <= su[i + 1] <= b[0][:, i].max() for i in range(4)):
+                continue
+            skip0 |= dj == 0
+            bigs.append(dj)
+        out = dict(J=J, raw_big=raw_big, bigs=bigs, nbig=min(len(bigs), BIGS), a=len(bigs) > BIGS, b=False, c=False, np2=None,
+                   classes=[], undecided=None)
+        listed = 0
+        for dj in bigs[:BIGS]:
+            q, ok, D = bucket(dj)
+            cls, cnt = np.unique(q, axis=0, return_counts=True)
+            mid = q[len(q) // 2]
+            nmid = int((q == mid).all(1).sum())
+            out["classes"].append((dj, tuple(int(v) for v in cls[np.argmax(cnt)]), len(q) - int(cnt.max())))
+            if out["a"] or out["b"]:  # the device reads no class any more
+                continue
+            if nmid != cnt.max():
+                out["undecided"] = "the middle record of bucket %d is not of its modal class" % (s0 + dj)
+                return out
+            if len(q) - nmid > OUTL:
+                out["b"] = True
+                continue
+            member = (q == mid).all(1)
+            DM = int(D[member][0])
+            listed += int((~member & ok & (D > 0) & (D != DM)).sum())
+        zero = 0
+        for j in range(J + 1):
+            for dj in ((0,) if j == 0 else (-j, j)):
+                b = bucket(dj)
+                if b is None or (len(b[0]) > BIG_SLICE and (j > 0 or skip0)):
+                    continue
+                listed += int((b[1] & (b[2] > 0)).sum())
+                if j == 0:
+                    zero = int((b[1] & (b[2] == 0)).sum())
+        out["zero"] = zero
+        if zero >= 33 and not (out["a"] or out["b"]):
+            out["undecided"] = "33 or more candidates of distance 0: the listing stops inside a batch"
+            return out
+        if zero < 33:
+            out["np2"] = listed
+            out["c"] = not (out["a"] or out["b"]) and listed > P2_CAP
+        out["fallback"] = out["a"] or out["b"] or out["c"]
+        return out
+
 
 # ---------------------------------------------------------------- the predictor of an 8x8 partition
 def _core(A, B, C):
@@ -270,6 +397,20 @@ def oracle_pair(fo, f0, f1, W, H, window, maxdiff, qp=12):
     o.encode_slice(1)
     rec = o.me_lists()
     out = rec0, rec, o.mb_type(), o.mv(), int(o.stats()[0])
+    o.close()
+    return out
+
+
+def oracle_pair_ref(fo, ref, f1, W, H, window, maxdiff, qp=12):
+    """oracle_pair with the reference picture given as it is (no I picture is coded): P picture f1 searched in `ref` with
+    recording -> (ref, lists, mb_type, mv, P_Skip count)"""
+    o = fo.Oracle(W, H, qp=qp, window=window, maxdiff=maxdiff)
+    o.set_dpb(ref)
+    o.fill_interpolated()
+    o.record_me()
+    o.set_frame(f1)
+    o.encode_slice(1)
+    out = ref, o.me_lists(), o.mb_type(), o.mv(), int(o.stats()[0])
     o.close()
     return out
 

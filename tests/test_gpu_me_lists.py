@@ -27,9 +27,11 @@ which lane holds which candidate) and must hold on at least one compared partiti
   tie at the list's end decided by arrival              every kind
   a speculation miss (guessed centre != mvp >> 2)       see MISS_KINDS
   a crowded partition (ST2N > 384) with lists           see CROWDED_KINDS
-Not shown to be reached (the model cannot decide them without the lane layout): T infinite in k_me_pre (fewer than 33
-lanes with a local candidate; possible only at the corners of the tiny pictures), T0 >= 2^21 and a metric >= 2^26 in
-select_topk_ex, the `fallback` bit of a crowded summary.
+Not reached by THIS content: T0 >= 2^21 in select_topk_ex and the `fallback` bit of a crowded summary; the pairs of
+route_content.py reach both, with predicates that need no lane layout (MeModel.stage2_routes, crowded_summary), and
+test_gpu_me_routes.py compares them.  A metric >= 2^26 is out of reach while the centre is at most 1715 samples from the
+block (test_route_content_host.py::test_metric_bounds; in larger pictures the guard stays live and unreached).  T infinite in k_me_pre (fewer than 33 lanes with a local candidate)
+stays unreached: no legal picture gives it, by the lane argument of test_gpu_me_pre_paths.py.
 """
 import numpy as np
 import pytest
@@ -47,7 +49,7 @@ CROWDED_KINDS = ["patch"]  # the crowded partitions of "letterbox" and "flat-hal
 
 READS = ("SUMA", "ST3", "ST3N", "V0", "SPEC_HDR", "SPEC_L1", "SPEC_L2", "MV", "MVD", "MBTYPE", "ST2N")
 SHAPES = dict(SUMA=(4, 5), ST3=(4, 33, 3), ST3N=(4,), V0=(4,), SPEC_HDR=(4, 4), SPEC_L1=(4, 17, 2), SPEC_L2=(4, 33, 2), MV=(4, 2),
-              MVD=(4, 2), MBTYPE=(), ST2N=(4,))
+              MVD=(4, 2), MBTYPE=(), ST2N=(4,), ST2=(4, CAP, 2))
 
 
 def frames_of(pkg, kind, W, H, seed=1234):
@@ -71,8 +73,10 @@ def frames_of(pkg, kind, W, H, seed=1234):
     return out
 
 
-def gpu_state(pkg, W, H, window, maxdiff, rec0s, f1s, speculate=True):
-    """one inter_encoding() over len(f1s) streams -> per stream a dict of the read-backs, partitions flattened"""
+def gpu_state(pkg, W, H, window, maxdiff, rec0s, f1s, speculate=True, extra=()):
+    """one inter_encoding() over len(f1s) streams -> per stream a dict of the read-backs (READS and `extra`), partitions
+    flattened"""
+    reads = READS + tuple(extra)
     S = len(f1s)
     g = pkg.FerHip(W, H, S, qp=12, window=window, maxdiff=maxdiff)
     if not speculate:
@@ -83,13 +87,13 @@ def gpu_state(pkg, W, H, window, maxdiff, rec0s, f1s, speculate=True):
         g.set_frames(np.stack(f1s))
         g.inter_encoding()
         assert g.status() == [0] * S
-        raw = {n: g.read(n).reshape((S, nmb) + SHAPES[n]) for n in READS}
+        raw = {n: g.read(n).reshape((S, nmb) + SHAPES[n]) for n in reads}
     finally:
         g.close()
     out = []
     for s in range(S):
-        st = {n: raw[n][s].astype(np.int64) for n in READS}
-        for n in READS:
+        st = {n: raw[n][s].astype(np.int64) for n in reads}
+        for n in reads:
             if n != "MBTYPE":
                 st[n] = st[n].reshape((nmb * 4,) + SHAPES[n][1:])
         out.append(st)

@@ -89,8 +89,6 @@ def walk_check(pkg, fo, kind, f0, f1, window):
     r.fill_interpolated()
     m = Model([r.kar(k, 0) for k in range(5)])
     r.close()
-    assert m.a.min() > 0, "a sum-0 position would put the stream on the mis-filed bucket layout"
-    cur = f1[: W * H].reshape(H, W)
     g = pkg.FerHip(W, H, 1, qp=12, window=window)
     g.set_reference(rec0[None])
     g.set_frames(f1[None])
@@ -99,7 +97,15 @@ def walk_check(pkg, fo, kind, f0, f1, window):
     n2 = g.read("ST2N")
     st2 = g.read("ST2").reshape(-1, CAP, 2)
     g.close()
-    mbw = W // 16
+    return walk_compare(kind, m, f1[: W * H].reshape(H, W), n2, st2)
+
+
+def walk_compare(kind, m, cur, n2, st2):
+    """the read-backs n2 = ST2N [partitions] and st2 = ST2 [partitions][CAP][2] of source luma `cur` (every column tile
+    in reach of every partition: at most 280 samples wide) against the walk model m of its reference"""
+    assert m.a.min() > 0, "a sum-0 position would put the stream on the mis-filed bucket layout"
+    assert cur.shape[1] <= 280
+    mbw = cur.shape[1] // 16
     seen_mid = seen_cap = 0
     for p in range(n2.size):
         mb, part = p // 4, p % 4
