@@ -29,9 +29,11 @@
 // (metric, arrival) -- solved without serial insertion (select_topk); the ballot-ordered insertion (wl_insert)
 // remains for the short serial tails.
 #include <stdlib.h>
+#include <type_traits>
 #include "fer_internal.h"
 #include "fer_mvpred.h"
 #include "fer_chain_idx.h"
+#include "fer_sel_thr.h"
 
 #define INF_M 1000000000
 
@@ -73,11 +75,12 @@ __device__ __forceinline__ void wl_insert(WList &L, int K, int lane, bool valid,
 // that is a selection problem.  The code below sits on the serial chain of k_me_resolve, where one
 // wavefront runs alone on its SIMD and every dependent instruction costs its full latency, so
 // it is built from few, wide steps:
-//   1. T0 = the need-th smallest per-lane minimum -- an upper bound of the need-th smallest
-//      candidate (binary search over the value with ballot counts: scalar work),
-//   2. the candidates <= T0 (typically 1.2-1.5 x need of them) are gathered in LDS, in no particular order,
+//   1. T0 = an upper bound of the need-th smallest candidate: the need-th smallest per-lane minimum rounded up to
+//      4 significant bits (fer_sel_thr.h; a search over the lanes' codes with ballot counts: scalar work),
+//   2. the candidates <= T0 (typically 1.2-1.6 x need of them) are gathered in LDS, in no particular order,
 //   3. their exact rank by (metric << 11 | arrival index) places the winners.
-// More than 64 survivors of step 2 or a T0 >= 2^21 take the binary-search route instead.
+// More than 64 survivors of step 2 repeat steps 1 and 2 with the exact need-th smallest lane minimum; more than 64 again,
+// or a T0 >= 2^21, take the binary-search route instead.
 // v[u] < 0 marks an invalid candidate; raw(u) is a cheap tag of the lane's candidate u that travels with it,
 // fin(tag) turns the tag of a winner into its packed vector (evaluated once per list slot).  sel = 256 ints of 16-byte aligned LDS owned by the wavefront.
 // sel is private to ONE wavefront: its LDS operations execute in program order, so ordering them needs no
@@ -101,12 +104,34 @@ __device__ __forceinline__ int lds_rank64(const unsigned *p, unsigned mine, int 
     return r;
 }
 
+// how many lanes hold the predicate, as a 32-bit scalar that is compared and selected on the scalar unit.  (The compiler
+// widens a compare of __popcll's result to 64 bits, whatever it is cast to, and a 64-bit compare is a VECTOR instruction
+// per step of the threshold searches: the count is taken where it cannot see through.)
+__device__ __forceinline__ int wave_count(bool p)
+{
+    int n;
+    asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(__builtin_amdgcn_ballot_w64(p)) : "scc");
+    return n;
+}
+// -DFER_STATS: per call site (stat = its three slots of d.timing) selections, cheap bounds that overflowed, selections that
+// left the wide route
+#ifdef FER_STATS
+#define SEL_STAT(k)                                                                        \
+    do {                                                                                   \
+        if (stat && lane == 0) atomicAdd((unsigned long long *)&stat[k], 1ull);            \
+    } while (0)
+#else
+#define SEL_STAT(k) (void)stat
+#endif
+
 // ORDERED = the registers hold the candidates in arrival order (candidate (u, lane) arrived as number u * 64 + lane).  A caller whose
 // candidates sit in any order passes ORDERED = false and arr(u) = the lane's arrival number of candidate u (unique, < 2048): the
 // wide steps only need the number inside the sort key; the binary-search route relies on the register order and is not taken then
 // -- the function returns false and leaves the selection to the caller.
-template <int NB, bool ORDERED, class RAW, class FIN, class ARR>
-__device__ __forceinline__ bool select_topk_ex(const int (&v)[NB], int K, int lane, int *sel, WList &L, RAW raw, FIN fin, ARR arr)
+// COARSE = false starts with the exact bound: for a caller whose coarse bound nearly always overflows (k_me_pre's full evaluation,
+// which runs where the pruned selection has already met more than 64 candidates under the exact bound: 99.6 % by FER_STATS).
+template <int NB, bool ORDERED, bool COARSE, class RAW, class FIN, class ARR>
+__device__ __forceinline__ bool select_topk_ex(const int (&v)[NB], int K, int lane, int *sel, WList &L, RAW raw, FIN fin, ARR arr, long long *stat = nullptr)
 {
     unsigned *A = (unsigned *)sel, *B = A + 64;
     int *Ci = sel + 128, *Di = sel + 192;
@@ -116,7 +141,7 @@ __device__ __forceinline__ bool select_topk_ex(const int (&v)[NB], int K, int la
     int lmin = 0x7fffffff, lmax = -1, total = 0;
 #pragma unroll
     for (int u = 0; u < NB; u++) {
-        total += __popcll(__ballot(v[u] >= 0));
+        total += wave_count(v[u] >= 0);
         lmin = (int)min((unsigned)lmin, (unsigned)v[u]);
         lmax = max(lmax, v[u]);
     }
@@ -124,53 +149,64 @@ __device__ __forceinline__ bool select_topk_ex(const int (&v)[NB], int K, int la
     L.m = INF_M;
     L.xy = 0;
     if (need == 0) return true;
+    SEL_STAT(0);
     int c = 65;
     if (!__any(lmax >= (1 << 26))) {
-        B[lane] = 0xffffffffu;
-        // T0 = the need-th smallest per-lane minimum -- an upper bound of the need-th smallest candidate -- by binary search
-        // over the value: one compare and one scalar population count per step.  (A rank computation over the 64 minima
-        // through LDS cost 130 vector instructions here; these kernels are bound by vector issue, the scalar unit has room.)
+        // T0 = an upper bound of the need-th smallest candidate, below 2^21.  It only filters -- what places the winners is
+        // their exact rank -- so the first bound is a cheap one: the top of the granule (fer_sel_thr.h, 4 significant bits)
+        // that holds the need-th smallest per-lane minimum, found in 8 steps over the lanes' codes.  When that lets more than
+        // 64 candidates through, the exact need-th smallest lane minimum is searched (21 steps over the value) and the
+        // gather runs again.  One compare and one scalar population count per step either way.  (A rank computation over
+        // the 64 minima through LDS cost 130 vector instructions here.)
         int T0 = 0x7fffffff;  // fewer than `need` lanes hold anything: every candidate is needed
-        if (__popcll(__ballot(lmin != 0x7fffffff)) >= need) {
-            int lo = 0, hi = (1 << 21) - 1;
-            if (__popcll(__ballot(lmin <= hi)) >= need) {
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (__popcll(__ballot(lmin <= mid)) >= need)
-                        hi = mid;
-                    else
-                        lo = mid + 1;
+        bool exact = true;
+        if (wave_count(lmin != 0x7fffffff) >= need) {
+            if (wave_count(lmin <= FER_SEL_LIMIT - 1) >= need) {
+                if (COARSE) {
+                    const int lcode = sel_code_of((unsigned)lmin);
+                    T0 = sel_thr(sel_search_bits<FER_SEL_CODE_BITS, FER_SEL_CODE_BITS>(need, [&](int trial) { return wave_count(lcode < trial); }));
+                    exact = false;
+                } else {
+                    T0 = sel_search_bits<21, 1>(need, [&](int trial) { return wave_count(lmin < trial); });
                 }
-                T0 = lo;
             } else {
-                T0 = 1 << 21;  // the general route below
+                T0 = FER_SEL_LIMIT;  // the general route below
             }
         }
-        WAVE_LDS_SYNC();
-        // The candidates <= T0 are gathered in NO particular order (an LDS counter hands out the slots, batches
-        // without survivors cost a compare and a branch); what orders them is the key metric << 11 | arrival index,
-        // exact as long as the survivors' metrics stay below 2^21 (they are the smallest ones; larger takes the
-        // general route).
-        if (T0 < (1 << 21) && NB * 64 <= 2048) {
-            int nsurv = 0;  // (slots from a running scalar count and the lane's rank among the takers of its batch: an LDS
-                            // counter costs a wave-aggregated atomic, twenty instructions, per batch with a survivor)
+        // The candidates <= T0 are gathered in NO particular order (batches without survivors cost a compare and a
+        // branch); what orders them is the key metric << 11 | arrival index, exact as long as the survivors' metrics
+        // stay below 2^21 (they are the smallest ones; larger takes the general route).
+        if (T0 < FER_SEL_LIMIT && NB * 64 <= 2048) {
+            for (;;) {
+                B[lane] = 0xffffffffu;
+                WAVE_LDS_SYNC();
+                int nsurv = 0;  // (slots from a running scalar count and the lane's rank among the takers of its batch: an LDS
+                                // counter costs a wave-aggregated atomic, twenty instructions, per batch with a survivor)
 #pragma unroll
-            for (int u = 0; u < NB; u++) {
-                const bool take = (unsigned)v[u] <= (unsigned)T0;  // (T0 < 2^21: an invalid candidate never passes)
-                const unsigned long long mk = __ballot(take);
-                if (mk) {
-                    const int slot = nsurv + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                    if (take && slot < 64) {
-                        B[slot] = ((unsigned)v[u] << 11) | (unsigned)arr(u);
-                        Ci[slot] = raw(u);
+                for (int u = 0; u < NB; u++) {
+                    const bool take = (unsigned)v[u] <= (unsigned)T0;  // (T0 < 2^21: an invalid candidate never passes)
+                    const unsigned long long mk = __ballot(take);
+                    if (mk) {
+                        const int slot = nsurv + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                        if (take && slot < 64) {
+                            B[slot] = ((unsigned)v[u] << 11) | (unsigned)arr(u);
+                            Ci[slot] = raw(u);
+                        }
+                        nsurv += (int)__builtin_popcountll(mk);
                     }
-                    nsurv += __popcll(mk);
                 }
+                WAVE_LDS_SYNC();
+                c = nsurv;
+                if (c <= 64 || exact) break;
+                // the cheap bound was too loose: the need-th smallest per-lane minimum itself (it is below 2^21: at least
+                // `need` lane minima are <= the bound that was tried)
+                SEL_STAT(1);
+                T0 = sel_search_bits<21, 1>(need, [&](int trial) { return wave_count(lmin < trial); });  // (rare: kept a loop)
+                exact = true;
             }
-            WAVE_LDS_SYNC();
-            c = nsurv;
         }
     }
+    if (c > 64) SEL_STAT(2);
     if (c <= 64) {
         WAVE_LDS_SYNC();
         const unsigned mine = B[lane];
@@ -249,11 +285,18 @@ __device__ __forceinline__ bool select_topk_ex(const int (&v)[NB], int K, int la
     WAVE_LDS_SYNC();
     return true;
 }
-template <int NB, class RAW, class FIN>
-__device__ __forceinline__ void select_topk(const int (&v)[NB], int K, int lane, int *sel, WList &L, RAW raw, FIN fin)
+template <int NB, bool COARSE = true, class RAW, class FIN>
+__device__ __forceinline__ void select_topk(const int (&v)[NB], int K, int lane, int *sel, WList &L, RAW raw, FIN fin, long long *stat = nullptr)
 {
-    select_topk_ex<NB, true>(v, K, lane, sel, L, raw, fin, [&](int u) { return u * 64 + lane; });
+    select_topk_ex<NB, true, COARSE>(v, K, lane, sel, L, raw, fin, [&](int u) { return u * 64 + lane; }, stat);
 }
+// the slots of d.timing that a call site of the selection counts in (-DFER_STATS).  tools/pre_stats.py reads them by these
+// numbers (its SEL_SITES table): change both together.
+#define SEL_SITE_ST1 8
+#define SEL_SITE_ST2 11
+#define SEL_SITE_ST3 14       // k_me_pre behind the pruned wide search
+#define SEL_SITE_ST3_FULL 17  // ... behind the full evaluation
+#define SEL_SITE_N2_HI 20     // one slot: stage-2 selections over all ST2_NB batches (the list runs beyond the first ST2_NB_LO)
 
 // ---- the 9-term feature distance of F/moestimation.cpp:267-276 on packed 16-bit pairs ----
 // A 12-byte record holds (k0,k1) (k2,k3) (k4,0) as u16 pairs, k0 = sum of the 8x8 box and k1..k4 = sums of half
@@ -687,16 +730,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
 #pragma unroll
         for (int u = 0; u < LB; u++) lminl = min(lminl, (unsigned)sel_lds[u * 64 + lane]);
         int T = 0x7fffffff;
-        if (__popcll(__ballot(lminl < (1u << 21))) >= 33) {
-            int lo = 0, hi = (1 << 21) - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (__popcll(__ballot(lminl <= (unsigned)mid)) >= 33)
-                    hi = mid;
-                else
-                    lo = mid + 1;
-            }
-            T = lo;
+        if (wave_count(lminl < (1u << 21)) >= 33) {  // (T is exact: it decides who reaches the full evaluation)
+            T = sel_search_bits<21, 21>(33, [&](int trial) { return wave_count(lminl < (unsigned)trial); });
         }
         int *surv = wide_m;  // arrival numbers of the surviving wide candidates; the row sums are dead
         int ns = 0;
@@ -763,7 +798,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
                 // (the selection's scratch lies behind the survivors in region A: the local metrics stay in region B for
                 // the full evaluation, which has to run when the selection gives up)
                 auto arrv = [&](int u) { return u < 2 ? ar[u < 2 ? u : 0] : wb * 64 + (u - 2) * 64 + lane; };
-                done = select_topk_ex<2 + LB, false>(v, 33, lane, wide_m + 128, L, arrv, fin, arrv);
+                done = select_topk_ex<2 + LB, false, true>(v, 33, lane, wide_m + 128, L, arrv, fin, arrv, d.timing + SEL_SITE_ST3);
             }
         }
         PP_MARK(1)
@@ -844,7 +879,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PRE_WAVES, P
             WAVE_LDS_SYNC();  // the selection reuses sel_lds
             auto raw = [&](int u) { return u * 64 + lane; };  // arrival index
             PP_MARK(2)
-            select_topk<ME_SEL_NB>(v, 33, lane, sel_lds, L, raw, fin);
+            select_topk<ME_SEL_NB, false>(v, 33, lane, sel_lds, L, raw, fin, d.timing + SEL_SITE_ST3_FULL);
         }
         PP_MARK(3)
     } else {
@@ -1527,9 +1562,13 @@ __device__ __forceinline__ void take_best(int best, int bestxy, int &bmin, int &
 #define ST1_UNROLL 7
 #define RES_SPIN_LIMIT (1 << 23)
 
+#define ST2_NB (FER_ST2_CAP / 64)  // 64-candidate batches of a partition's stage-2 list
+#define ST2_NB_LO (ST2_NB / 2)     // ... of which the first ones are read at once: the walk stops after the step that takes its
+                                   // count past 128, so a list rarely runs beyond them
 struct ResPre {  // predictor-independent operands of one partition (res_prefetch: role 1 = all of them, role 0 = the last two lines)
     int n2, n3, n2raw;
-    int2 e2[FER_ST2_CAP / 64];  // a crowded partition: e2[0] = (J, Dmin), e2[1].x = distance-0 candidates listed
+    int2 e2[ST2_NB];  // (batches from ST2_NB_LO on: read when n2raw says the list reaches them, 0 otherwise)
+                      // a crowded partition: e2[0] = (J, Dmin), e2[1].x = distance-0 candidates listed
     int2 z;                     // ... and the lane's distance-0 candidate
     int c3x, c3y, c3s;
     int su[5];
@@ -1551,7 +1590,7 @@ __device__ __forceinline__ void res_prefetch(const FerDev &d, int s, int gx, int
         p.n3 = FER_DBGF(d, 64) ? 0 : d.st3n[pidx];
         const int2 *c2 = (const int2 *)(d.st2 + pidx * FER_ST2_CAP * 2);
 #pragma unroll
-        for (int u = 0; u < FER_ST2_CAP / 64; u++) p.e2[u] = c2[u * 64 + lane];  // slots >= n2 hold stale data, masked later
+        for (int u = 0; u < ST2_NB_LO; u++) p.e2[u] = c2[u * 64 + lane];  // slots >= n2 hold stale data, masked later
         p.z = p.e2[0];  // (a crowded partition: slots 0 .. 32 = its candidates of distance 0, 40 .. 46 = its summary, 64 .. = its list)
         const int *c3 = d.st3 + pidx * 33 * 3;
         const int l3 = min(lane, 32);
@@ -1562,6 +1601,14 @@ __device__ __forceinline__ void res_prefetch(const FerDev &d, int s, int gx, int
 #pragma unroll
     for (int k = 0; k < 5; k++) p.su[k] = d.suma[pidx * 5 + k];
     p.sb = src_block_load(d.curY + (size_t)s * d.ysz, d.W, gx * 8, gy * 8);
+    // The rest of the list only where the count says there is one (a crowded partition's listed candidates lie there too).
+    // EVERY role-1 call waits for the count here before it can take the branch -- behind everything else it has asked for, so
+    // that the wait overlaps those requests -- and the partitions beyond the first batches pay one more round trip on top.
+    if (role == 1 && !d.basic && __builtin_amdgcn_readfirstlane(p.n2raw) > ST2_NB_LO * 64) {
+        const int2 *c2 = (const int2 *)(d.st2 + pidx * FER_ST2_CAP * 2);
+#pragma unroll
+        for (int u = ST2_NB_LO; u < ST2_NB; u++) p.e2[u] = c2[u * 64 + lane];
+    }
 }
 
 // Vectors travel between rows as self-validating 64-bit words in d.chain64 [S][nmb][4]:
@@ -1701,7 +1748,7 @@ __device__ __forceinline__ int stage1_list(const FerDev &d, int s, int gx, int g
         int m[NB1];
 #pragma unroll
         for (int u = 0; u < NB1; u++) m[u] = mtab[u * 64 + lane];
-        select_topk<NB1>(m, 17, lane, sel_lds, L1, raw1, fin1);
+        select_topk<NB1>(m, 17, lane, sel_lds, L1, raw1, fin1, d.timing + SEL_SITE_ST1);
     } else {
         const SuPk sp = su_pack(P.su);
         const IPlanes ip = ip_stream(d, s);
@@ -1817,7 +1864,7 @@ __device__ __forceinline__ void resolve_crowded(const FerDev &d, int s, int sx, 
     }
     if (zc < 33) {
 #pragma unroll
-        for (int u = 1; u < FER_ST2_CAP / 64; u++) {  // the listed candidates: position relative to the block, D | j << 20 | side << 28
+        for (int u = 1; u < ST2_NB; u++) {  // the listed candidates: position relative to the block, D | j << 20 | side << 28
             if ((u - 1) * 64 < np2) {
                 const bool on = (u - 1) * 64 + lane < np2;
                 const int rel = P.e2[u].x;
@@ -1918,16 +1965,27 @@ __device__ __forceinline__ int stage2_list(const FerDev &d, int s, int gx, int g
             return false;
         });
     } else {
-        int m2[FER_ST2_CAP / 64];
-#pragma unroll
-        for (int u = 0; u < FER_ST2_CAP / 64; u++) {
-            int cc = u * 64 + lane;
-            int tx = P.e2[u].x >> 16, ty = (int)(short)(P.e2[u].x & 0xffff);  // k_me_walk stores (tx << 16) | (ty & 0xffff)
-            m2[u] = (int)__umul24((uint32_t)(iabs(tx - genx) + iabs(ty - geny) + 4), (uint32_t)P.e2[u].y) | (cc < P.n2 ? 0 : -1);
-        }
+        // priced and selected over the batches the list reaches (wave-uniform): the first ST2_NB_LO, or all of them
         auto raw2 = [&](int u) { return P.e2[u].x; };
         auto fin2 = [&](int e) { return pack_xy((e >> 16) * 4, (int)(short)(e & 0xffff) * 4); };
-        select_topk<FER_ST2_CAP / 64>(m2, 33, lane, sel_lds, L2, raw2, fin2);
+        auto over = [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            int m2[NB];
+#pragma unroll
+            for (int u = 0; u < NB; u++) {
+                int cc = u * 64 + lane;
+                int tx = P.e2[u].x >> 16, ty = (int)(short)(P.e2[u].x & 0xffff);  // k_me_walk stores (tx << 16) | (ty & 0xffff)
+                m2[u] = (int)__umul24((uint32_t)(iabs(tx - genx) + iabs(ty - geny) + 4), (uint32_t)P.e2[u].y) | (cc < P.n2 ? 0 : -1);
+            }
+            select_topk<NB>(m2, 33, lane, sel_lds, L2, raw2, fin2, d.timing + SEL_SITE_ST2);
+        };
+#ifdef FER_STATS
+        if (lane == 0 && P.n2 > ST2_NB_LO * 64) atomicAdd((unsigned long long *)&d.timing[SEL_SITE_N2_HI], 1ull);
+#endif
+        if (__builtin_amdgcn_readfirstlane(P.n2) <= ST2_NB_LO * 64)
+            over(std::integral_constant<int, ST2_NB_LO>());
+        else
+            over(std::integral_constant<int, ST2_NB>());
     }
     return __popcll(__ballot(lane < 33 && L2.m < 100000000));
 }
